@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native DINER render path: rendered rays/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--scaling auto|weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--scaling auto|weak|strong] [--dump-outputs DIR]
 
 A *step* renders one full target frame per GPU through the product path
 (`diner_amd.NeRFRendererDGS.forward`: depth-guided sampler -> fused projection/gather/fusion-MLP
@@ -92,6 +92,9 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample-rays", type=int, default=0, help="rays of the cpu_baseline sample (0 = the config's default)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline / exact-fp32 / 4096-ray legs")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "fp32"], help="arithmetic of the fusion-MLP GEMMs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the gathered frame: rgb [rays,3], depth [rays]) as float32 "
+                         "DIR/rgb.npy and DIR/depth.npy, so that two builds can be compared output for output")
     # CPU rehearsal of the launcher + sharding + gather + one-line contract (tests/test_bench_launch.py): gloo backend,
     # host tensors and a stub tile producer instead of the HIP render path.  Never a measurement.
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)
@@ -252,6 +255,23 @@ def stub_tile(rays):
     return torch.cat([r[:, 3:6] * 0.5 + 0.5, (r[:, 6:7] + r[:, 7:8]) * 0.5], 1).contiguous()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, frame):
+    """--dump-outputs: the last timed frame [rays, 4] (rgb, depth; float32) as out_dir/rgb.npy [rays, 3] and out_dir/depth.npy
+    [rays].  A frame above DUMP_MAX_BYTES is cut to evenly spaced rays (a fixed sample: the same rays in every run); no
+    configuration of CONFIGS comes near that."""
+    import numpy as np
+    n = frame.shape[0]
+    n_keep = min(n, DUMP_MAX_BYTES // (frame.shape[1] * frame.itemsize))
+    if n_keep < n:
+        frame = frame[np.linspace(0, n - 1, n_keep).astype(np.int64)]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "rgb.npy", np.ascontiguousarray(frame[:, :3], dtype=np.float32))
+    np.save(out_dir / "depth.npy", np.ascontiguousarray(frame[:, 3], dtype=np.float32))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -410,6 +430,9 @@ def main(argv=None):
 
     form = Form(strong)
     elapsed, frame, events = form.timed()
+    if args.dump_outputs and rank == 0:
+        # now, before the extra legs below render into the same double buffer
+        dump_outputs(Path(args.dump_outputs), frame.cpu().numpy())
     stub_ok = form.stub_frame_ok(frame) if stub else None
     n_mine, rpc = form.n_mine, form.rpc
     render_into_tile, og = form.render_into_tile, form.og

@@ -32,3 +32,20 @@ def test_bench_prints_one_contract_line():
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1 and isinstance(c["sample"], str)
     assert d["parity_on_sample"]["frac_rays_rgb_within_1e-4"] >= 0.97
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs: the last timed frame of the real render path, identical in two runs with the same arguments"""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", "tiny", "--steps", "2", "--warmup", "1",
+                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600,
+                           cwd=str(ROOT))
+        assert p.returncode == 0, p.stderr[-2000:]
+        got.append((np.load(tmp_path / d / "rgb.npy"), np.load(tmp_path / d / "depth.npy")))
+    (rgb, depth), (rgb2, depth2) = got
+    assert rgb.shape == (64 * 64, 3) and depth.shape == (64 * 64,) and rgb.dtype == depth.dtype == np.float32
+    assert np.isfinite(rgb).all() and np.isfinite(depth).all() and rgb.std() > 0
+    assert np.array_equal(rgb, rgb2) and np.array_equal(depth, depth2)

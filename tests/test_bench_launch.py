@@ -121,3 +121,38 @@ def test_source_digest_sees_code_not_comments(tmp_path):
     py.write_text("x = 1  # // not C++\n")
     assert bench._code_bytes(a) == bench._code_bytes(b) != bench._code_bytes(c)
     assert bench._code_bytes(py) == py.read_bytes()
+
+
+def _dump(tmp, *extra):
+    p = run("--dump-outputs", str(tmp), *extra)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert json.loads(p.stdout.strip())["stub_frame_ok"] is True
+    import numpy as np
+    assert sorted(f.name for f in tmp.iterdir()) == ["depth.npy", "rgb.npy"]
+    return np.load(tmp / "rgb.npy"), np.load(tmp / "depth.npy")
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_dump_outputs_is_the_last_frame_and_repeatable(tmp_path, gpus):
+    """--dump-outputs writes the last timed frame (the whole gathered frame with N ranks), the same from run to run"""
+    import numpy as np
+    extra = ["--config", "cfg4s", "--gpus", str(gpus), "--scaling", "strong"]
+    rgb, depth = _dump(tmp_path / "a", *extra)
+    assert rgb.shape == (48 * 60, 3) and depth.shape == (48 * 60,)
+    assert rgb.dtype == np.float32 and depth.dtype == np.float32 and np.isfinite(rgb).all() and np.isfinite(depth).all()
+    rgb2, depth2 = _dump(tmp_path / "b", *extra)
+    assert np.array_equal(rgb, rgb2) and np.array_equal(depth, depth2)
+    # cfg4s cycles its target poses step by step: one more timed step is another last frame
+    rgb3, _ = _dump(tmp_path / "c", *extra, "--steps", "3")
+    assert not np.array_equal(rgb, rgb3)
+
+
+def test_dump_outputs_stays_under_64_mb(tmp_path):
+    sys.path.insert(0, str(ROOT))
+    import numpy as np
+    import bench
+    frame = np.arange(5_000_000 * 4, dtype=np.float32).reshape(-1, 4)
+    bench.dump_outputs(tmp_path, frame)
+    rgb, depth = np.load(tmp_path / "rgb.npy"), np.load(tmp_path / "depth.npy")
+    assert rgb.nbytes + depth.nbytes <= 64 << 20 and rgb.shape[0] == depth.shape[0] == (64 << 20) // 16
+    assert np.array_equal(rgb[:, 0] + 3, depth) and depth[0] == 3 and depth[-1] == frame[-1, 3]
