@@ -78,13 +78,9 @@ __device__ __forceinline__ void project(const View &v, float iw, float ih, float
 // the 2^-22 x 16 granularity of the fp16 hi/lo operand split the value goes through next -- for 6 instructions instead of the ~90 of
 // the inlined sinf (with its Payne-Hanek path), 48 times per point and view.  Used by the default (f16x3) inference kernel
 // (points_mlp_f16.hip) and by the training path's point_inputs_kernel (train.hip); the exact-fp32 inference kernel (points_mlp.hip)
-// keeps sinf.  -DDINER_PE_LIBM=1: sinf everywhere.
-#ifndef DINER_PE_LIBM
-#define DINER_PE_LIBM 0
-#endif
+// keeps sinf.  (Tried sinf in the f16x3 paths too: measured 0.5 % slower, not kept.)
 __device__ __forceinline__ float pe_sin(float a)
 {
-    if (DINER_PE_LIBM) return sinf(a);
     const float C_HI = 0.15915494f;                                             // fp32(1 / 2pi)
     const float C_LO = (float)(0.15915494309189535 - (double)0.15915494f);
     const float r1 = a * C_HI;

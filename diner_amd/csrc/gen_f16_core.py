@@ -40,14 +40,11 @@ import sys
 CAP = 96                                        # set by main(): 256 - 128 - 16 * RING
 PRIO = 0                                        # --prio=N: s_setprio N for the S phases, 0 inside the layer blocks
 SPIN_LIMIT = 1 << 18                            # polls before a flow-mode wait gives up (~25 ms; a real wait lasts microseconds)
-PRODS = "small"                                 # --prods=share: W_hi*a_lo, W_hi*a_hi, W_lo*a_hi (neighbours share an operand; probe)
 ORDER = "prod"                                  # --order=acc|prod: MFMA order inside a point tile of a half-step (shape 16)
 SHAPE = 32                                      # --shape=16: v_mfma_f32_16x16x32_f16 (Block16), default v_mfma_f32_32x32x16_f16
-PRIO_B = 0                                      # --priob=N: GEMM priority of waves 4-7 (waves 0-3: 0)
-WBITS = ""                                      # --wbits=nt|sc0|...: cache-policy bits of the weight-stream loads
 STAMPS = False                                  # --stamps: diagnostic layer blocks only (namespace of --ns), 6 s_memtime stamps each (tools/trace_f16.py)
 FLOW = False                                    # --flow: arrival counters in LDS instead of the three workgroup barriers per layer
-SLEEP = 1                                       # --sleep=N: s_sleep between two polls of an arrival counter (N x 64 clocks)
+SLEEP = 1                                       # s_sleep between two polls of an arrival counter (N x 64 clocks)
 X_OFF, NET_OFF, RING_OFF = 0, 64, 128           # relative to CAP
 POISON_OFF = 24                                 # byte offset (from the arrival counters) of the workgroup's poison word, see Block.wait
 
@@ -80,8 +77,8 @@ class Block:
         for tn, w in ((0, "%[w0]"), (1, "%[w1]")):
             if self.noload:
                 continue
-            self.e(f"global_load_dwordx4 {ring(slot, tn, 0)}, %[voff], {w}{WBITS}")
-            self.e(f"global_load_dwordx4 {ring(slot, tn, 1)}, %[voff], {w} offset:1024{WBITS}")
+            self.e(f"global_load_dwordx4 {ring(slot, tn, 0)}, %[voff], {w}")
+            self.e(f"global_load_dwordx4 {ring(slot, tn, 1)}, %[voff], {w} offset:1024")
         self.e("v_add_u32 %[voff], 2048, %[voff]")
 
     def switch_to_next(self):
@@ -204,12 +201,6 @@ class Block:
         self.e(f"v_add_u32 %[voff], {(D - 1) * step}, %[loff]")      # k-blocks 0..D-2 of this layer are already in the ring
         if PRIO:
             self.e("s_setprio 0")                                     # GEMM at low priority: the partner's S phase (VALU, LDS, gather) goes first
-            if PRIO_B:                                                # ... and waves 4-7 (the critical path: they never wait) ahead of waves 0-3
-                self.e("s_cmp_lg_u32 %[half], 0")
-                self.e(f"s_cbranch_scc0 PB{self.nlabel}_%=")
-                self.e(f"s_setprio {PRIO_B}")
-                self.e(f"PB{self.nlabel}_%=:")
-                self.nlabel += 1
         if FLOW:
             self.stamp(0)
             self.signal("half")                                       # my operand rows are written: SA or SB += 1
@@ -263,20 +254,8 @@ class Block16(Block):
     Weight stream of a wave: ONE sequence of half-steps, 4 KiB each: [tf2][hi/lo][lane][8 halfs], lane = 16 kq + r holds
     W[feature 16 (2j + tf2) + r][k = 32 kstep + 8 kq ..+7].  nkb1 / nkb2 count k-steps."""
 
-    def __init__(self, name, acc_base, nks1, nks2, D, region1_off=65536, zero_init=False, convert_tail=False, bias_init=False):
+    def __init__(self, name, acc_base, nks1, nks2, D, region1_off=65536, zero_init=False):
         assert D == 2 and nks1 > 0
-        # bias_init: acc := bias + W a without an initialisation pass -- the first product of every accumulator takes the bias as its C
-        # operand: 4 register quads %[bq0..3] (features 64w + 16tf + 4q ..+3: the same for the 4 point tiles of a lane), read from LDS
-        # by the caller.  The first k-step is peeled off the loop for it.
-        self.bias_init = bias_init
-        assert not (bias_init and zero_init)
-        # convert_tail: the layer's result is needed ONLY as the next layer's operand (net of a residual block: relu -> fp16 hi/lo
-        # split -> LDS).  The relu + split then happens IN PLACE in the layer's last k-step, tile by tile behind the tile's last product
-        # (two tiles later: far beyond the MFMA write -> VALU read wait states), in the shadow of the remaining MFMAs, instead of in the
-        # wave's next S phase, which is on the layer schedule's critical path.  Afterwards registers 0..3 of a tile hold
-        # lo(v0,v1) | hi(v0,v1) | lo(v2,v3) | hi(v2,v3) as packed fp16 pairs; the glue only stores them (store_converted).
-        self.convert_tail = convert_tail
-        self.converting = False
         self.name, self.base, self.nkb1, self.nkb2, self.D = name, acc_base, nks1, nks2, D
         self.region1_off = region1_off
         # zero_init: the accumulators need no initialisation by the caller -- the first product of every accumulator takes the inline
@@ -298,7 +277,7 @@ class Block16(Block):
     def loads(self, slot):
         for i in range(4):                                            # (tf2, part) = (i >> 1, i & 1)
             if not self.noload:
-                self.e(f"global_load_dwordx4 {ring(slot, i >> 1, i & 1)}, %[voff], %[w0] offset:{1024 * i}{WBITS}")
+                self.e(f"global_load_dwordx4 {ring(slot, i >> 1, i & 1)}, %[voff], %[w0] offset:{1024 * i}")
         self.e("v_add_u32 %[voff], 4096, %[voff]")
 
     def switch_to_next(self):
@@ -310,30 +289,16 @@ class Block16(Block):
             self.e(f"ds_read_b128 {self.fr(tp, part)}, %[ab] offset:{imm + 256 * tp + 1024 * part}")
 
     def mfmas16(self, j, tp):
-        prods = ((0, 1), (0, 0), (1, 0)) if PRODS == "share" else ((1, 0), (0, 1), (0, 0))   # default: W_lo*a_hi, W_hi*a_lo, W_hi*a_hi (small terms first)
+        prods = ((1, 0), (0, 1), (0, 0))                            # W_lo*a_hi, W_hi*a_lo, W_hi*a_hi (small terms first)
         pairs = [(p, tf2) for tf2 in range(2) for p in prods] if ORDER == "acc" else [(p, tf2) for p in prods for tf2 in range(2)]
         for (wpart, fpart), tf2 in pairs:                             # --order=acc: the 3 products of an accumulator back to back
             a = self.acc16(2 * j + tf2, tp)
             c = a
             if self.first_step and (wpart, fpart) == prods[0]:        # the accumulator's first product of the layer
-                c = "0" if self.zero_init else f"%[bq{2 * j + tf2}]"  # zero_init / bias_init
+                c = "0"                                               # zero_init
             self.e(f"v_mfma_f32_16x16x32_f16 {a}, {ring(j, tf2, wpart)}, {self.fr(tp, fpart)}, {c}")
 
-    def convert(self, tf, tp):
-        """relu (keeps every NaN, like torch.relu and relu_split4<SAFE>) + hi/lo split of accumulator tile (tf, tp), in place"""
-        r = CAP + self.base + 4 * (4 * tf + tp)
-        for i in range(4):
-            self.e(f"v_cmp_ngt_f32_e64 %[m{i}], 0, v{r + i}")
-        for i in range(4):
-            self.e(f"v_cndmask_b32_e64 v{r + i}, 0, v{r + i}, %[m{i}]")
-        for a, b in ((r, r + 1), (r + 2, r + 3)):
-            self.e(f"v_cvt_pk_f16_f32 %[cva], v{a}, v{b}")
-            self.e(f"v_fma_mixlo_f16 v{a}, %[cva], -1.0, v{a} op_sel_hi:[1,0,0]")                       # lo16 of v_a := f16(v_a - hi_a); the rest of v_a stays
-            self.e(f"v_fma_mixhi_f16 v{a}, %[cva], -1.0, v{b} op_sel:[1,0,0] op_sel_hi:[1,0,0]")       # hi16 of v_a := f16(v_b - hi_b)
-            self.e(f"v_mov_b32 v{b}, %[cva]")
-
     def body(self, tail, switch):
-        done = []                                                     # (tf, tp) of the tiles whose last product has been issued
         for j in range(2):
             self.loads((j + 1) % 2)                                   # the next half-step's weights into the slot just used up
             if switch and j == 0:
@@ -347,29 +312,12 @@ class Block16(Block):
                 self.mfmas16(j, tp)
                 if j == 1 and not tail:
                     self.frag_read(tp)                                # rolling reload: needed again 18 MFMAs from here
-                if self.converting:                                   # the layer's last k-step: convert the tile that finished two tiles ago
-                    for tf2 in range(2):
-                        done.append((2 * j + tf2, tp))
-                    while len(done) > 2:
-                        self.convert(*done.pop(0))
-        if self.converting:
-            self.e("s_nop 15")                                        # the last two tiles: MFMA write -> VALU read wait states
-            self.e("s_nop 7")
-            for t in done:
-                self.convert(*t)
 
     def half(self, nks, region, last_half):
         self.e(f"v_add_u32 %[ab], {self.region1_off * region}, %[ab0]")
         for tp in range(4):
             self.frag_read(tp)                                        # the half's first k-step, behind the barrier / arrival wait
         self.first_step = self.zero_init and region == 0              # (nks == 1 there: the tail body below is the layer's first k-step)
-        peel = self.bias_init and region == 0
-        if peel:                                                      # the layer's first k-step, peeled: C = bias
-            assert nks > 2
-            self.first_step = True
-            self.body(tail=False, switch=False)
-            self.first_step = False
-            nks -= 1
         if nks > 1:
             lbl = f"L{self.nlabel}_%="
             self.nlabel += 1
@@ -379,9 +327,7 @@ class Block16(Block):
             self.e("s_sub_u32 %[cnt], %[cnt], 1")
             self.e("s_cmp_lg_u32 %[cnt], 0")
             self.e(f"s_cbranch_scc1 {lbl}")
-        self.converting = self.convert_tail and last_half
         self.body(tail=True, switch=last_half)
-        self.converting = False
         self.first_step = False
 
 
@@ -396,24 +342,18 @@ def asm_body(lines):
 def cxx(block):
     lines = block.emit()
     frag_ops = ", ".join(f'[f{b}{i}] "=&v"(f{b}{i})' for b in range(2) for i in range(4))
-    cv = getattr(block, "convert_tail", False)
-    cv_decl = "    unsigned cva; unsigned long long m0, m1, m2, m3;\n" if cv else ""
-    cv_outs = ', [cva] "=&v"(cva), [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3)' if cv else ""
-    bi = getattr(block, "bias_init", False)
-    bi_args = ", const f32x4 &bq0, const f32x4 &bq1, const f32x4 &bq2, const f32x4 &bq3" if bi else ""
-    bi_ins = ', [bq0] "v"(bq0), [bq1] "v"(bq1), [bq2] "v"(bq2), [bq3] "v"(bq3)' if bi else ""
     return f"""
 // {block.name}: accumulators v[{CAP + block.base}:{CAP + block.base + 63}], {block.nkb1} + {block.nkb2} k-blocks, ring depth {block.D}
 // w0/w1: this wave's weight streams (feature tile 0/1) of THIS layer; nw0/nw1: of the layer executed next
-__device__ __forceinline__ void {block.name}(uint64_t w0, uint64_t w1, uint64_t nw0, uint64_t nw1, unsigned loff, unsigned ab0, const Sync &sy{bi_args}{", Stamps &st" if STAMPS else ""})
+__device__ __forceinline__ void {block.name}(uint64_t w0, uint64_t w1, uint64_t nw0, uint64_t nw1, unsigned loff, unsigned ab0, const Sync &sy{", Stamps &st" if STAMPS else ""})
 {{
     h8 f00, f01, f02, f03, f10, f11, f12, f13;
     unsigned ab, voff, cnt;
-{cv_decl}{flow_decl()}
+{flow_decl()}
     asm volatile(
 {asm_body(lines)}
-        : {frag_ops}, [ab] "=&v"(ab), [voff] "=&v"(voff), [cnt] "=&s"(cnt), [w0] "+s"(w0), [w1] "+s"(w1){flow_outs()}{cv_outs}{"".join(f', [tk{i}] "=&s"(st.t[{i}])' for i in range(6)) if STAMPS else ""}
-        : [nw0] "s"(nw0), [nw1] "s"(nw1), [loff] "v"(loff), [ab0] "v"(ab0){flow_ins()}{bi_ins}
+        : {frag_ops}, [ab] "=&v"(ab), [voff] "=&v"(voff), [cnt] "=&s"(cnt), [w0] "+s"(w0), [w1] "+s"(w1){flow_outs()}{"".join(f', [tk{i}] "=&s"(st.t[{i}])' for i in range(6)) if STAMPS else ""}
+        : [nw0] "s"(nw0), [nw1] "s"(nw1), [loff] "v"(loff), [ab0] "v"(ab0){flow_ins()}
         : "memory", "scc", {clobbers(block.D)});
 }}
 """
@@ -619,17 +559,13 @@ def main():
     global CAP, PRIO
     CAP = 256 - 128 - 16 * D
     PRIO = next((int(a.split('=', 1)[1]) for a in sys.argv[1:] if a.startswith('--prio=')), 0)
-    global FLOW, STAMPS, WBITS, PRIO_B, SHAPE, ORDER, PRODS, SLEEP
-    SLEEP = next((int(a.split('=', 1)[1]) for a in sys.argv[1:] if a.startswith('--sleep=')), 1)
-    PRODS = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--prods=')), "small")
+    global FLOW, STAMPS, SHAPE, ORDER
     ORDER = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--order=')), "prod")
     SHAPE = next((int(a.split('=', 1)[1]) for a in sys.argv[1:] if a.startswith('--shape=')), 32)
     assert SHAPE in (16, 32)
     B_ = Block16 if SHAPE == 16 else Block
     NK = 8 if SHAPE == 16 else 16                  # k-steps (32 k) / k-blocks (16 k) per half of a 512-wide layer
     NKI = 1 if SHAPE == 16 else 2                  # ... of lin_in (64 inputs)
-    PRIO_B = next((int(a.split('=', 1)[1]) for a in sys.argv[1:] if a.startswith('--priob=')), 0)
-    WBITS = next((" " + a.split("=", 1)[1].replace(",", " ") for a in sys.argv[1:] if a.startswith("--wbits=")), "")
     FLOW = '--flow' in sys.argv
     STAMPS = '--stamps' in sys.argv
     if STAMPS:
@@ -639,9 +575,6 @@ def main():
                f"namespace {ns} {{\nstruct Stamps {{ unsigned long long t[6]; }};\n"]
         out.append(cxx(B_("layer_x_full", X_OFF, NK, NK, D)))
         out.append(cxx(B_("layer_net_full", NET_OFF, NK, NK, D)))
-        if SHAPE == 16:
-            out.append(cxx(B_("layer_net_full_cv", NET_OFF, NK, NK, D, convert_tail=True)))
-            out.append(cxx(B_("layer_net_full_b", NET_OFF, NK, NK, D, bias_init=True)))
         out.append(cxx(B_("layer_x_in", X_OFF, NKI, NKI, D, region1_off=8192)))
         if SHAPE == 16:
             out.append(cxx(B_("layer_x_in0", X_OFF, NKI, NKI, D, region1_off=8192, zero_init=True)))
@@ -660,9 +593,6 @@ constexpr int F16_X = {CAP + X_OFF}, F16_NET = {CAP + NET_OFF};   // first regis
     out.append(prologue(D))
     out.append(cxx(B_("layer_x_full", X_OFF, NK, NK, D)))
     out.append(cxx(B_("layer_net_full", NET_OFF, NK, NK, D)))
-    if SHAPE == 16:   # net = W0 relu(x) + b0 whose only reader is fc_1's operand: relu + split in the block's last k-step (convert_tail)
-        out.append(cxx(B_("layer_net_full_cv", NET_OFF, NK, NK, D, convert_tail=True)))
-        out.append(cxx(B_("layer_net_full_b", NET_OFF, NK, NK, D, bias_init=True)))     # net := b0 + W0 relu(x), the bias as the first C operand
     # lin_in: 64 inputs = 4 k-blocks; waves 0-3 write unit-rows 0-3 (k < 32), waves 4-7 unit-rows 4-7 (8 KiB further)
     if D == 2:   # (the ring-4 build is a probe-only variant: tools/chain_probe.hip)
         out.append(cxx(B_("layer_x_in", X_OFF, NKI, NKI, D, region1_off=8192)))

@@ -38,10 +38,7 @@ constexpr int IMG_BYTES = 128 * 1024;
 constexpr int LDS_CTR = IMG_BYTES;                      // the core's arrival counters
 constexpr int LDS_BYTES = LDS_CTR + 64;
 constexpr int X = F16_X, NET = F16_NET;
-#ifndef DINER_DEPHASE
-#define DINER_DEPHASE 4
-#endif
-constexpr int DEPHASE = DINER_DEPHASE, DEPHASE_CYCLES = 65024;   // ~ one tile period (8 x 8128 cycles of s_sleep 127)
+constexpr int DEPHASE = 4, DEPHASE_CYCLES = 65024;   // ~ one tile period (8 x 8128 cycles of s_sleep 127)
 
 struct Args {
     const float *A;
@@ -191,6 +188,7 @@ __global__ __launch_bounds__(NWAVES * 64) __attribute__((amdgpu_num_vgpr(F16_VGP
     // De-phase the workgroups: every tile is a memory phase (epilogue + operand load: 256 KiB per CU) followed by a GEMM phase, and
     // workgroups that start together stay in lockstep -- HBM saturated during the memory phases and idle during the GEMMs.
     // A start delay of (blockIdx % DEPHASE) / DEPHASE of a tile period spreads the memory phases over the period.
+    // (Tried other spreads: measured no change, not kept.)
     for (int d = 0; d < (int)(blockIdx.x % DEPHASE) * (DEPHASE_CYCLES / DEPHASE / 8128); ++d) __builtin_amdgcn_s_sleep(127);
 #pragma unroll 1
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {

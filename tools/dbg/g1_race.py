@@ -1,4 +1,4 @@
-"""Hunt for a rare, timing-dependent mismatch (points_mlp_f16.hip, DINER_GEOM_WAVES): REPS fresh processes, each rendering goldens g1 / g3 / g0
+"""Hunt for a rare, timing-dependent mismatch (points_mlp_f16.hip; first seen in 4-wave geometry builds): REPS fresh processes, each rendering goldens g1 / g3 / g0
 through render_points twice per variant (lin_z as per-point GEMMs and as maps; the first renders of a process run with cold caches);
 prints per render the number of samples beyond 1e-4 (@ray.sample of the first ones).  usage: [REPS=12] g1_race.py lib [lib ...]"""
 import os, subprocess, sys
