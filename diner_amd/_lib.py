@@ -18,7 +18,7 @@ _FP = C.c_void_p  # device pointers travel as integers
 
 N_BLOCKS, COMBINE = 5, 3
 # the ABI version THIS binding (the argument lists in SYMBOLS below) is written against = DINER_ABI_VERSION of include/diner_hip.h
-ABI_VERSION = 2
+ABI_VERSION = 3
 PRECISIONS = {"fp32": 0, "f16x3": 1}
 
 
@@ -45,6 +45,20 @@ class DinerTargetCam(C.Structure):
 class DinerSamplerCfg(C.Structure):
     _fields_ = [("n_candidates", C.c_int32), ("n_samples", C.c_int32), ("n_gaussian", C.c_int32),
                 ("depth_diff_max", C.c_float)]
+
+
+class DinerMlpShape(C.Structure):
+    _fields_ = [("d_in", C.c_int32), ("d_latent", C.c_int32), ("d_hidden", C.c_int32), ("n_blocks", C.c_int32),
+                ("combine_layer", C.c_int32), ("num_freqs", C.c_int32), ("beta", C.c_float), ("d_out", C.c_int32),
+                ("combine_type", C.c_int32)]
+
+
+class DinerMlpGenRaw(C.Structure):
+    _fields_ = [("lin_in_w", _FP), ("lin_in_b", _FP),
+                ("lin_z_w", C.POINTER(_FP)), ("lin_z_b", C.POINTER(_FP)),
+                ("fc0_w", C.POINTER(_FP)), ("fc0_b", C.POINTER(_FP)),
+                ("fc1_w", C.POINTER(_FP)), ("fc1_b", C.POINTER(_FP)),
+                ("lin_out_w", _FP), ("lin_out_b", _FP)]
 
 
 # every symbol include/diner_hip.h declares: name -> (restype, argtypes)
@@ -90,6 +104,13 @@ SYMBOLS = {
                                      _P, _P, _P, _P, _P, _P, _P]),
     "diner_render": (C.c_int, [C.POINTER(DinerScene), _P, _P, _I64, C.POINTER(DinerSamplerCfg), _I32, _I32,
                                _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_mlp_gen_packed_floats": (_I64, [C.POINTER(DinerMlpShape)]),
+    "diner_pack_mlp_gen": (C.c_int, [C.POINTER(DinerMlpShape), C.POINTER(DinerMlpGenRaw), _P, _P]),
+    "diner_render_points_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, _P, _P, _I64, _I32, _P, _P]),
+    "diner_render_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, _P, _I64, C.POINTER(DinerSamplerCfg), _I32,
+                                   _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, C.POINTER(DinerTargetCam),
+                                         C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

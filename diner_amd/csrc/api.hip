@@ -107,6 +107,12 @@ int64_t mlp_f16_packed_floats();
 int launch_pack_mlp_f16(const DinerMlpRaw &, float *, hipStream_t);
 int launch_points_mlp_f16(const DinerScene &, const float *, const float *, const float *, int64_t, int, float *, float *, hipStream_t);
 int64_t points_mlp_f16_scratch_floats(int64_t SB, int NV);
+namespace gen {
+int check_shape(const DinerMlpShape &);
+int64_t packed_floats(const DinerMlpShape &);
+int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+}
 
 static int bad(const char *msg)
 {
@@ -437,6 +443,80 @@ int diner_render_image(const DinerScene *scene, const float *mlp_packed, const D
                              (hipStream_t)stream)))
         return rc;
     if ((rc = diner_render_points(scene, mlp_packed, rays, z, NR, cfg->n_samples, precision, scratch, rgbsigma, stream))) return rc;
+    return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
+}
+
+/* ---- shape-general inference path (points_mlp_gen.hip) ---------------------------------------------------------------- */
+int64_t diner_mlp_gen_packed_floats(const DinerMlpShape *shape)
+{
+    if (!shape) return bad("mlp_gen_packed_floats: shape is NULL");
+    const int rc = gen::check_shape(*shape);
+    return rc ? rc : gen::packed_floats(*shape);
+}
+
+int diner_pack_mlp_gen(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, float *packed_out, void *stream)
+{
+    if (!shape || !raw || !packed_out) return bad("pack_mlp_gen: NULL pointer");
+    int rc;
+    if ((rc = gen::check_shape(*shape))) return rc;
+    const int nlz = shape->combine_layer < shape->n_blocks ? shape->combine_layer : shape->n_blocks;
+    if (!raw->lin_in_w || !raw->lin_in_b || !raw->lin_out_w || !raw->lin_out_b) return bad("pack_mlp_gen: NULL weight pointer");
+    if ((nlz && (!raw->lin_z_w || !raw->lin_z_b)) || !raw->fc0_w || !raw->fc0_b || !raw->fc1_w || !raw->fc1_b) return bad("pack_mlp_gen: NULL layer array");
+    for (int b = 0; b < nlz; ++b)
+        if (!raw->lin_z_w[b] || !raw->lin_z_b[b]) return bad("pack_mlp_gen: NULL lin_z pointer");
+    for (int b = 0; b < shape->n_blocks; ++b)
+        if (!raw->fc0_w[b] || !raw->fc0_b[b] || !raw->fc1_w[b] || !raw->fc1_b[b]) return bad("pack_mlp_gen: NULL block pointer");
+    return gen::launch_pack_mlp(*shape, *raw, packed_out, (hipStream_t)stream);
+}
+
+int diner_render_points_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, const float *z,
+                            int64_t NR, int32_t K, float *rgbsigma_out, void *stream)
+{
+    int rc;
+    if (!shape) return bad("render_points_gen: shape is NULL");
+    if ((rc = gen::check_shape(*shape))) return rc;
+    if ((rc = check_scene(scene, shape->combine_layer > 0))) return rc;
+    if (NR < 0 || K < 1) return bad("render_points_gen: bad NR / K");
+    if (!mlp_packed) return bad("render_points_gen: mlp_packed is NULL");
+    if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points_gen: NULL rays / z / out");
+    return gen::launch_points_mlp(*scene, *shape, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
+}
+
+int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, int64_t NR,
+                     const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss, const float *u_fill,
+                     uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
+{
+    int rc;
+    if (!shape) return bad("render_gen: shape is NULL");
+    if ((rc = gen::check_shape(*shape)) || (rc = check_scene(scene, shape->combine_layer > 0)) || (rc = check_cfg(cfg))) return rc;
+    if (NR < 0) return bad("NR < 0");
+    if (NR == 0 || scene->SB == 0) return DINER_OK;
+    if (!workspace) return bad("render_gen: workspace is NULL");
+    const int64_t N = (int64_t)scene->SB * NR;
+    float *z = workspace, *rgbsigma = workspace + N * cfg->n_samples;
+    if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr, nullptr, stream))) return rc;
+    if ((rc = diner_render_points_gen(scene, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
+}
+
+int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const DinerTargetCam *cam,
+                           const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out, float *rgb_out,
+                           float *depth_out, float *weights_out, uint32_t *status, void *stream)
+{
+    int rc;
+    if (!shape) return bad("render_image_gen: shape is NULL");
+    if ((rc = gen::check_shape(*shape)) || (rc = check_scene(scene, shape->combine_layer > 0)) || (rc = check_cfg(cfg))) return rc;
+    if (!cam || !cam->extrinsics || !cam->intrinsics || !cam->z_near || !cam->z_far) return bad("render_image_gen: NULL camera");
+    if (cam->H <= 0 || cam->W <= 0) return bad("render_image_gen: bad image size");
+    if (scene->SB == 0) return DINER_OK;
+    if (!workspace) return bad("render_image_gen: workspace is NULL");
+    const int64_t NR = (int64_t)cam->H * cam->W, N = (int64_t)scene->SB * NR;
+    float *rays = rays_out ? rays_out : workspace;
+    float *z = workspace + N * 8, *rgbsigma = z + N * cfg->n_samples;
+    if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
+                             (hipStream_t)stream)))
+        return rc;
+    if ((rc = diner_render_points_gen(scene, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 

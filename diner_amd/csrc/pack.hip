@@ -38,6 +38,22 @@ __global__ __launch_bounds__(256) void pack_latent_kernel(const float *__restric
     }
 }
 
+// the same for any other channel count (the shape-general path, C a multiple of 8 up to 1024): 32 pixels x 32 channels per block
+__global__ __launch_bounds__(256) void pack_latent_any_kernel(const float *__restrict__ in, int C, int64_t hw, float *__restrict__ out)
+{
+    __shared__ float tile[32][33];
+    const int64_t img = blockIdx.z, p0 = (int64_t)blockIdx.x * 32;
+    const int c0 = blockIdx.y * 32;
+    const float *src = in + img * C * hw;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int c = ty; c < 32; c += 8)
+        tile[c][tx] = (c0 + c < C && p0 + tx < hw) ? src[(int64_t)(c0 + c) * hw + p0 + tx] : 0.f;
+    __syncthreads();
+    float *dst = out + img * hw * C;
+    for (int p = ty; p < 32; p += 8)
+        if (p0 + p < hw && c0 + tx < C) dst[(p0 + p) * C + c0 + tx] = tile[tx][p];
+}
+
 int launch_pack_maps(const float *d, const float *s, const float *n, int64_t N, int H, int W, float *out,
                      hipStream_t st)
 {
@@ -50,9 +66,18 @@ int launch_pack_maps(const float *d, const float *s, const float *n, int64_t N, 
 
 int launch_pack_latent(const float *in, int64_t N, int C, int h, int w, float *out, hipStream_t st)
 {
-    if (C != DINER_D_LATENT) { set_error("pack_latent: C=%d unsupported (need %d)", C, DINER_D_LATENT); return DINER_E_UNSUPPORTED; }
+    if (C != DINER_D_LATENT && (C < 8 || C > 1024 || C % 8)) {
+        set_error("pack_latent: C=%d unsupported (%d, or a multiple of 8 up to 1024)", C, DINER_D_LATENT);
+        return DINER_E_UNSUPPORTED;
+    }
     const int64_t hw = (int64_t)h * w;
     if (N * hw == 0) return DINER_OK;
+    if (C != DINER_D_LATENT) {
+        if (N > 65535) { set_error("pack_latent: N=%lld images unsupported for C=%d", (long long)N, C); return DINER_E_UNSUPPORTED; }
+        hipLaunchKernelGGL(pack_latent_any_kernel, dim3((unsigned)((hw + 31) / 32), (unsigned)(C / 32 + (C % 32 != 0)), (unsigned)N), dim3(256),
+                           0, st, in, C, hw, out);
+        return check_launch("pack_latent_any_kernel");
+    }
     hipLaunchKernelGGL(pack_latent_kernel<DINER_D_LATENT>, dim3((unsigned)((hw + 31) / 32), (unsigned)N), dim3(256), 0, st,
                        in, hw, out);
     return check_launch("pack_latent_kernel");

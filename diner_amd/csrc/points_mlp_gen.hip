@@ -1,0 +1,452 @@
+// Shape-general fused per-point evaluation: the job of points_mlp_kernel (points_mlp.hip) -- multi-view projection, positional
+// encodings, bilinear latent gather, the ResnetFC fusion MLP and the sigmoid/relu head -- for any MLP shape the reference's
+// constructors accept within the envelope below, described at RUN time by a DinerMlpShape instead of compile-time constants:
+//   PixelNeRF.forward            src/models/pixelnerf.py:55-145 (d_in = PE3 (3+6F) + viewdir 3 + PE1 (1+2F))
+//   PositionalEncoding.forward   src/models/positional_encoding.py:33-53 (num_freqs F >= 1, include_input)
+//   SpatialEncoder.index         src/models/image_encoder.py:97-127 (d_latent = the encoder's channel count)
+//   ResnetFC.forward             src/models/resnetfc.py:129-159 (d_hidden, n_blocks, combine_layer, ReLU or Softplus(beta))
+//
+// Envelope: d_hidden in {32, 64, ..., 512}; d_latent a multiple of 8 up to 1024; n_blocks >= 1; combine_layer >= 0 (>= n_blocks:
+// no mean over views, NV must be 1 -- pixelnerf.py:137 reshapes (SB,NV,B,4) to (SB,B,4)); d_in = 7 + 8F <= 512; d_out = 4.
+//
+// Arithmetic and structure are those of points_mlp_kernel (exact fp32 v_mfma_f32_32x32x2_f32, the same k order, the same bias /
+// residual / mean order), so at the standard shape this kernel computes the same values; what changes is that the layer widths are
+// loop bounds:
+//   * 64 points per workgroup, 8 waves; the output columns of a layer are 32-wide tiles (NT = d_hidden / 32) distributed over the
+//     waves by one of three instantiations <RB row blocks, CT column tiles per wave>: <1,1> for NT <= 4, <2,1> for NT <= 8,
+//     <2,2> for NT <= 16.  A wave whose tile index passes NT-1 reads the last tile again and discards its result (uniform);
+//   * the A operand of every layer is staged in one 128-KiB LDS image [k/8][k%2][row][(k/2)%4] of 512 columns; the latent GEMM
+//     (d_latent up to 1024) runs in 512-column pieces: gather a piece, multiply, gather the next;
+//   * weights are packed per layer in the B-fragment order of points_mlp.hip (diner_pack_mlp_gen) and streamed from L2 with one
+//     k-block of prefetch;
+//   * views are processed one after another; the hidden state, `net` and the running view-sum stay in registers.
+#include "common.hpp"
+
+namespace diner {
+namespace gen {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TILE_P = 64;                     // points per workgroup
+constexpr int NWAVES = 8;                      // waves per workgroup
+constexpr int KMAX = 512;                      // columns of the LDS A image
+constexpr int A_F4 = KMAX / 8 * 2 * TILE_P;    // float4 entries of the A image (8192 = 128 KiB)
+
+// ---- packed weight image ---------------------------------------------------------------------------------------------------------
+// layers in order lin_in | lin_z[0..nlz) | fc_0[0..nb) | fc_1[0..nb) | lin_out, each [col_tile][jb][lane][4]: lane = h*32+c holds
+// W[n = 32*col_tile + c][k = 8*jb + 2*ji + h], ji = 0..3 (zero outside the layer); then the biases: lin_in | lin_z[b] | fc_0[b] |
+// fc_1[b] (d_hidden floats each) | lin_out padded to 32.
+struct Layout {
+    int H, NT;             // d_hidden, 32-column tiles
+    int din, njb_in;       // d_in (7 + 8F), its k-blocks of 8
+    int dlat, njb_lat;     // d_latent, its k-blocks
+    int nb, cl, nlz, nvb;  // n_blocks, combine_layer, lin_z layers = min(cl, nb), blocks evaluated per view = nlz
+    int F;                 // num_freqs
+    float beta;            // Softplus beta, 0 = ReLU
+    int64_t w_in, w_z, w_h, w_out;              // floats of one layer of each kind
+    int64_t off_in, off_z, off_fc0, off_fc1, off_out, off_bias, total;
+    __host__ __device__ int bias_lin_in() const { return 0; }
+    __host__ __device__ int bias_lin_z(int b) const { return (1 + b) * H; }
+    __host__ __device__ int bias_fc0(int b) const { return (1 + nlz + b) * H; }
+    __host__ __device__ int bias_fc1(int b) const { return (1 + nlz + nb + b) * H; }
+    __host__ __device__ int bias_lin_out() const { return (1 + nlz + 2 * nb) * H; }
+};
+
+static Layout layout_of(const DinerMlpShape &m)
+{
+    Layout L;
+    L.H = m.d_hidden; L.NT = m.d_hidden / 32;
+    L.din = m.d_in; L.njb_in = (m.d_in + 7) / 8;
+    L.dlat = m.d_latent; L.njb_lat = m.d_latent / 8;
+    L.nb = m.n_blocks; L.cl = m.combine_layer; L.nlz = m.combine_layer < m.n_blocks ? m.combine_layer : m.n_blocks; L.nvb = L.nlz;
+    L.F = m.num_freqs; L.beta = m.beta;
+    L.w_in = (int64_t)L.NT * L.njb_in * 256;
+    L.w_z = (int64_t)L.NT * L.njb_lat * 256;
+    L.w_h = (int64_t)L.NT * (L.H / 8) * 256;
+    L.w_out = (int64_t)(L.H / 8) * 256;
+    L.off_in = 0;
+    L.off_z = L.off_in + L.w_in;
+    L.off_fc0 = L.off_z + L.nlz * L.w_z;
+    L.off_fc1 = L.off_fc0 + L.nb * L.w_h;
+    L.off_out = L.off_fc1 + L.nb * L.w_h;
+    L.off_bias = L.off_out + L.w_out;
+    L.total = L.off_bias + (int64_t)(1 + L.nlz + 2 * L.nb) * L.H + 32;
+    return L;
+}
+
+// DINER_OK, or DINER_E_UNSUPPORTED with the reason in diner_last_error()
+int check_shape(const DinerMlpShape &m)
+{
+    if (m.d_out != 4) { set_error("mlp shape: d_out=%d unsupported (PixelNeRF's head is rgb + sigma: 4)", m.d_out); return DINER_E_UNSUPPORTED; }
+    if (m.combine_type != DINER_COMBINE_AVERAGE) { set_error("mlp shape: combine_type %d unsupported (only 'average', resnetfc.py:9-14)", m.combine_type); return DINER_E_UNSUPPORTED; }
+    if (m.d_hidden < 32 || m.d_hidden > 512 || m.d_hidden % 32) { set_error("mlp shape: d_hidden=%d unsupported (a multiple of 32 in [32, 512])", m.d_hidden); return DINER_E_UNSUPPORTED; }
+    if (m.d_latent < 8 || m.d_latent > 1024 || m.d_latent % 8) { set_error("mlp shape: d_latent=%d unsupported (a multiple of 8 in [8, 1024])", m.d_latent); return DINER_E_UNSUPPORTED; }
+    if (m.n_blocks < 1 || m.n_blocks > 64) { set_error("mlp shape: n_blocks=%d unsupported (1..64)", m.n_blocks); return DINER_E_UNSUPPORTED; }
+    if (m.combine_layer < 0) { set_error("mlp shape: combine_layer=%d unsupported (>= 0)", m.combine_layer); return DINER_E_UNSUPPORTED; }
+    if (m.num_freqs < 1 || 7 + 8 * m.num_freqs > KMAX) { set_error("mlp shape: num_freqs=%d unsupported (1..63)", m.num_freqs); return DINER_E_UNSUPPORTED; }
+    if (m.d_in != 7 + 8 * m.num_freqs) { set_error("mlp shape: d_in=%d does not match num_freqs=%d (PixelNeRF: d_in = 7 + 8 * num_freqs)", m.d_in, m.num_freqs); return DINER_E_UNSUPPORTED; }
+    if (!(m.beta >= 0.0f) || !(m.beta < __builtin_inff())) { set_error("mlp shape: beta must be finite and >= 0 (0 = ReLU)"); return DINER_E_UNSUPPORTED; }
+    return DINER_OK;
+}
+
+int64_t packed_floats(const DinerMlpShape &m) { return layout_of(m).total; }
+
+// one thread per packed float of one layer
+__global__ void pack_layer_kernel(const float *__restrict__ w, int in_dim, int out_dim, int njb, int64_t n, float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int ji = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    const int64_t blk = i >> 8;
+    const int jb = (int)(blk % njb), tile = (int)(blk / njb);
+    const int r = tile * 32 + (lane & 31), k = jb * 8 + ji * 2 + (lane >> 5);
+    out[i] = (r < out_dim && k < in_dim) ? w[(int64_t)r * in_dim + k] : 0.0f;
+}
+
+__global__ void pack_bias_kernel(const float *__restrict__ b, int n, int npad, float *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < npad) out[i] = i < n ? b[i] : 0.0f;
+}
+
+static int pack_layer(const float *w, int in_dim, int out_dim, int njb, int tiles, float *out, hipStream_t st)
+{
+    const int64_t n = (int64_t)tiles * njb * 256;
+    hipLaunchKernelGGL(pack_layer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, in_dim, out_dim, njb, n, out);
+    return check_launch("pack_layer_kernel");
+}
+
+static int pack_bias(const float *b, int n, int npad, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(pack_bias_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st, b, n, npad, out);
+    return check_launch("pack_bias_kernel");
+}
+
+int launch_pack_mlp(const DinerMlpShape &m, const DinerMlpGenRaw &raw, float *out, hipStream_t st)
+{
+    const Layout L = layout_of(m);
+    int rc;
+    float *bias = out + L.off_bias;
+    if ((rc = pack_layer(raw.lin_in_w, L.din, L.H, L.njb_in, L.NT, out + L.off_in, st))) return rc;
+    if ((rc = pack_bias(raw.lin_in_b, L.H, L.H, bias + L.bias_lin_in(), st))) return rc;
+    for (int b = 0; b < L.nlz; ++b) {
+        if ((rc = pack_layer(raw.lin_z_w[b], L.dlat, L.H, L.njb_lat, L.NT, out + L.off_z + b * L.w_z, st))) return rc;
+        if ((rc = pack_bias(raw.lin_z_b[b], L.H, L.H, bias + L.bias_lin_z(b), st))) return rc;
+    }
+    for (int b = 0; b < L.nb; ++b) {
+        if ((rc = pack_layer(raw.fc0_w[b], L.H, L.H, L.H / 8, L.NT, out + L.off_fc0 + b * L.w_h, st))) return rc;
+        if ((rc = pack_bias(raw.fc0_b[b], L.H, L.H, bias + L.bias_fc0(b), st))) return rc;
+        if ((rc = pack_layer(raw.fc1_w[b], L.H, L.H, L.H / 8, L.NT, out + L.off_fc1 + b * L.w_h, st))) return rc;
+        if ((rc = pack_bias(raw.fc1_b[b], L.H, L.H, bias + L.bias_fc1(b), st))) return rc;
+    }
+    if ((rc = pack_layer(raw.lin_out_w, L.H, 4, L.H / 8, 1, out + L.off_out, st))) return rc;
+    return pack_bias(raw.lin_out_b, 4, 32, bias + L.bias_lin_out(), st);
+}
+
+// ---- LDS A image (points_mlp.hip) -------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int a_off(int row, int k) { return ((((k >> 3) * 2 + (k & 1)) * TILE_P + row) << 2) + ((k >> 1) & 3); }
+
+// acc[tm][tn] += A[rows of row block rb0 + tm] x W^T over k-blocks jb0 .. jb0 + njb of the layer (A image column 0 = k-block jb0).
+// Wl: packed layer of njb_layer k-blocks per column tile; this wave's tiles ct0 .. ct0 + CT - 1 (clamped to NT - 1).
+template <int RB, int CT>
+__device__ __forceinline__ void gemm(f32x16 (&acc)[RB][CT], const f32x4 *A4, const f32x4 *__restrict__ Wl, int njb_layer, int jb0,
+                                     int njb, int rb0, int ct0, int NT, int lane)
+{
+    const f32x4 *ap = A4 + (lane >> 5) * TILE_P + rb0 * 32 + (lane & 31);
+    const f32x4 *bp[CT];
+#pragma unroll
+    for (int tn = 0; tn < CT; ++tn) {
+        const int t = ct0 + tn < NT ? ct0 + tn : NT - 1;
+        bp[tn] = Wl + ((int64_t)t * njb_layer + jb0) * 64 + lane;
+    }
+    f32x4 b_cur[CT], b_nxt[CT];
+#pragma unroll
+    for (int tn = 0; tn < CT; ++tn) b_cur[tn] = bp[tn][0];
+#pragma unroll 2
+    for (int jb = 0; jb < njb; ++jb) {
+        const int jn = jb + 1 < njb ? jb + 1 : jb;  // last iteration re-loads (harmless, keeps the loop branch-free)
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn) b_nxt[tn] = bp[tn][jn * 64];
+        f32x4 a[RB];
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm) a[tm] = ap[jb * 2 * TILE_P + 32 * tm];
+#pragma unroll
+        for (int ji = 0; ji < 4; ++ji)
+#pragma unroll
+            for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+                for (int tm = 0; tm < RB; ++tm)
+                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm][ji], b_cur[tn][ji], acc[tm][tn], 0, 0, 0);
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn) b_cur[tn] = b_nxt[tn];
+    }
+}
+
+template <int RB, int CT>
+__device__ __forceinline__ void acc_bias(f32x16 (&acc)[RB][CT], const float *__restrict__ bias, bool add, int ct0, int NT, int lane)
+{
+#pragma unroll
+    for (int tn = 0; tn < CT; ++tn) {
+        const int t = ct0 + tn < NT ? ct0 + tn : NT - 1;
+        const float b = bias[t * 32 + (lane & 31)];
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[tm][tn][i] = add ? acc[tm][tn][i] + b : b;
+    }
+}
+
+// Softplus(beta) as torch evaluates it (x * beta > 20: linear); a NaN stays NaN
+__device__ __forceinline__ float softplus(float v, float beta)
+{
+    const float xb = v * beta;
+    return xb > 20.0f ? v : log1pf(expf(xb)) / beta;
+}
+
+// activation(acc) -> LDS A image: this wave's columns become k = 32 * tile + c of the next layer (resnetfc.py:62-63,158)
+template <int RB, int CT>
+__device__ __forceinline__ void store_act(const f32x16 (&acc)[RB][CT], float *A, float beta, int rb0, int ct0, int NT, int lane)
+{
+    const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int tn = 0; tn < CT; ++tn) {
+        if (ct0 + tn >= NT) continue;
+        const int k = (ct0 + tn) * 32 + c;
+        float *col = A + ((((k >> 3) * 2 + (k & 1)) * TILE_P) << 2) + ((k >> 1) & 3);
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm) {
+            const int r0 = (rb0 + tm) * 32 + 4 * h;
+            if (beta > 0.0f) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) col[(r0 + 8 * (i >> 2) + (i & 3)) << 2] = softplus(acc[tm][tn][i], beta);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {   // C/D layout of the 32x32 MFMA; keeps NaN, like torch.relu
+                    const float v = acc[tm][tn][i];
+                    col[(r0 + 8 * (i >> 2) + (i & 3)) << 2] = v < 0.0f ? 0.0f : v;
+                }
+            }
+        }
+    }
+}
+
+struct Tap {        // bilinear footprint of one (point, view) in the latent map
+    int o00, o01, o10, o11;  // float4 offsets of the 4 texels (clamped, always readable)
+    float nw, ne, sw, se;    // weights; a tap outside the map has its weight forced to 0
+};
+
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                     const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                     int64_t NR, int K, float *__restrict__ rgbsigma)
+{
+    __shared__ f32x4 lds[A_F4 + TILE_P * 2];  // A image + one Tap per row
+    f32x4 *A4 = lds;
+    float *A = (float *)lds;
+    Tap *taps = (Tap *)(lds + A_F4);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rb0 = RB == 2 ? 0 : (wave & 1), ct0 = RB == 2 ? wave * CT : (wave >> 1) * CT;
+    const int NT = L.NT, H = L.H;
+    const int sb = blockIdx.y;
+    const int64_t P = NR * (int64_t)K;
+    int64_t tile;   // XCD-aware tile order (points_mlp.hip)
+    {
+        const int64_t nwg = gridDim.x, b = blockIdx.x, q = nwg / 8, r = nwg % 8, xcd = b % 8;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+    }
+    const float *bias = Wp + L.off_bias;
+
+    const int row = tid & 63;
+    int64_t p = tile * TILE_P + row;
+    if (p > P - 1) p = P - 1;  // tail tile: duplicate the last point, masked at the store
+    const int64_t ray = p / K;
+    const float *rp = rays + ((int64_t)sb * NR + ray) * 8;
+    const float zz = zsamp[(int64_t)sb * P + p];
+    const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
+    const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
+
+    f32x16 x[RB][CT], net[RB][CT], xsum[RB][CT];
+#pragma unroll
+    for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = 0.0f;
+
+    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
+    const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+    const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1, din_pad = 8 * L.njb_in;
+    const int c4 = L.dlat / 4;   // float4 per latent texel
+
+    for (int v = 0; v < s.NV; ++v) {
+        // ---- geometry + positional encodings -> A[:, 0:din_pad]; bilinear footprint -> taps ----------
+        {
+            const View vw = load_view(s, sb, v);
+            float px, py, pz, u, w;
+            project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // pixelnerf.py:91-93,105-108
+            float dcx, dcy, dcz;
+            rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :99-101
+            const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
+            const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
+            const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
+            const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :114-115
+            const float half_pi = 1.5707963267948966f;
+            for (int e = wave; e < din_pad; e += NWAVES) {                      // input layout :128
+                float val;
+                if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
+                else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
+                    val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
+                else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
+                else if (e == e_dir) val = delta;
+                else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
+                    val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
+                else val = 0.0f;
+                A[a_off(row, e)] = val;
+            }
+            if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127)
+                const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
+                const float iy = clipf(unnorm(w * syl, (float)s.h / 2.0f), (float)(s.h - 1));
+                const float x0f = floorf(ix), y0f = floorf(iy);
+                const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
+                const int x0 = safe_idx(x0f, s.w), y0 = safe_idx(y0f, s.h);
+                const bool x1ok = x0 + 1 <= s.w - 1, y1ok = y0 + 1 <= s.h - 1;
+                const int x1 = x1ok ? x0 + 1 : x0, y1 = y1ok ? y0 + 1 : y0;
+                Tap t;
+                t.o00 = (y0 * s.w + x0) * c4; t.o01 = (y0 * s.w + x1) * c4;
+                t.o10 = (y1 * s.w + x0) * c4; t.o11 = (y1 * s.w + x1) * c4;
+                t.nw = ey * ex; t.ne = x1ok ? ey * fx : 0.0f;
+                t.sw = y1ok ? fy * ex : 0.0f; t.se = (x1ok && y1ok) ? fy * fx : 0.0f;
+                taps[row] = t;
+            }
+        }
+        __syncthreads();
+        acc_bias(x, bias + L.bias_lin_in(), false, ct0, NT, lane);
+        gemm(x, A4, (const f32x4 *)(Wp + L.off_in), L.njb_in, 0, L.njb_in, rb0, ct0, NT, lane);   // resnetfc.py:139
+        __syncthreads();
+
+        const f32x4 *lat = (const f32x4 *)s.latent + ((int64_t)sb * s.NV + v) * s.h * s.w * c4;
+        for (int b = 0; b < L.nvb; ++b) {
+            acc_bias(x, bias + L.bias_lin_z(b), true, ct0, NT, lane);                               // :152-153 x = x + lin_z(z)
+            for (int k0 = 0; k0 < L.dlat; k0 += KMAX) {
+                // ---- z[:, k0 : k0 + kc] = bilinear latent of the 64 points -> A (each wave gathers 8 rows) ---------
+                const int kc4 = (L.dlat - k0 < KMAX ? L.dlat - k0 : KMAX) / 4;
+                for (int rr = 0; rr < TILE_P / NWAVES; ++rr) {
+                    const int r = wave * (TILE_P / NWAVES) + rr;
+                    const Tap t = taps[r];
+                    for (int q = lane; q < kc4; q += 64) {
+                        const int qq = k0 / 4 + q;
+                        const f32x4 a = lat[t.o00 + qq], bb = lat[t.o01 + qq], c = lat[t.o10 + qq], d = lat[t.o11 + qq];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
+                            A[a_off(r, 4 * q + i)] =
+                                __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+                    }
+                }
+                __syncthreads();
+                gemm(x, A4, (const f32x4 *)(Wp + L.off_z + b * L.w_z), L.njb_lat, k0 / 8, kc4 / 2, rb0, ct0, NT, lane);
+                __syncthreads();
+            }
+            store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
+            __syncthreads();
+            acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
+            gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+            __syncthreads();
+            store_act(net, A, L.beta, rb0, ct0, NT, lane);                                          // :63 fc_1(act(net))
+            __syncthreads();
+            acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                 // :69 x + dx
+            gemm(x, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < CT; ++tn) xsum[tm][tn] += x[tm][tn];                              // :146-149
+    }
+    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
+        const float nv = (float)s.NV;
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
+    }
+    for (int b = L.nvb; b < L.nb; ++b) {
+        store_act(xsum, A, L.beta, rb0, ct0, NT, lane);
+        __syncthreads();
+        acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
+        gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+        __syncthreads();
+        store_act(net, A, L.beta, rb0, ct0, NT, lane);
+        __syncthreads();
+        acc_bias(xsum, bias + L.bias_fc1(b), true, ct0, NT, lane);
+        gemm(xsum, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+        __syncthreads();
+    }
+    store_act(xsum, A, L.beta, rb0, ct0, NT, lane);                                                 // :158 lin_out(act(x))
+    __syncthreads();
+    if (wave < 2) {  // lin_out: one 32-column tile (4 real outputs), wave w = rows 32w..32w+31
+        f32x16 o;
+        const float bo = bias[L.bias_lin_out() + (lane & 31)];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = bo;
+        const f32x4 *ap = A4 + (lane >> 5) * TILE_P + wave * 32 + (lane & 31);
+        const f32x4 *bp = (const f32x4 *)(Wp + L.off_out) + lane;
+#pragma unroll 4
+        for (int jb = 0; jb < H / 8; ++jb) {
+            const f32x4 a = ap[jb * 2 * TILE_P], bq = bp[jb * 64];
+#pragma unroll
+            for (int ji = 0; ji < 4; ++ji) o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ji], bq[ji], o, 0, 0, 0);
+        }
+        const int c = lane & 31, h = lane >> 5;
+        if (c < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int r = wave * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
+                const int64_t pp = tile * TILE_P + r;
+                if (pp < P) {
+                    const float val = o[i];                                                         // pixelnerf.py:139-143
+                    rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
+                }
+            }
+        }
+    }
+}
+
+// the instantiation a d_hidden runs on: <1,1> for up to 128 columns, <2,1> up to 256, <2,2> up to 512
+const char *kernel_name(int d_hidden)
+{
+    return d_hidden <= 128 ? "points_mlp_gen_kernel<1,1>" : d_hidden <= 256 ? "points_mlp_gen_kernel<2,1>" : "points_mlp_gen_kernel<2,2>";
+}
+
+int launch_points_mlp(const DinerScene &s, const DinerMlpShape &m, const float *mlp_packed, const float *rays, const float *z, int64_t NR,
+                      int K, float *rgbsigma, hipStream_t st)
+{
+    int rc;
+    if ((rc = check_shape(m))) return rc;
+    if (m.combine_layer >= m.n_blocks && s.NV != 1) {
+        set_error("render_points_gen: combine_layer=%d >= n_blocks=%d never averages over views, which the reference supports for NV = 1 "
+                  "only (src/models/pixelnerf.py:137 reshapes (SB, NV, B, 4) to (SB, B, 4)); NV=%d", m.combine_layer, m.n_blocks, s.NV);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (s.C != m.d_latent) { set_error("render_points_gen: latent channels C=%d != d_latent=%d", s.C, m.d_latent); return DINER_E_INVALID; }
+    if (s.num_freqs != m.num_freqs) { set_error("render_points_gen: scene num_freqs=%d != shape num_freqs=%d", s.num_freqs, m.num_freqs); return DINER_E_INVALID; }
+    const int64_t P = NR * (int64_t)K;
+    if (P == 0 || s.SB == 0) return DINER_OK;
+    const int64_t tiles = (P + TILE_P - 1) / TILE_P;
+    if (tiles > 0x7fffffffLL) { set_error("render_points_gen: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
+    const Layout L = layout_of(m);
+    const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);
+    if (m.d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma);
+    else if (m.d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma);
+    return check_launch(kernel_name(m.d_hidden));
+}
+
+}  // namespace gen
+}  // namespace diner

@@ -22,13 +22,38 @@ every ``encode()`` of the reference, which re-binds ``encoder.latent/depths/...`
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 import weakref
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
 from ._lib import DinerMlpRaw, DinerSamplerCfg, DinerScene, check
+
+
+class MlpShape(NamedTuple):
+    """The fusion-MLP / positional-encoding shape of a PixelNeRF (reference src/models/pixelnerf.py:14-24,
+    src/models/resnetfc.py:72-127): what ``NeRFRendererDGS._validate_model`` returns."""
+    d_in: int
+    d_latent: int
+    d_hidden: int
+    n_blocks: int
+    combine_layer: int
+    num_freqs: int
+    beta: float = 0.0          # Softplus beta; 0 = ReLU
+
+    @property
+    def standard(self) -> bool:
+        """the one model the 512-wide kernels are built for (include/diner_hip.h DINER_D_*)"""
+        return self == STANDARD_SHAPE
+
+    def c_struct(self) -> _lib.DinerMlpShape:
+        return _lib.DinerMlpShape(self.d_in, self.d_latent, self.d_hidden, self.n_blocks, self.combine_layer, self.num_freqs,
+                                  float(self.beta), 4, 0)
+
+
+STANDARD_SHAPE = MlpShape(55, 512, 512, 5, 3, 6, 0.0)
 
 
 class RenderOutput(dict):
@@ -209,6 +234,13 @@ class NeRFRendererDGS(torch.nn.Module):
         self.fc1_on_mean = True
         self._mlp_key = None
         self._mlp_pack = None
+        # Models of any other shape (MlpShape) run on the shape-general fp32 kernel (points_mlp_gen.hip) through the *_gen entry
+        # points, always through ctypes.  After every inference call: `last_route` = the point kernel that ran ("points_mlp_f16",
+        # "points_mlp" or "points_mlp_gen"), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
+        self._mlp_gen_key = self._mlp_gen_pack = None
+        self.last_route = self.last_binding = self.effective_precision = None
+        self._warned_precision = False
+        self._force_gen = False      # test-only: run the standard shape on the shape-general kernel as well
         self._latent_gen = self._mlp_gen = 0         # bumped by every re-pack; the lin_z maps depend on both
         # Non-finite guard.  The compositing kernel ORs DINER_STATUS_NONFINITE into a device word when an rgb-sigma
         # sample is inf/NaN (in f16x3 mode: an MLP activation beyond the fp16 range, |x| >= ~1e6).  The word is copied
@@ -233,20 +265,75 @@ class NeRFRendererDGS(torch.nn.Module):
     # model -> packed device state (cached)
     # ------------------------------------------------------------------------------------------
     @staticmethod
-    def _validate_model(model):
+    def _validate_model(model) -> MlpShape:
+        """The shape of ``model``'s fusion MLP and encodings; raises ``NotImplementedError`` naming what lies outside what the kernels
+        serve: the standard shape (the 512-wide kernels) and the envelope of the shape-general kernel (include/diner_hip.h)."""
         enc, mlp = model.encoder, model.mlp_fine
         if getattr(enc, "index_interp", "bilinear") != "bilinear" or getattr(enc, "index_padding", "border") != "border":
             raise NotImplementedError("only index_interp='bilinear', index_padding='border' (image_encoder.py:24-25)")
         if getattr(mlp, "combine_type", "average") != "average":
-            raise NotImplementedError("only combine_type='average' (resnetfc.py:9-14)")
-        if not isinstance(getattr(mlp, "activation", torch.nn.ReLU()), torch.nn.ReLU):
-            raise NotImplementedError("only ReLU activations (beta=0, resnetfc.py:124-127)")
-        dims = (mlp.d_in, mlp.d_latent, mlp.d_hidden, mlp.d_out, mlp.n_blocks, mlp.combine_layer)
-        if dims != (55, 512, 512, 4, 5, 3):
-            raise NotImplementedError(f"fusion MLP dims {dims} unsupported; kernels are built for (55,512,512,4,5,3)")
+            raise NotImplementedError(f"only combine_type='average' (resnetfc.py:9-14), not {mlp.combine_type!r}")
+        act = getattr(mlp, "activation", torch.nn.ReLU())
+        if isinstance(act, torch.nn.ReLU):
+            beta = 0.0
+        elif isinstance(act, torch.nn.Softplus) and act.beta > 0 and act.threshold == 20:
+            beta = float(act.beta)
+        else:
+            raise NotImplementedError(f"activation {act!r} unsupported: ReLU or Softplus(beta > 0, threshold=20) (resnetfc.py:124-127)")
+        for blk in getattr(mlp, "blocks", []):
+            ba = getattr(blk, "activation", None)
+            if ba is not None and (type(ba) is not type(act) or getattr(ba, "beta", None) != getattr(act, "beta", None)):
+                raise NotImplementedError("every ResnetBlockFC must use the ResnetFC's activation (resnetfc.py:49-52, 117-119)")
+        if mlp.d_out != 4:
+            raise NotImplementedError(f"fusion MLP d_out={mlp.d_out} unsupported (PixelNeRF's head is rgb + sigma: 4)")
         for pe in (model.poscode, model.depthcode):
-            if pe.num_freqs != 6 or not pe.include_input:
-                raise NotImplementedError("positional encoding must be num_freqs=6, include_input=True")
+            if not pe.include_input:
+                raise NotImplementedError("positional encoding must have include_input=True")
+        F = int(model.poscode.num_freqs)
+        if int(model.depthcode.num_freqs) != F or float(model.depthcode.freqs[0]) != float(model.poscode.freqs[0]):
+            raise NotImplementedError("poscode and depthcode must share num_freqs and freq_factor (pixelnerf.py:14-15)")
+        shape = MlpShape(int(mlp.d_in), int(mlp.d_latent), int(mlp.d_hidden), int(mlp.n_blocks), int(mlp.combine_layer), F, beta)
+        if shape.standard:
+            return shape
+        why = []
+        if not (32 <= shape.d_hidden <= 512 and shape.d_hidden % 32 == 0):
+            why.append(f"d_hidden={shape.d_hidden} (a multiple of 32 in [32, 512])")
+        if not (8 <= shape.d_latent <= 1024 and shape.d_latent % 8 == 0):
+            why.append(f"d_latent={shape.d_latent} (a multiple of 8 in [8, 1024])")
+        if not 1 <= shape.n_blocks <= 64:
+            why.append(f"n_blocks={shape.n_blocks} (1..64)")
+        if shape.combine_layer < 0:
+            why.append(f"combine_layer={shape.combine_layer} (>= 0)")
+        if not (F >= 1 and 7 + 8 * F <= 512):
+            why.append(f"num_freqs={F} (1..63)")
+        elif shape.d_in != 7 + 8 * F:
+            why.append(f"d_in={shape.d_in} (PixelNeRF: 7 + 8 * num_freqs = {7 + 8 * F})")
+        if why:
+            raise NotImplementedError("fusion MLP shape outside what the kernels serve: " + "; ".join(why) +
+                                      f" (standard shape {tuple(STANDARD_SHAPE)[:6]} or the shape-general envelope, include/diner_hip.h)")
+        return shape
+
+    def _route(self, model) -> MlpShape:
+        """validate ``model``; for a shape that takes the shape-general kernel, settle the precision (fp32 is what runs)"""
+        shape = self._validate_model(model)
+        if self._use_gen(shape):
+            if self.precision != "fp32" and not self._warned_precision:
+                warnings.warn(f"diner_amd.NeRFRendererDGS: precision={self.precision!r} is available for the standard model only; "
+                              f"the fusion MLP {tuple(shape)} runs in exact fp32 (renderer.effective_precision)", stacklevel=3)
+                self._warned_precision = True
+            self.effective_precision = "fp32"
+        else:
+            self.effective_precision = self.precision
+        return shape
+
+    def _use_gen(self, shape: MlpShape) -> bool:
+        return self._force_gen or not shape.standard
+
+    @staticmethod
+    def _gen_training_unsupported(shape: MlpShape):
+        raise NotImplementedError(f"training (autograd through the renderer) supports the standard fusion MLP {tuple(STANDARD_SHAPE)[:6]} only; "
+                                  f"the shape {tuple(shape)} is supported for inference: call it under torch.no_grad() or with "
+                                  "parameters that do not require grad")
 
     def _scene(self, model, need_latent=True, packed_mlp=None) -> Tuple[DinerScene, tuple]:
         enc = model.encoder
@@ -315,7 +402,8 @@ class NeRFRendererDGS(torch.nn.Module):
         (diner_amd/training.py: every layer's input in fp32, 24 GB for 4096 rays x 40 samples x 4 views)."""
         nb = lambda t: 0 if t is None else t.numel() * t.element_size()
         maps = self._maps_pack[0] if self._maps_pack is not None else None
-        rep = {"cached": {"maps": nb(maps), "latent_nhwc": nb(self._latent_pack), "linz_maps": nb(self._linz_pack), "mlp_packed": nb(self._mlp_pack)}}
+        rep = {"cached": {"maps": nb(maps), "latent_nhwc": nb(self._latent_pack), "linz_maps": nb(self._linz_pack), "mlp_packed": nb(self._mlp_pack),
+                         "mlp_gen_packed": nb(self._mlp_gen_pack)}}
         rep["cached"]["total"] = sum(rep["cached"].values())
         rep["linz_maps_max_bytes"] = self.linz_maps_max_bytes
         if rays_per_call is not None:
@@ -355,6 +443,34 @@ class NeRFRendererDGS(torch.nn.Module):
             self._mlp_pack, self._mlp_key = packed, _Sources(params)
             self._mlp_gen += 1
         return self._mlp_pack
+
+    def _mlp_shape_general(self, model, shape: MlpShape) -> torch.Tensor:
+        """the packed image of diner_pack_mlp_gen, cached like _mlp() (and on the shape)"""
+        mlp = model.mlp_fine
+        nlz = min(shape.combine_layer, shape.n_blocks)
+        params = [mlp.lin_in.weight, mlp.lin_in.bias, mlp.lin_out.weight, mlp.lin_out.bias]
+        for b in range(nlz):
+            params += [mlp.lin_z[b].weight, mlp.lin_z[b].bias]
+        for b in range(shape.n_blocks):
+            params += [mlp.blocks[b].fc_0.weight, mlp.blocks[b].fc_0.bias, mlp.blocks[b].fc_1.weight, mlp.blocks[b].fc_1.bias]
+        if self._mlp_gen_key is None or self._mlp_gen_key[0] != shape or not self._mlp_gen_key[1].valid_for(params):
+            keep = [_f32c(p) for p in params]
+            ptrs = [t.data_ptr() for t in keep]
+            arr = lambda xs: (C.c_void_p * max(1, len(xs)))(*xs)
+            lz, blk = ptrs[4:4 + 2 * nlz], ptrs[4 + 2 * nlz:]
+            arrays = [arr(lz[0::2]), arr(lz[1::2]), arr(blk[0::4]), arr(blk[1::4]), arr(blk[2::4]), arr(blk[3::4])]
+            pp = lambda a: C.cast(a, C.POINTER(C.c_void_p))
+            raw = _lib.DinerMlpGenRaw(ptrs[0], ptrs[1], *[pp(a) for a in arrays], ptrs[2], ptrs[3])
+            cs = shape.c_struct()
+            n = int(_lib.lib().diner_mlp_gen_packed_floats(C.byref(cs)))
+            if n < 0:
+                check(n, "diner_mlp_gen_packed_floats")
+            dev = keep[0].device
+            packed = torch.empty(n, dtype=torch.float32, device=dev)
+            check(_lib.lib().diner_pack_mlp_gen(C.byref(cs), C.byref(raw), _ptr(packed), _stream(dev)), "diner_pack_mlp_gen")
+            torch.cuda.current_stream(dev).synchronize()  # `keep` may be temporaries: finish before they die
+            self._mlp_gen_pack, self._mlp_gen_key = packed, (shape, _Sources(params))
+        return self._mlp_gen_pack
 
     # ------------------------------------------------------------------------------------------
     # non-finite guard
@@ -469,6 +585,17 @@ class NeRFRendererDGS(torch.nn.Module):
         r = self._check_rays(rays)
         z = _f32c(z_samp)
         SB, NR, K = z.shape
+        shape = self._route(model)
+        if self._use_gen(shape):
+            packed = self._mlp_shape_general(model, shape)
+            sc, _keep = self._scene(model, need_latent=True)
+            assert SB == sc.SB
+            out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
+            cs = shape.c_struct()
+            check(_lib.lib().diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out),
+                                                     _stream(r.device)), "diner_render_points_gen")
+            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+            return out
         packed = self._mlp(model)
         sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
         assert SB == sc.SB  # pixelnerf.py:68
@@ -479,6 +606,7 @@ class NeRFRendererDGS(torch.nn.Module):
         check(_lib.lib().diner_render_points(C.byref(sc), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
                                              _ptr(out), _stream(r.device)),
               "diner_render_points")
+        self.last_route, self.last_binding = ("points_mlp_f16" if self.precision == "f16x3" else "points_mlp"), "ctypes"
         return out
 
     def composite(self, model, rays, z_samp, *, rgbsigma=None, _sync=False):
@@ -488,6 +616,9 @@ class NeRFRendererDGS(torch.nn.Module):
         SB, NR, K = z.shape
         if rgbsigma is None and torch.is_grad_enabled() and (any(p.requires_grad for p in model.mlp_fine.parameters())
                                                              or model.encoder.latent.requires_grad):
+            shape = self._validate_model(model)
+            if not shape.standard:
+                self._gen_training_unsupported(shape)
             out = self._forward_train(model, rays, True, z_samples=z).fine   # differentiable like the reference's composite
             return out.weights, out.rgb, out.depth
         if rgbsigma is None:
@@ -521,9 +652,13 @@ class NeRFRendererDGS(torch.nn.Module):
         :return: ``out.fine.rgb`` [SB,B,3], ``out.fine.depth`` [SB,B], ``out.fine.weights`` iff requested
         """
         assert len(rays.shape) == 3
-        self._validate_model(model)
+        shape = self._validate_model(model)
         if torch.is_grad_enabled() and (any(p.requires_grad for p in model.mlp_fine.parameters()) or model.encoder.latent.requires_grad):
+            if not shape.standard:
+                self._gen_training_unsupported(shape)
             return self._forward_train(model, rays, want_weights, noise=noise, z_samples=z_samples)
+        if z_samples is None and self._use_gen(shape):
+            return self._forward_gen(model, rays, want_weights, shape, noise)
         with torch.no_grad():
             r = self._check_rays(rays)
             SB, NR, _ = r.shape
@@ -579,6 +714,56 @@ class NeRFRendererDGS(torch.nn.Module):
                     ev[3].record()
                     self.stage_events.append(ev)
                 self._after_launch(dev, sync=big)
+                self.effective_precision = self.precision
+                self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
+                self.last_binding = "torch_ops" if use_ops else "ctypes"
+        return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
+
+    @torch.no_grad()
+    def _forward_gen(self, model, rays, want_weights, shape: MlpShape, noise):
+        """forward() for a non-standard model: diner_render_gen (sampler -> shape-general point kernel -> compositing), or the three
+        stage entry points when stage_events is a list"""
+        self._route(model)
+        r = self._check_rays(rays)
+        SB, NR, _ = r.shape
+        K = int(self.n_samples)
+        dev = r.device
+        big = want_weights or SB * NR > int(self.finite_sync_rays)
+        packed = self._mlp_shape_general(model, shape)
+        sc, _keep = self._scene(model, need_latent=True)
+        assert SB == sc.SB
+        cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
+        cs = shape.c_struct()
+        u_c = n_g = u_f = None
+        if noise is not None:
+            u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
+        L, st, seed = _lib.lib(), _stream(dev), self._next_seed()
+        self._poll_status()
+        status = _ptr(self._status_word(dev))
+        ws = torch.empty(int(L.diner_render_workspace_floats(SB, NR, K, sc.NV, _lib.PRECISIONS["fp32"])), dtype=torch.float32, device=dev)
+        rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
+        depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
+        weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
+        if self.stage_events is None:
+            check(L.diner_render_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st),
+                  "diner_render_gen")
+        else:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
+            ev[0].record()
+            check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
+                                             None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
+            ev[1].record()
+            check(L.diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st),
+                  "diner_render_points_gen")
+            ev[2].record()
+            check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
+                                    _ptr(depth), _ptr(weights), status, st), "diner_composite")
+            ev[3].record()
+            self.stage_events.append(ev)
+        self._after_launch(dev, sync=big)
+        self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     @torch.no_grad()
@@ -589,14 +774,19 @@ class NeRFRendererDGS(torch.nn.Module):
         chunks, no ``torch.cat``), output in the reference's image layout.  Bit-identical to ``forward(gen_rays(...))``.
         :param target_extrinsics: [SB,4,4] world->cam;  target_intrinsics: [SB,3,3];  z_near, z_far: [SB] or scalars
         :return: rgb [SB,3,H,W] (, depth [SB,1,H,W])"""
-        self._validate_model(model)
+        shape = self._route(model)
+        gen = self._use_gen(shape)
         dev = target_extrinsics.device
         SB = target_extrinsics.shape[0]
         E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
         zn = torch.as_tensor(z_near, dtype=torch.float32, device=dev).expand(SB).contiguous()
         zf = torch.as_tensor(z_far, dtype=torch.float32, device=dev).expand(SB).contiguous()
-        packed = self._mlp(model)
-        sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
+        if gen:
+            packed = self._mlp_shape_general(model, shape)
+            sc, _keep = self._scene(model, need_latent=True)
+        else:
+            packed = self._mlp(model)
+            sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
         assert SB == sc.SB
         K = int(self.n_samples)
         cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
@@ -607,7 +797,17 @@ class NeRFRendererDGS(torch.nn.Module):
         L = _lib.lib()
         self._poll_status()
         seed = self._next_seed()
-        if self.binding == "torch_ops":
+        if gen:
+            cs = shape.c_struct()
+            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
+                             dtype=torch.float32, device=dev)
+            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
+            check(L.diner_render_image_gen(C.byref(sc), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)),
+                                           seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
+                  "diner_render_image_gen")
+            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+        elif self.binding == "torch_ops":
             from . import ops as _ops
             maps_t, poses_t, focal_t, c_t, latent_t, linz_t = _keep
             rgb, depth = _ops.load().render_image(maps_t, poses_t, focal_t, c_t, latent_t, linz_t, packed, E, Ki, zn, zf, int(H), int(W), sc.image_w,
@@ -620,6 +820,9 @@ class NeRFRendererDGS(torch.nn.Module):
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
             check(L.diner_render_image(C.byref(sc), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec, seed,
                                        _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image")
+        if not gen:
+            self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
+            self.last_binding = self.binding
         self._after_launch(dev, sync=self.finite_check != "off")    # once per frame: a NaN image never leaves this function
         rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
         if return_depth:

@@ -96,8 +96,8 @@ typedef struct DinerTargetCam {
 /* Version of THIS ABI (argument lists, struct layouts).  Bumped by every incompatible change; a binding compiled or written
  * against another value must refuse to call in: diner_version() returns the value the loaded library was built with, the
  * torch-ops extension checks it at every op entry, diner_amd/_lib.py at load time.  (2: diner_render / diner_composite gained
- * `status`.) */
-#define DINER_ABI_VERSION 2
+ * `status`.  3: the shape-general inference path, the *_gen entry points below.) */
+#define DINER_ABI_VERSION 3
 
 const char *diner_last_error(void);
 int diner_version(void);
@@ -129,7 +129,7 @@ int diner_decode_depth_u16(const uint16_t *depth, const uint16_t *conf, const ui
                            int32_t W, int32_t stride, float mul0, float div, float mul1, float std_a, float std_b,
                            float *depth_out, float *std_out, float *mask_out, void *stream);
 /* latent [N,C,h,w] (NCHW, src/models/image_encoder.py:271) -> [N,h,w,C] with the channel order
- * the MLP kernel stages into LDS (C = 512) */
+ * the MLP kernel stages into LDS (C = 512; any other multiple of 8 up to 1024 for the shape-general path) */
 int diner_pack_latent(const float *latent_nchw, int64_t N, int32_t C, int32_t h, int32_t w,
                       float *latent_out, void *stream);
 /* ---- once per weight version: MFMA-fragment-ordered copies of the fusion MLP (one image per
@@ -212,6 +212,51 @@ int diner_render_image(const DinerScene *scene, const float *mlp_packed, const D
                        const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, uint64_t seed,
                        float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
                        uint32_t *status, void *stream);
+
+/* ---- shape-general inference path ----------------------------------------------------------------------------------------
+ * The entry points above serve the one model the configs ship (DINER_D_* above).  The reference renders any ResnetFC /
+ * PositionalEncoding its constructors accept (src/models/pixelnerf.py:14-24, src/models/resnetfc.py:72-127,
+ * src/models/positional_encoding.py:9-31); these entry points take the shape at run time and evaluate it with exact fp32 MFMA
+ * (the arithmetic of DINER_PRECISION_FP32) in a second point/MLP kernel.  Envelope (anything else: DINER_E_UNSUPPORTED with
+ * the reason in diner_last_error()):
+ *   d_hidden a multiple of 32 in [32, 512]; d_latent a multiple of 8 in [8, 1024]; n_blocks in [1, 64]; combine_layer >= 0
+ *   (>= n_blocks: no mean over views, which the reference supports for NV = 1 only, src/models/pixelnerf.py:137);
+ *   num_freqs F >= 1 with d_in = 7 + 8F <= 512 (both encodings, include_input); activation ReLU (beta = 0) or
+ *   Softplus(beta) (beta > 0); d_out = 4; combine_type average. */
+#define DINER_COMBINE_AVERAGE 0
+typedef struct DinerMlpShape {
+    int32_t d_in, d_latent, d_hidden, n_blocks, combine_layer, num_freqs;
+    float beta;              /* Softplus beta; 0 = ReLU (resnetfc.py:124-127) */
+    int32_t d_out;           /* must be 4 */
+    int32_t combine_type;    /* must be DINER_COMBINE_AVERAGE */
+} DinerMlpShape;
+
+/* ResnetFC parameters of any shape, nn.Linear layout weight [out,in].  The per-block members are HOST arrays of device pointers:
+ * lin_z_*: min(combine_layer, n_blocks) entries ([d_hidden,d_latent], [d_hidden]); fc0_*, fc1_*: n_blocks entries
+ * ([d_hidden,d_hidden], [d_hidden]). */
+typedef struct DinerMlpGenRaw {
+    const float *lin_in_w, *lin_in_b;                  /* [d_hidden,d_in], [d_hidden] */
+    const float *const *lin_z_w, *const *lin_z_b;
+    const float *const *fc0_w, *const *fc0_b;
+    const float *const *fc1_w, *const *fc1_b;
+    const float *lin_out_w, *lin_out_b;                /* [4,d_hidden], [4] */
+} DinerMlpGenRaw;
+
+/* floats of the packed image of a shape (< 0: the DINER_E_* code of an unsupported shape) */
+int64_t diner_mlp_gen_packed_floats(const DinerMlpShape *shape);
+int diner_pack_mlp_gen(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, float *packed_out, void *stream);
+/* diner_render_points for a shape: mlp_packed from diner_pack_mlp_gen; scene->C must be d_latent and scene->num_freqs F */
+int diner_render_points_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,
+                            const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream);
+/* diner_render / diner_render_image for a shape (workspace: diner_render_workspace_floats / diner_render_image_workspace_floats
+ * with DINER_PRECISION_FP32) */
+int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, int64_t NR,
+                     const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss, const float *u_fill,
+                     uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status,
+                     void *stream);
+int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const DinerTargetCam *cam,
+                           const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out,
+                           float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
 
 /* ---- training path: building blocks of the forward-with-saved-activations and
  * the backward of composite (src/models/nerf_renderer.py:286-365) + PixelNeRF.forward

@@ -24,13 +24,13 @@ class _Block(nn.Module):
 
 
 class _ResnetFCState(nn.Module):
-    def __init__(self, d_in=55, d_out=4, n_blocks=5, d_latent=512, d_hidden=512, combine_layer=3):
+    def __init__(self, d_in=55, d_out=4, n_blocks=5, d_latent=512, d_hidden=512, combine_layer=3, beta=0.0):
         super().__init__()
         self.lin_in = nn.Linear(d_in, d_hidden)
         self.lin_out = nn.Linear(d_hidden, d_out)
         self.blocks = nn.ModuleList([_Block(d_hidden) for _ in range(n_blocks)])
         self.lin_z = nn.ModuleList([nn.Linear(d_latent, d_hidden) for _ in range(min(combine_layer, n_blocks))])
-        self.activation = nn.ReLU()
+        self.activation = nn.Softplus(beta=beta) if beta > 0 else nn.ReLU()   # resnetfc.py:124-127
         self.n_blocks, self.d_latent, self.d_in, self.d_out, self.d_hidden = n_blocks, d_latent, d_in, d_out, d_hidden
         self.combine_layer, self.combine_type = combine_layer, "average"
 
@@ -57,22 +57,26 @@ class _EncoderState(nn.Module):
 
 
 class PixelNeRFState(nn.Module):
-    def __init__(self, feature_padding=32, freq_factor=6.28):
+    def __init__(self, feature_padding=32, freq_factor=6.28, num_freqs=6, **mlp_dims):
+        """``mlp_dims``: ResnetFC keyword arguments (d_latent, d_hidden, n_blocks, combine_layer, beta); d_in follows num_freqs
+        (pixelnerf.py:18) and the encoder's latent size follows d_latent"""
         super().__init__()
-        self.poscode = _PEState(d_in=3, freq_factor=freq_factor)
-        self.depthcode = _PEState(d_in=1, freq_factor=freq_factor)
+        self.poscode = _PEState(num_freqs=num_freqs, d_in=3, freq_factor=freq_factor)
+        self.depthcode = _PEState(num_freqs=num_freqs, d_in=1, freq_factor=freq_factor)
         self.encoder = _EncoderState(feature_padding)
-        self.mlp_fine = _ResnetFCState()
+        self.mlp_fine = _ResnetFCState(d_in=self.poscode.d_out + self.depthcode.d_out + 3, **mlp_dims)
+        self.encoder.latent_size = self.mlp_fine.d_latent
         self.poses = self.focal = self.c = self.image_shape = None
 
     def forward(self, *a, **k):
         raise RuntimeError("model stub: points are evaluated by diner_amd.NeRFRendererDGS")
 
 
-def model_from_scene(scene, weights, device="cuda", latent: torch.Tensor | None = None) -> PixelNeRFState:
+def model_from_scene(scene, weights, device="cuda", latent: torch.Tensor | None = None, num_freqs=6, **mlp_dims) -> PixelNeRFState:
     """Build the stand-in from a ``synthetic.synth.Scene`` and a ``make_mlp_weights`` dict.
-    ``latent`` may be passed as a device tensor [SB,NV,C,h,w] for scenes generated on the GPU."""
-    m = PixelNeRFState(feature_padding=scene.feature_padding)
+    ``latent`` may be passed as a device tensor [SB,NV,C,h,w] for scenes generated on the GPU.
+    ``num_freqs`` / ``mlp_dims`` (d_latent, d_hidden, n_blocks, combine_layer, beta) describe a non-default model."""
+    m = PixelNeRFState(feature_padding=scene.feature_padding, num_freqs=num_freqs, **mlp_dims)
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
     m.mlp_fine.load_state_dict(sd, strict=True)
     m = m.to(device)

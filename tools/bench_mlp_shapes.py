@@ -1,0 +1,69 @@
+"""Throughput of the shape-general inference path (points_mlp_gen.hip) on one GPU: rays/s of a whole 512 x 512 frame through
+NeRFRendererDGS.forward for a non-standard model, with the event time of each stage (sampler | generic point kernel | compositing).
+A record, not a gate.  Default: case (a) of tools/gen_shape_golden.py (d_hidden 128, 5 blocks, combine_layer 3) at K = 40,
+NV = 2, the reference's renderer defaults otherwise.
+
+    python tools/bench_mlp_shapes.py [--res 512] [--K 40] [--NV 2] [--d_hidden 128] [--steps 5] [--warmup 2]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--K", type=int, default=40)
+    ap.add_argument("--G", type=int, default=15)
+    ap.add_argument("--NV", type=int, default=2)
+    ap.add_argument("--d_hidden", type=int, default=128)
+    ap.add_argument("--n_blocks", type=int, default=5)
+    ap.add_argument("--combine_layer", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from diner_amd import NeRFRendererDGS
+    from synthetic import synth
+    from synthetic.model_stub import model_from_scene
+
+    dev = torch.device("cuda:0")
+    dims = dict(d_hidden=a.d_hidden, n_blocks=a.n_blocks, combine_layer=a.combine_layer)
+    sc = synth.make_scene(a.res, a.res, a.NV, seed=0, feature_padding=32, with_latent=False)
+    h, w = sc.latent_hw
+    g = torch.Generator(device=dev).manual_seed(1)
+    latent = torch.randn((1, a.NV, 512, h, w), device=dev, generator=g)
+    m = model_from_scene(sc, synth.make_mlp_weights(1, bias_scale=0.1, **dims), device=dev, latent=latent, **dims)
+    rays = torch.from_numpy(np.ascontiguousarray(sc.target_rays())).to(dev)
+    NR = rays.shape[1]
+    r = NeRFRendererDGS(n_samples=a.K, n_gaussian=a.G, white_bkgd=sc.white_bkgd)
+    r.precision = "fp32"
+    with torch.no_grad():
+        for _ in range(a.warmup):
+            r(m, rays)
+        torch.cuda.synchronize()
+        r.stage_events = []
+        for _ in range(a.steps):
+            r(m, rays)
+        torch.cuda.synchronize()
+    assert r.last_route == "points_mlp_gen"
+    st = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(3)] for ev in r.stage_events])   # ms
+    frame = float(np.median(st.sum(1)))
+    print(json.dumps(dict(path="points_mlp_gen", d_hidden=a.d_hidden, n_blocks=a.n_blocks, combine_layer=a.combine_layer, NV=a.NV, K=a.K,
+                          rays=NR, steps=a.steps, rays_per_s=NR / (frame / 1e3), frame_ms=frame,
+                          sampler_ms=float(np.median(st[:, 0])), points_mlp_gen_ms=float(np.median(st[:, 1])),
+                          composite_ms=float(np.median(st[:, 2])),
+                          points_mlp_gen_min_ms=float(st[:, 1].min()), points_mlp_gen_max_ms=float(st[:, 1].max()))))
+
+
+if __name__ == "__main__":
+    main()
