@@ -61,6 +61,15 @@ class DinerMlpGenRaw(C.Structure):
                 ("lin_out_w", _FP), ("lin_out_b", _FP)]
 
 
+class DinerLatentIndex(C.Structure):
+    _fields_ = [("interp", C.c_int32), ("padding", C.c_int32)]
+
+
+# SpatialEncoder's index_interp / index_padding (reference src/models/image_encoder.py:24-25) -> DINER_INDEX_* of include/diner_hip.h
+INDEX_INTERP = {"bilinear": 0, "nearest": 1}
+INDEX_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
+
+
 # every symbol include/diner_hip.h declares: name -> (restype, argtypes)
 _I64, _I32, _U64, _P = C.c_int64, C.c_int32, C.c_uint64, C.c_void_p
 SYMBOLS = {
@@ -111,6 +120,22 @@ SYMBOLS = {
                                    _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "diner_render_image_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, C.POINTER(DinerTargetCam),
                                          C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    # the latent lookup modes (DinerLatentIndex; NULL = bilinear / border)
+    "diner_linz_maps_floats": (_I64, [_I64, _I32, _I32, C.POINTER(DinerLatentIndex)]),
+    "diner_pack_linz_maps_ix": (C.c_int, [_P, _I64, _I32, _I32, _P, C.POINTER(DinerLatentIndex), _P, _P]),
+    "diner_render_points_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "diner_render_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _I64, C.POINTER(DinerSamplerCfg), _I32, _I32,
+                                  _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, C.POINTER(DinerTargetCam),
+                                        C.POINTER(DinerSamplerCfg), _I32, _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "diner_render_points_gen_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _P,
+                                             _I64, _I32, _P, _P]),
+    "diner_render_gen_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _I64,
+                                      C.POINTER(DinerSamplerCfg), _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P,
+                                            C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "diner_train_point_inputs_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _I32, _P, _P, _I64, _I32, _I32, _P,
+                                              _P, _P, _P]),
 }
 
 _lib = None

@@ -84,7 +84,7 @@ int launch_train_gemm_core(const float *, int64_t, const void *, const float *, 
 int launch_train_gemm_panel(const float *, int64_t, const void *, const void *, const float *, const float *, int64_t, const float *,
                             int64_t, float *, int64_t, int64_t, int, int, const unsigned int *, int, int, hipStream_t);
 int launch_train_colsum(const float *, int64_t, int, int64_t, float *, hipStream_t);
-int launch_train_point_inputs(const DinerScene &, const float *, int, const float *, const float *, int64_t, int, int, float *, float *,
+int launch_train_point_inputs(const DinerScene &, const DinerLatentIndex &, const float *, int, const float *, const float *, int64_t, int, int, float *, float *,
                               float *, hipStream_t);
 int launch_train_bilinear_scatter(const float *, const float *, int64_t, int, int, int, int, int, float *, hipStream_t);
 int launch_train_view_mean(const float *, int64_t, int, float *, int, hipStream_t);
@@ -98,20 +98,21 @@ int launch_pack_maps_from_depth(const float *, const float *, const float *, int
 int launch_decode_depth(const unsigned short *, const unsigned short *, const unsigned short *, int64_t, int, int, int, float, float, float,
                         float, float, float *, float *, float *, hipStream_t);
 int launch_linz_maps(const float *, int64_t, const float *, float *, hipStream_t);
+int launch_linz_maps_ring(const float *, int64_t, int, int, const float *, float *, hipStream_t);
 int launch_sampler(const DinerScene &, const float *, const DinerTargetCam *, float *, int64_t, const DinerSamplerCfg &, const float *,
                    const float *, const float *, const float *, uint64_t, float *, float *, float *, hipStream_t);
 int launch_sample_coarse(const float *, int64_t, int, const float *, uint64_t, float *, hipStream_t);
 int launch_fill_up(const float *, const float *, int64_t, int, const float *, uint64_t, float *, hipStream_t);
-int launch_points_mlp(const DinerScene &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
 int64_t mlp_f16_packed_floats();
 int launch_pack_mlp_f16(const DinerMlpRaw &, float *, hipStream_t);
-int launch_points_mlp_f16(const DinerScene &, const float *, const float *, const float *, int64_t, int, float *, float *, hipStream_t);
+int launch_points_mlp_f16(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, float *, float *, hipStream_t);
 int64_t points_mlp_f16_scratch_floats(int64_t SB, int NV);
 namespace gen {
 int check_shape(const DinerMlpShape &);
 int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
-int launch_points_mlp(const DinerScene &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
 }
 
 static int bad(const char *msg)
@@ -129,6 +130,23 @@ static int check_scene(const DinerScene *s, bool need_latent)
     if (need_latent) {
         if (!s->latent) return bad("scene: latent is NULL");
         if (s->h <= 0 || s->w <= 0) return bad("scene: bad latent size");
+    }
+    return DINER_OK;
+}
+
+static const DinerLatentIndex k_default_index = {DINER_INDEX_BILINEAR, DINER_INDEX_PAD_BORDER};
+
+// NULL = bilinear / border (the entry points without _ix)
+static int check_index(const DinerLatentIndex *ix, const char *who)
+{
+    if (!ix) return DINER_OK;
+    if (ix->interp != DINER_INDEX_BILINEAR && ix->interp != DINER_INDEX_NEAREST) {
+        set_error("%s: latent index interp=%d unknown (DINER_INDEX_BILINEAR 0 or DINER_INDEX_NEAREST 1)", who, ix->interp);
+        return DINER_E_INVALID;
+    }
+    if (ix->padding != DINER_INDEX_PAD_BORDER && ix->padding != DINER_INDEX_PAD_ZEROS && ix->padding != DINER_INDEX_PAD_REFLECTION) {
+        set_error("%s: latent index padding=%d unknown (DINER_INDEX_PAD_BORDER 0, _ZEROS 1 or _REFLECTION 2)", who, ix->padding);
+        return DINER_E_INVALID;
     }
     return DINER_OK;
 }
@@ -251,6 +269,25 @@ int diner_sample_depthguided(const DinerScene *scene, const float *rays, int64_t
                           (hipStream_t)stream);
 }
 
+int64_t diner_linz_maps_floats(int64_t N, int32_t h, int32_t w, const DinerLatentIndex *index)
+{
+    if (check_index(index, "linz_maps_floats")) return DINER_E_INVALID;
+    if (N < 0 || h <= 0 || w <= 0) return bad("linz_maps_floats: bad size");
+    const int r = (index && index->padding == DINER_INDEX_PAD_ZEROS) ? 1 : 0;
+    return 3 * N * (int64_t)(h + 2 * r) * (w + 2 * r) * DINER_D_LATENT;
+}
+
+int diner_pack_linz_maps_ix(const float *latent_packed, int64_t N, int32_t h, int32_t w, const float *mlp_packed,
+                            const DinerLatentIndex *index, float *out, void *stream)
+{
+    int rc;
+    if ((rc = check_index(index, "pack_linz_maps_ix"))) return rc;
+    if (!index || index->padding != DINER_INDEX_PAD_ZEROS) return diner_pack_linz_maps(latent_packed, N, h, w, mlp_packed, out, stream);
+    if (!latent_packed || !mlp_packed || !out) return bad("pack_linz_maps_ix: NULL pointer");
+    if (N < 0 || h <= 0 || w <= 0) return bad("pack_linz_maps_ix: bad size");
+    return launch_linz_maps_ring(latent_packed, N, h, w, mlp_packed, out, (hipStream_t)stream);
+}
+
 int64_t diner_render_points_scratch_floats(int64_t SB, int32_t NV, int32_t precision)
 {
     return precision == DINER_PRECISION_F16X3 ? points_mlp_f16_scratch_floats(SB, NV) : 0;
@@ -259,14 +296,39 @@ int64_t diner_render_points_scratch_floats(int64_t SB, int32_t NV, int32_t preci
 int diner_render_points(const DinerScene *scene, const float *mlp_packed, const float *rays, const float *z,
                         int64_t NR, int32_t K, int32_t precision, float *scratch, float *rgbsigma_out, void *stream)
 {
+    return diner_render_points_ix(scene, nullptr, mlp_packed, rays, z, NR, K, precision, scratch, rgbsigma_out, stream);
+}
+
+int diner_render_points_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const float *rays,
+                           const float *z, int64_t NR, int32_t K, int32_t precision, float *scratch, float *rgbsigma_out, void *stream)
+{
     int rc;
-    if ((rc = check_scene(scene, true))) return rc;
+    if ((rc = check_scene(scene, true)) || (rc = check_index(index, "render_points"))) return rc;
+    const DinerLatentIndex &ix = index ? *index : k_default_index;
     if (NR < 0 || K < 1) return bad("render_points: bad NR / K");
     if (!mlp_packed) return bad("render_points: mlp_packed is NULL");
     if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points: NULL rays / z / out");
-    if (precision == DINER_PRECISION_FP32) return launch_points_mlp(*scene, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
+    if (precision == DINER_PRECISION_F16X3 && scene->linz_maps && ix.padding == DINER_INDEX_PAD_ZEROS && scene->SB > 0) {
+        // zeros padding reads the RINGED lin_z maps ((h+2) x (w+2) texels per view, diner_pack_linz_maps_ix); DinerScene cannot say which
+        // layout linz_maps holds, so refuse a buffer whose allocation ends before the ringed size (the plain maps of diner_pack_linz_maps)
+        // instead of reading past it.  (A caller who sub-allocates can still hand plain maps in a larger block: wrong values, no fault.)
+        const size_t need = (size_t)3 * scene->SB * scene->NV * (size_t)(scene->h + 2) * (size_t)(scene->w + 2) * DINER_D_LATENT * sizeof(float);
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)scene->linz_maps) == hipSuccess) {
+            if ((const char *)scene->linz_maps + need > (const char *)base + size) {
+                set_error("render_points(f16x3, zeros padding): linz_maps must be the ringed maps of diner_pack_linz_maps_ix "
+                          "(%zu bytes), its allocation ends %zu bytes earlier", need,
+                          (size_t)((const char *)scene->linz_maps + need - ((const char *)base + size)));
+                return DINER_E_INVALID;
+            }
+        } else {
+            (void)hipGetLastError();   // not a runtime allocation (e.g. virtual memory): nothing to check against
+        }
+    }
+    if (precision == DINER_PRECISION_FP32) return launch_points_mlp(*scene, ix, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
     if (precision == DINER_PRECISION_F16X3)
-        return launch_points_mlp_f16(*scene, mlp_packed + mlp_packed_floats(), rays, z, NR, K, scratch, rgbsigma_out,
+        return launch_points_mlp_f16(*scene, ix, mlp_packed + mlp_packed_floats(), rays, z, NR, K, scratch, rgbsigma_out,
                                      (hipStream_t)stream);
     return bad("render_points: unknown precision");
 }
@@ -355,11 +417,18 @@ int diner_train_colsum(const float *dY, int64_t M, int32_t N, int64_t ld, float 
 int diner_train_point_inputs(const DinerScene *scene, const float *latent, int32_t latent_is_nhwc, const float *rays, const float *z,
                              int64_t NR, int32_t K, int32_t sb, float *in56, float *zlat, float *taps, void *stream)
 {
+    return diner_train_point_inputs_ix(scene, nullptr, latent, latent_is_nhwc, rays, z, NR, K, sb, in56, zlat, taps, stream);
+}
+
+int diner_train_point_inputs_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *latent, int32_t latent_is_nhwc,
+                                const float *rays, const float *z, int64_t NR, int32_t K, int32_t sb, float *in56, float *zlat,
+                                float *taps, void *stream)
+{
     int rc;
-    if ((rc = check_scene(scene, false))) return rc;
+    if ((rc = check_scene(scene, false)) || (rc = check_index(index, "train_point_inputs"))) return rc;
     if (!latent || !rays || !z || !in56 || !zlat || !taps) return bad("train_point_inputs: NULL pointer");
     if (scene->C != DINER_D_LATENT || scene->h <= 0 || scene->w <= 0 || sb < 0 || sb >= scene->SB) return bad("train_point_inputs: bad scene");
-    return launch_train_point_inputs(*scene, latent, latent_is_nhwc, rays, z, NR, K, sb, in56, zlat, taps, (hipStream_t)stream);
+    return launch_train_point_inputs(*scene, index ? *index : k_default_index, latent, latent_is_nhwc, rays, z, NR, K, sb, in56, zlat, taps, (hipStream_t)stream);
 }
 
 int diner_train_bilinear_scatter(const float *dz, const float *taps, int64_t P, int32_t C, int32_t h, int32_t w, int32_t NV, int32_t sb,
@@ -406,8 +475,17 @@ int diner_render(const DinerScene *scene, const float *mlp_packed, const float *
                  const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
                  float *weights_out, uint32_t *status, void *stream)
 {
+    return diner_render_ix(scene, nullptr, mlp_packed, rays, NR, cfg, white_bkgd, precision, u_coarse, n_gauss, u_fill, seed, workspace,
+                           rgb_out, depth_out, weights_out, status, stream);
+}
+
+int diner_render_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const float *rays, int64_t NR,
+                    const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, const float *u_coarse, const float *n_gauss,
+                    const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                    float *weights_out, uint32_t *status, void *stream)
+{
     int rc;
-    if ((rc = check_scene(scene, true)) || (rc = check_cfg(cfg))) return rc;
+    if ((rc = check_scene(scene, true)) || (rc = check_cfg(cfg)) || (rc = check_index(index, "render"))) return rc;
     if (NR < 0) return bad("NR < 0");
     if (NR == 0 || scene->SB == 0) return DINER_OK;
     if (!workspace) return bad("render: workspace is NULL");
@@ -416,7 +494,7 @@ int diner_render(const DinerScene *scene, const float *mlp_packed, const float *
     if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr,
                                        nullptr, stream)))
         return rc;
-    if ((rc = diner_render_points(scene, mlp_packed, rays, z, NR, cfg->n_samples, precision, scratch, rgbsigma, stream))) return rc;
+    if ((rc = diner_render_points_ix(scene, index, mlp_packed, rays, z, NR, cfg->n_samples, precision, scratch, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
@@ -430,8 +508,16 @@ int diner_render_image(const DinerScene *scene, const float *mlp_packed, const D
                        int32_t white_bkgd, int32_t precision, uint64_t seed, float *workspace, float *rays_out, float *rgb_out,
                        float *depth_out, float *weights_out, uint32_t *status, void *stream)
 {
+    return diner_render_image_ix(scene, nullptr, mlp_packed, cam, cfg, white_bkgd, precision, seed, workspace, rays_out, rgb_out, depth_out,
+                                 weights_out, status, stream);
+}
+
+int diner_render_image_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const DinerTargetCam *cam,
+                          const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, uint64_t seed, float *workspace,
+                          float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
+{
     int rc;
-    if ((rc = check_scene(scene, true)) || (rc = check_cfg(cfg))) return rc;
+    if ((rc = check_scene(scene, true)) || (rc = check_cfg(cfg)) || (rc = check_index(index, "render_image"))) return rc;
     if (!cam || !cam->extrinsics || !cam->intrinsics || !cam->z_near || !cam->z_far) return bad("render_image: NULL camera");
     if (cam->H <= 0 || cam->W <= 0) return bad("render_image: bad image size");
     if (scene->SB == 0) return DINER_OK;
@@ -442,7 +528,7 @@ int diner_render_image(const DinerScene *scene, const float *mlp_packed, const D
     if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
                              (hipStream_t)stream)))
         return rc;
-    if ((rc = diner_render_points(scene, mlp_packed, rays, z, NR, cfg->n_samples, precision, scratch, rgbsigma, stream))) return rc;
+    if ((rc = diner_render_points_ix(scene, index, mlp_packed, rays, z, NR, cfg->n_samples, precision, scratch, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
@@ -472,22 +558,39 @@ int diner_pack_mlp_gen(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, fl
 int diner_render_points_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, const float *z,
                             int64_t NR, int32_t K, float *rgbsigma_out, void *stream)
 {
+    return diner_render_points_gen_ix(scene, nullptr, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream);
+}
+
+int diner_render_points_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                               const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)
+{
     int rc;
     if (!shape) return bad("render_points_gen: shape is NULL");
+    if ((rc = check_index(index, "render_points_gen"))) return rc;
     if ((rc = gen::check_shape(*shape))) return rc;
     if ((rc = check_scene(scene, shape->combine_layer > 0))) return rc;
     if (NR < 0 || K < 1) return bad("render_points_gen: bad NR / K");
     if (!mlp_packed) return bad("render_points_gen: mlp_packed is NULL");
     if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points_gen: NULL rays / z / out");
-    return gen::launch_points_mlp(*scene, *shape, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
+    return gen::launch_points_mlp(*scene, index ? *index : k_default_index, *shape, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
 }
 
 int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, int64_t NR,
                      const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss, const float *u_fill,
                      uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
 {
+    return diner_render_gen_ix(scene, nullptr, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss, u_fill, seed, workspace, rgb_out,
+                               depth_out, weights_out, status, stream);
+}
+
+int diner_render_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                        const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                        const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                        float *weights_out, uint32_t *status, void *stream)
+{
     int rc;
     if (!shape) return bad("render_gen: shape is NULL");
+    if ((rc = check_index(index, "render_gen"))) return rc;
     if ((rc = gen::check_shape(*shape)) || (rc = check_scene(scene, shape->combine_layer > 0)) || (rc = check_cfg(cfg))) return rc;
     if (NR < 0) return bad("NR < 0");
     if (NR == 0 || scene->SB == 0) return DINER_OK;
@@ -495,7 +598,7 @@ int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const 
     const int64_t N = (int64_t)scene->SB * NR;
     float *z = workspace, *rgbsigma = workspace + N * cfg->n_samples;
     if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr, nullptr, stream))) return rc;
-    if ((rc = diner_render_points_gen(scene, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = diner_render_points_gen_ix(scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
@@ -503,8 +606,17 @@ int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, 
                            const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out, float *rgb_out,
                            float *depth_out, float *weights_out, uint32_t *status, void *stream)
 {
+    return diner_render_image_gen_ix(scene, nullptr, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace, rays_out, rgb_out, depth_out,
+                                     weights_out, status, stream);
+}
+
+int diner_render_image_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
+                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
+{
     int rc;
     if (!shape) return bad("render_image_gen: shape is NULL");
+    if ((rc = check_index(index, "render_image_gen"))) return rc;
     if ((rc = gen::check_shape(*shape)) || (rc = check_scene(scene, shape->combine_layer > 0)) || (rc = check_cfg(cfg))) return rc;
     if (!cam || !cam->extrinsics || !cam->intrinsics || !cam->z_near || !cam->z_far) return bad("render_image_gen: NULL camera");
     if (cam->H <= 0 || cam->W <= 0) return bad("render_image_gen: bad image size");
@@ -516,7 +628,7 @@ int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, 
     if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
                              (hipStream_t)stream)))
         return rc;
-    if ((rc = diner_render_points_gen(scene, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = diner_render_points_gen_ix(scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 

@@ -22,7 +22,8 @@ int check_launch(const char *what);
 // persistent grids, and the raised dynamic-LDS limit of a kernel (hipFuncSetAttribute acts on the current device's copy of the function).
 // Both are cached per device ordinal (api.hip); thread-safe (atomics; a race only repeats an idempotent call).
 int device_cus();                                                    // CUs of the current device (256 on MI355X)
-enum LdsSlot { LDS_SLOT_F16_LINZ = 0, LDS_SLOT_F16_LATENT = 2, LDS_SLOT_F16_TRACE = 4, LDS_SLOT_TRAIN_CORE0 = 6, LDS_SLOT_DW512 = 10, LDS_SLOT_COUNT = 12 };   // (the f16 slots come in pairs: view-sequential / views-in-tile)
+enum LdsSlot { LDS_SLOT_F16_LINZ = 0, LDS_SLOT_F16_LATENT = 2, LDS_SLOT_F16_TRACE = 4, LDS_SLOT_TRAIN_CORE0 = 6, LDS_SLOT_DW512 = 10,
+               LDS_SLOT_F16_GIX = 12, LDS_SLOT_COUNT = 16 };   // (the f16 slots come in pairs: view-sequential / views-in-tile; + LDS_SLOT_F16_GIX: the any-lookup-mode twins)
 int ensure_dynamic_lds(const void *kernel, int bytes, int slot);    // DINER_OK, or DINER_E_LAUNCH with the error set
 
 // --------------------------------------------------------------------------------------------
@@ -104,6 +105,83 @@ __device__ __forceinline__ int safe_idx(float f, int size)
 {
     int i = (int)f;  // v_cvt_i32_f32 saturates, NaN -> 0
     return i < 0 ? 0 : (i > size - 1 ? size - 1 : i);
+}
+
+// --------------------------------------------------------------------------------------------
+// latent lookup: SpatialEncoder.index (image_encoder.py:97-127) = grid_sample(align_corners=False, mode=index_interp,
+// padding_mode=index_padding) of the latent map at the feature_padding-rescaled uv.  Every mode is a footprint of at most 4 texels
+// (x0|x1) x (y0|y1) with the weights nw ne sw se, consumed in ATen's accumulation order by the gathers and by the training path's
+// scatter.  Indices are always inside the map, so every tap is readable.
+// --------------------------------------------------------------------------------------------
+struct LatentFoot {
+    int x0, x1, y0, y1;
+    float nw, ne, sw, se;
+};
+
+// ATen's reflect_coordinates(in, -1, 2 size - 1): reflect over [-0.5, size - 0.5]
+__device__ __forceinline__ float reflect_coord(float x, int size)
+{
+    const float span = (float)size;
+    const float in = fabsf(x + 0.5f);
+    const float extra = fmodf(in, span);
+    const int flips = (int)floorf(in / span);
+    return (flips & 1) ? span - extra - 0.5f : extra - 0.5f;
+}
+
+// GIX = false: bilinear / border, the instruction sequence every kernel had before the other modes existed.  GIX = true: any mode
+// (DINER_INDEX_*, uniform).  ring = 1: the map has a one-texel ring around its lw x lh interior (the zeros-padded lin_z maps,
+// diner_pack_linz_maps_ix): taps outside the interior then go to the ring with their full weight instead of weight 0; the indices
+// are those of the (lw + 2) x (lh + 2) map.
+template <bool GIX>
+__device__ __forceinline__ LatentFoot latent_footprint(float u, float w, float sxl, float syl, int lw, int lh, int interp = 0,
+                                                       int padding = 0, int ring = 0)
+{
+    LatentFoot f;
+    if (!GIX) {
+        const float ix = clipf(unnorm(u * sxl, (float)lw / 2.0f), (float)(lw - 1));
+        const float iy = clipf(unnorm(w * syl, (float)lh / 2.0f), (float)(lh - 1));
+        const float x0f = floorf(ix), y0f = floorf(iy);
+        const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
+        const int x0 = safe_idx(x0f, lw), y0 = safe_idx(y0f, lh);
+        const bool x1ok = x0 + 1 <= lw - 1, y1ok = y0 + 1 <= lh - 1;
+        f.x0 = x0; f.y0 = y0;
+        f.x1 = x1ok ? x0 + 1 : x0; f.y1 = y1ok ? y0 + 1 : y0;
+        f.nw = ey * ex; f.ne = x1ok ? ey * fx : 0.0f;   // a tap outside the map has its weight forced to 0
+        f.sw = y1ok ? fy * ex : 0.0f; f.se = (x1ok && y1ok) ? fy * fx : 0.0f;
+        return f;
+    }
+    float ix = unnorm(u * sxl, (float)lw / 2.0f), iy = unnorm(w * syl, (float)lh / 2.0f);
+    if (padding == DINER_INDEX_PAD_REFLECTION) { ix = reflect_coord(ix, lw); iy = reflect_coord(iy, lh); }
+    if (padding != DINER_INDEX_PAD_ZEROS) { ix = clipf(ix, (float)(lw - 1)); iy = clipf(iy, (float)(lh - 1)); }
+    float xa, ya, nw, ne, sw, se;
+    if (interp == DINER_INDEX_NEAREST) {
+        xa = __builtin_rintf(ix); ya = __builtin_rintf(iy);   // round half to even, like ATen's nearbyint
+        nw = 1.0f; ne = sw = se = 0.0f;
+    } else {
+        xa = floorf(ix); ya = floorf(iy);
+        const float fx = ix - xa, ex = 1.0f - fx, fy = iy - ya, ey = 1.0f - fy;
+        nw = ey * ex; ne = ey * fx; sw = fy * ex; se = fy * fx;
+    }
+    const float xb = interp == DINER_INDEX_NEAREST ? xa : xa + 1.0f, yb = interp == DINER_INDEX_NEAREST ? ya : ya + 1.0f;
+    // in-map tests on the float positions (NaN: outside)
+    const bool xa_in = xa >= 0.0f && xa <= (float)(lw - 1), xb_in = xb >= 0.0f && xb <= (float)(lw - 1);
+    const bool ya_in = ya >= 0.0f && ya <= (float)(lh - 1), yb_in = yb >= 0.0f && yb <= (float)(lh - 1);
+    if (!ring) {
+        f.nw = (xa_in && ya_in) ? nw : 0.0f; f.ne = (xb_in && ya_in) ? ne : 0.0f;
+        f.sw = (xa_in && yb_in) ? sw : 0.0f; f.se = (xb_in && yb_in) ? se : 0.0f;
+    } else {   // (a NaN position reads the ring with weight 0 instead: the result is the biases, lin_z of grid_sample's 0)
+        const bool ok = ix == ix && iy == iy;
+        f.nw = ok ? nw : 0.0f; f.ne = ok ? ne : 0.0f; f.sw = ok ? sw : 0.0f; f.se = ok ? se : 0.0f;
+        if (!ok) f.nw = 1.0f;
+    }
+    // indices clamped into [-ring, size - 1 + ring], then shifted by ring (v_cvt_i32_f32 saturates, NaN -> 0)
+    auto idx = [&](float p, int size) {
+        int i = (int)p;
+        i = i < -ring ? -ring : (i > size - 1 + ring ? size - 1 + ring : i);
+        return ring ? (p == p ? i + ring : 0) : i;
+    };
+    f.x0 = idx(xa, lw); f.x1 = idx(xb, lw); f.y0 = idx(ya, lh); f.y1 = idx(yb, lh);
+    return f;
 }
 
 // --------------------------------------------------------------------------------------------

@@ -57,6 +57,7 @@ __host__ __device__ constexpr int bias_slot_lin_z(int b) { return 1 + b; }
 __host__ __device__ constexpr int bias_slot_fc0(int b) { return 4 + b; }
 __host__ __device__ constexpr int bias_slot_fc1(int b) { return 9 + b; }
 
+#ifndef DINER_FP32_KERNEL_ONLY   // (points_mlp_ix.hip includes this file for the point kernel template alone)
 int64_t mlp_packed_floats() { return PACKED_FLOATS; }
 
 // one thread per packed weight float
@@ -92,6 +93,7 @@ int launch_pack_mlp(const DinerMlpRaw &raw, float *out, hipStream_t st)
     hipLaunchKernelGGL(pack_mlp_kernel, dim3((unsigned)((PACKED_FLOATS + 255) / 256)), dim3(256), 0, st, raw, out);
     return check_launch("pack_mlp_kernel");
 }
+#endif  // DINER_FP32_KERNEL_ONLY
 
 // ---- LDS A image ---------------------------------------------------------------------------------
 // float offset of element (row, k): [k/8][k%2][row][(k/2)%4]
@@ -169,10 +171,16 @@ struct Tap {        // bilinear footprint of one (point, view) in the latent map
     float nw, ne, sw, se;    // weights; a tap outside the map has its weight forced to 0
 };
 
+// IX: empty (bilinear / border), or <int, int> = any latent lookup mode (interp, padding: DINER_INDEX_*).  The <int, int> twin is
+// instantiated in points_mlp_ix.hip only: compiled next to the default kernel it changed that kernel's register allocation (more spills).
+template <class... IX>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_kernel(DinerScene s, const float *__restrict__ Wp,
                                                          const float *__restrict__ rays, const float *__restrict__ zsamp,
-                                                         int64_t NR, int K, float *__restrict__ rgbsigma)
+                                                         int64_t NR, int K, float *__restrict__ rgbsigma, IX... ix)
 {
+    constexpr bool GIX = sizeof...(IX) == 2;
+    const int ixv[] = {ix..., 0, 0};
+    const int ix_interp = GIX ? ixv[0] : 0, ix_padding = GIX ? ixv[1] : 0;
     __shared__ f32x4 lds[A_F4 + TILE_P * 2];  // A image + one Tap per row (all LDS in ONE array)
     f32x4 *A4 = lds;
     float *A = (float *)lds;
@@ -236,7 +244,16 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_kernel(DinerScene s, c
                 else val = 0.0f;
                 A[a_off(row, e)] = val;
             }
-            if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127)
+            if (wave == 0 && GIX) {  // footprint of any lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
+                const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
+                Tap t;
+                const int f4 = HID / 4;
+                t.o00 = (f.y0 * s.w + f.x0) * f4; t.o01 = (f.y0 * s.w + f.x1) * f4;
+                t.o10 = (f.y1 * s.w + f.x0) * f4; t.o11 = (f.y1 * s.w + f.x1) * f4;
+                t.nw = f.nw; t.ne = f.ne; t.sw = f.sw; t.se = f.se;
+                taps[row] = t;
+            } else if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127; = latent_footprint<false>,
+                                     // written out: through the helper the compiler schedules this kernel differently)
                 const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
                 const float iy = clipf(unnorm(w * syl, (float)s.h / 2.0f), (float)(s.h - 1));
                 const float x0f = floorf(ix), y0f = floorf(iy);
@@ -346,6 +363,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_kernel(DinerScene s, c
     }
 }
 
+#ifndef DINER_FP32_KERNEL_ONLY
 // ---- once per encode(): G_b = lin_z[b](latent) as three extra feature maps ------------------------
 // lin_z is linear and SpatialEncoder.index is a convex combination of 4 texels, so
 //   lin_z[b](bilerp(F)(uv)) = bilerp(lin_z[b](F))(uv)            (resnetfc.py:152, image_encoder.py:97-127)
@@ -358,9 +376,16 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_kernel(DinerScene s, c
 //   map b >= 1 also carries fc_1[b-1]'s   (x = x + fc_1(...) + b1; x += lin_z[b](z)        resnetfc.py:69,152),
 // so the per-point kernel adds three bias vectors per view fewer (points_mlp_f16.hip, LINZ path).
 // in: latent [N,h,w,512] NHWC rows; out: [3][N,h,w,512].
+// RING (zeros padding, diner_pack_linz_maps_ix): out [3][N,h+2,w+2,512], output row r = texel (y, x) of the ringed map of image n; the
+// ring texels are evaluated on a latent of 0 -- they hold the biases alone, lin_z[b] of what grid_sample returns outside the map.
+// (HW: empty, or <int, int> = (h, w) of the ringed maps)
+template <class... HW>
 __global__ __launch_bounds__(NWAVES * 64) void linz_maps_kernel(const float *__restrict__ latent, int64_t rows,
-                                                                const float *__restrict__ Wp, float *__restrict__ out)
+                                                                const float *__restrict__ Wp, float *__restrict__ out, HW... hw)
 {
+    constexpr bool RING = sizeof...(HW) == 2;
+    const int hwv[] = {hw..., 0, 0};
+    const int h = hwv[0], w = hwv[1];
     __shared__ f32x4 lds[A_F4];
     f32x4 *A4 = lds;
     float *A = (float *)lds;
@@ -369,12 +394,20 @@ __global__ __launch_bounds__(NWAVES * 64) void linz_maps_kernel(const float *__r
     // stage 64 latent rows (2 KiB each) into the A image
     for (int rr = 0; rr < TILE_P / NWAVES; ++rr) {
         const int r = wave * (TILE_P / NWAVES) + rr;
-        const int64_t gr = row0 + r < rows ? row0 + r : rows - 1;
+        int64_t gr = row0 + r < rows ? row0 + r : rows - 1;
+        bool inside = true;
+        if (RING) {   // (wave-uniform) ringed row -> latent row
+            const int64_t mw = w + 2, per = (int64_t)(h + 2) * mw, n = gr / per, t = gr - n * per;
+            const int y = (int)(t / mw) - 1, x = (int)(t - (t / mw) * mw) - 1;
+            inside = x >= 0 && x < w && y >= 0 && y < h;
+            gr = inside ? (n * h + y) * w + x : 0;
+        }
         const f32x4 *src = (const f32x4 *)(latent + gr * HID);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int q = lane + 64 * half;
-            const f32x4 v = src[q];
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (inside) v = src[q];
 #pragma unroll
             for (int i = 0; i < 4; ++i) A[a_off(r, 4 * q + i)] = v[i];
         }
@@ -403,13 +436,26 @@ __global__ __launch_bounds__(NWAVES * 64) void linz_maps_kernel(const float *__r
 int launch_linz_maps(const float *latent_nhwc, int64_t rows, const float *mlp_packed, float *out, hipStream_t st)
 {
     if (rows == 0) return DINER_OK;
-    hipLaunchKernelGGL(linz_maps_kernel, dim3((unsigned)((rows + TILE_P - 1) / TILE_P)), dim3(NWAVES * 64), 0, st, latent_nhwc,
+    hipLaunchKernelGGL(linz_maps_kernel<>, dim3((unsigned)((rows + TILE_P - 1) / TILE_P)), dim3(NWAVES * 64), 0, st, latent_nhwc,
                        rows, mlp_packed, out);
     return check_launch("linz_maps_kernel");
 }
 
-int launch_points_mlp(const DinerScene &s, const float *mlp_packed, const float *rays, const float *z, int64_t NR,
-                      int K, float *rgbsigma, hipStream_t st)
+// the ringed maps of zeros padding: N images of (h+2) x (w+2) texels
+int launch_linz_maps_ring(const float *latent_nhwc, int64_t N, int h, int w, const float *mlp_packed, float *out, hipStream_t st)
+{
+    const int64_t rows = N * (h + 2) * (int64_t)(w + 2);
+    if (rows == 0) return DINER_OK;
+    hipLaunchKernelGGL((linz_maps_kernel<int, int>), dim3((unsigned)((rows + TILE_P - 1) / TILE_P)), dim3(NWAVES * 64), 0, st, latent_nhwc,
+                       rows, mlp_packed, out, h, w);
+    return check_launch("linz_maps_kernel<ring>");
+}
+
+int launch_points_mlp_ix_kernel(const DinerScene &s, int interp, int padding, const float *mlp_packed, const float *rays, const float *z,
+                                int64_t NR, int K, int64_t tiles, float *rgbsigma, hipStream_t st);   // points_mlp_ix.hip
+
+int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const float *mlp_packed, const float *rays, const float *z,
+                      int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {
     const int64_t P = NR * (int64_t)K;
     if (P == 0 || s.SB == 0) return DINER_OK;
@@ -417,9 +463,12 @@ int launch_points_mlp(const DinerScene &s, const float *mlp_packed, const float 
     if (s.num_freqs != 6) { set_error("render_points: num_freqs=%d unsupported (need 6)", s.num_freqs); return DINER_E_UNSUPPORTED; }
     const int64_t tiles = (P + TILE_P - 1) / TILE_P;
     if (tiles > 0x7fffffffLL) { set_error("render_points: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
-    hipLaunchKernelGGL(points_mlp_kernel, dim3((unsigned)tiles, (unsigned)s.SB), dim3(NWAVES * 64), 0, st, s, mlp_packed, rays, z,
+    if (ix.interp != DINER_INDEX_BILINEAR || ix.padding != DINER_INDEX_PAD_BORDER)   // any other lookup mode: the twin of points_mlp_ix.hip
+        return launch_points_mlp_ix_kernel(s, (int)ix.interp, (int)ix.padding, mlp_packed, rays, z, NR, K, tiles, rgbsigma, st);
+    hipLaunchKernelGGL(points_mlp_kernel<>, dim3((unsigned)tiles, (unsigned)s.SB), dim3(NWAVES * 64), 0, st, s, mlp_packed, rays, z,
                        NR, K, rgbsigma);
     return check_launch("points_mlp_kernel");
 }
+#endif  // DINER_FP32_KERNEL_ONLY
 
 }  // namespace diner

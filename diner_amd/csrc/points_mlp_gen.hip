@@ -75,6 +75,7 @@ static Layout layout_of(const DinerMlpShape &m)
     return L;
 }
 
+#ifndef DINER_GEN_IX
 // DINER_OK, or DINER_E_UNSUPPORTED with the reason in diner_last_error()
 int check_shape(const DinerMlpShape &m)
 {
@@ -143,6 +144,7 @@ int launch_pack_mlp(const DinerMlpShape &m, const DinerMlpGenRaw &raw, float *ou
     if ((rc = pack_layer(raw.lin_out_w, L.H, 4, L.H / 8, 1, out + L.off_out, st))) return rc;
     return pack_bias(raw.lin_out_b, 4, 32, bias + L.bias_lin_out(), st);
 }
+#endif  // DINER_GEN_IX
 
 // ---- LDS A image (points_mlp.hip) -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int a_off(int row, int k) { return ((((k >> 3) * 2 + (k & 1)) * TILE_P + row) << 2) + ((k >> 1) & 3); }
@@ -236,11 +238,26 @@ struct Tap {        // bilinear footprint of one (point, view) in the latent map
     float nw, ne, sw, se;    // weights; a tap outside the map has its weight forced to 0
 };
 
+// points_mlp_gen_ix.hip compiles this file a second time with DINER_GEN_IX defined: the kernel is then points_mlp_gen_ix_kernel, which
+// serves every other latent lookup mode (ix_interp / ix_padding, DINER_INDEX_*; common.hpp latent_footprint).  Its own translation
+// unit keeps this one's code object -- the three bilinear / border kernels -- exactly what it was.
+#ifndef DINER_GEN_IX
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
                                                                      const float *__restrict__ rays, const float *__restrict__ zsamp,
                                                                      int64_t NR, int K, float *__restrict__ rgbsigma)
 {
+    constexpr bool GIX = false;
+    const int ix_interp = 0, ix_padding = 0;
+#else
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                        const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                        int64_t NR, int K, float *__restrict__ rgbsigma, int ix_interp,
+                                                                        int ix_padding)
+{
+    constexpr bool GIX = true;
+#endif
     __shared__ f32x4 lds[A_F4 + TILE_P * 2];  // A image + one Tap per row
     f32x4 *A4 = lds;
     float *A = (float *)lds;
@@ -305,7 +322,15 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
                 else val = 0.0f;
                 A[a_off(row, e)] = val;
             }
-            if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127)
+            if (wave == 0 && GIX) {  // footprint of any lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
+                const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
+                Tap t;
+                t.o00 = (f.y0 * s.w + f.x0) * c4; t.o01 = (f.y0 * s.w + f.x1) * c4;
+                t.o10 = (f.y1 * s.w + f.x0) * c4; t.o11 = (f.y1 * s.w + f.x1) * c4;
+                t.nw = f.nw; t.ne = f.ne; t.sw = f.sw; t.se = f.se;
+                taps[row] = t;
+            } else if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127; = latent_footprint<false>,
+                                     // written out: through the helper the compiler schedules this kernel differently)
                 const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
                 const float iy = clipf(unnorm(w * syl, (float)s.h / 2.0f), (float)(s.h - 1));
                 const float x0f = floorf(ix), y0f = floorf(iy);
@@ -415,14 +440,31 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
     }
 }
 
+#ifdef DINER_GEN_IX
+int launch_points_mlp_ix(const DinerScene &s, const Layout &L, int d_hidden, int ix_interp, int ix_padding, const float *mlp_packed,
+                         const float *rays, const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
+{
+    const dim3 grid((unsigned)((NR * (int64_t)K + TILE_P - 1) / TILE_P), (unsigned)s.SB), block(NWAVES * 64);
+    if (d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_ix_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_interp, ix_padding);
+    else if (d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_ix_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_interp, ix_padding);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_ix_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_interp, ix_padding);
+    return check_launch("points_mlp_gen_ix_kernel");
+}
+#else
+int launch_points_mlp_ix(const DinerScene &, const Layout &, int, int, int, const float *, const float *, const float *, int64_t, int,
+                         float *, hipStream_t);   // points_mlp_gen_ix.hip
+
 // the instantiation a d_hidden runs on: <1,1> for up to 128 columns, <2,1> up to 256, <2,2> up to 512
 const char *kernel_name(int d_hidden)
 {
     return d_hidden <= 128 ? "points_mlp_gen_kernel<1,1>" : d_hidden <= 256 ? "points_mlp_gen_kernel<2,1>" : "points_mlp_gen_kernel<2,2>";
 }
 
-int launch_points_mlp(const DinerScene &s, const DinerMlpShape &m, const float *mlp_packed, const float *rays, const float *z, int64_t NR,
-                      int K, float *rgbsigma, hipStream_t st)
+int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const DinerMlpShape &m, const float *mlp_packed, const float *rays,
+                      const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {
     int rc;
     if ((rc = check_shape(m))) return rc;
@@ -438,6 +480,8 @@ int launch_points_mlp(const DinerScene &s, const DinerMlpShape &m, const float *
     const int64_t tiles = (P + TILE_P - 1) / TILE_P;
     if (tiles > 0x7fffffffLL) { set_error("render_points_gen: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
     const Layout L = layout_of(m);
+    if (ix.interp != DINER_INDEX_BILINEAR || ix.padding != DINER_INDEX_PAD_BORDER)
+        return launch_points_mlp_ix(s, L, m.d_hidden, ix.interp, ix.padding, mlp_packed, rays, z, NR, K, rgbsigma, st);
     const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);
     if (m.d_hidden <= 128)
         hipLaunchKernelGGL((points_mlp_gen_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma);
@@ -447,6 +491,7 @@ int launch_points_mlp(const DinerScene &s, const DinerMlpShape &m, const float *
         hipLaunchKernelGGL((points_mlp_gen_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma);
     return check_launch(kernel_name(m.d_hidden));
 }
+#endif  // DINER_GEN_IX
 
 }  // namespace gen
 }  // namespace diner

@@ -956,12 +956,16 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ d
 // ---- per-(view, point) MLP inputs: in55 (padded to 56), bilinear latent z, and the footprint ------------------
 // rows are view-major: row = v*P + p.  latent is the reference's NCHW tensor [NV,C,h,w] (its gradient has
 // that layout too).  taps_out [R,8] = 4 texel indices (y*w+x, as int bits) + 4 weights.
-template <bool NHWC>
+// IX: empty (bilinear / border), or <int, int> = any latent lookup mode (interp, padding: DINER_INDEX_*)
+template <bool NHWC, class... IX>
 __global__ __launch_bounds__(64) void point_inputs_kernel(DinerScene s, const float *__restrict__ latent_nchw,
                                                           const float *__restrict__ rays, const float *__restrict__ zsamp,
                                                           int64_t NR, int K, int sb, float *__restrict__ in56,
-                                                          float *__restrict__ zlat, float *__restrict__ taps_out)
+                                                          float *__restrict__ zlat, float *__restrict__ taps_out, IX... ix)
 {
+    constexpr bool GIX = sizeof...(IX) == 2;
+    const int ixv[] = {ix..., 0, 0};
+    const int ix_interp = GIX ? ixv[0] : 0, ix_padding = GIX ? ixv[1] : 0;
     const int64_t P = NR * (int64_t)K, row = blockIdx.x;
     const int v = (int)(row / P);
     const int64_t p = row - (int64_t)v * P;
@@ -992,17 +996,25 @@ __global__ __launch_bounds__(64) void point_inputs_kernel(DinerScene s, const fl
         else val = 0.0f;
         in56[row * 56 + e] = val;
     }
-    // bilinear / border footprint (image_encoder.py:97-127)
+    // footprint in the latent map (image_encoder.py:97-127; common.hpp)
     const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-    const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
-    const float iy = clipf(unnorm(w * syl, (float)s.h / 2.0f), (float)(s.h - 1));
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
-    const int x0 = safe_idx(x0f, s.w), y0 = safe_idx(y0f, s.h);
-    const bool x1ok = x0 + 1 <= s.w - 1, y1ok = y0 + 1 <= s.h - 1;
-    const int x1 = x1ok ? x0 + 1 : x0, y1 = y1ok ? y0 + 1 : y0;
-    const int o[4] = {y0 * s.w + x0, y0 * s.w + x1, y1 * s.w + x0, y1 * s.w + x1};
-    const float wt[4] = {ey * ex, x1ok ? ey * fx : 0.0f, y1ok ? fy * ex : 0.0f, (x1ok && y1ok) ? fy * fx : 0.0f};
+    int o[4];
+    float wt[4];
+    if (GIX) {
+        const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
+        o[0] = f.y0 * s.w + f.x0; o[1] = f.y0 * s.w + f.x1; o[2] = f.y1 * s.w + f.x0; o[3] = f.y1 * s.w + f.x1;
+        wt[0] = f.nw; wt[1] = f.ne; wt[2] = f.sw; wt[3] = f.se;
+    } else {   // bilinear / border (= latent_footprint<false>, written out: through the helper the compiler schedules this kernel differently)
+        const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
+        const float iy = clipf(unnorm(w * syl, (float)s.h / 2.0f), (float)(s.h - 1));
+        const float x0f = floorf(ix), y0f = floorf(iy);
+        const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
+        const int x0 = safe_idx(x0f, s.w), y0 = safe_idx(y0f, s.h);
+        const bool x1ok = x0 + 1 <= s.w - 1, y1ok = y0 + 1 <= s.h - 1;
+        const int x1 = x1ok ? x0 + 1 : x0, y1 = y1ok ? y0 + 1 : y0;
+        o[0] = y0 * s.w + x0; o[1] = y0 * s.w + x1; o[2] = y1 * s.w + x0; o[3] = y1 * s.w + x1;
+        wt[0] = ey * ex; wt[1] = x1ok ? ey * fx : 0.0f; wt[2] = y1ok ? fy * ex : 0.0f; wt[3] = (x1ok && y1ok) ? fy * fx : 0.0f;
+    }
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { taps_out[row * 8 + i] = __int_as_float(o[i]); taps_out[row * 8 + 4 + i] = wt[i]; }
@@ -1018,7 +1030,9 @@ __global__ __launch_bounds__(64) void point_inputs_kernel(DinerScene s, const fl
     }
 }
 
-// dlatent_nhwc[v][texel][ch] += dz[row][ch] * w_tap  (bilinear backward; atomics: several points share a texel).
+// dlatent_nhwc[v][texel][ch] += dz[row][ch] * w_tap  (grid_sample's input gradient; atomics: several points share a texel).
+// Every lookup mode arrives here as 4 taps: a tap of weight 0 (zeros padding outside the map, the unused taps of nearest, which
+// repeat the picked texel's index) adds nothing and is never flushed, so a run still merges exactly the rows whose four indices agree.
 // The target is NHWC on purpose: a wave's 64 channels of one texel are 256 contiguous bytes, the shape in which
 // float atomics run at the full memory-side rate (64 lanes in 64 different rows are ~17x slower: scattering
 // straight into the reference's NCHW layout took 82 ms per step, this + the transpose below 5 ms).
@@ -1218,13 +1232,18 @@ int launch_train_colsum(const float *dY, int64_t M, int N, int64_t ld, float *db
     return check_launch("train::colsum_kernel");
 }
 
-int launch_train_point_inputs(const DinerScene &s, const float *latent, int nhwc, const float *rays, const float *z, int64_t NR, int K,
-                              int sb, float *in56, float *zlat, float *taps, hipStream_t st)
+int launch_train_point_inputs(const DinerScene &s, const DinerLatentIndex &ix, const float *latent, int nhwc, const float *rays, const float *z,
+                              int64_t NR, int K, int sb, float *in56, float *zlat, float *taps, hipStream_t st)
 {
     const int64_t R = NR * (int64_t)K * s.NV;
     if (R == 0) return DINER_OK;
-    if (nhwc) hipLaunchKernelGGL((point_inputs_kernel<true>), dim3((unsigned)R), dim3(64), 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps);
-    else hipLaunchKernelGGL((point_inputs_kernel<false>), dim3((unsigned)R), dim3(64), 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps);
+    const dim3 g((unsigned)R), b(64);
+    const int ii = ix.interp, ip = ix.padding;
+    if (ii != DINER_INDEX_BILINEAR || ip != DINER_INDEX_PAD_BORDER) {
+        if (nhwc) hipLaunchKernelGGL((point_inputs_kernel<true, int, int>), g, b, 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps, ii, ip);
+        else hipLaunchKernelGGL((point_inputs_kernel<false, int, int>), g, b, 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps, ii, ip);
+    } else if (nhwc) hipLaunchKernelGGL((point_inputs_kernel<true>), g, b, 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps);
+    else hipLaunchKernelGGL((point_inputs_kernel<false>), g, b, 0, st, s, latent, rays, z, NR, K, sb, in56, zlat, taps);
     return check_launch("train::point_inputs_kernel");
 }
 

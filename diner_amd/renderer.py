@@ -269,8 +269,7 @@ class NeRFRendererDGS(torch.nn.Module):
         """The shape of ``model``'s fusion MLP and encodings; raises ``NotImplementedError`` naming what lies outside what the kernels
         serve: the standard shape (the 512-wide kernels) and the envelope of the shape-general kernel (include/diner_hip.h)."""
         enc, mlp = model.encoder, model.mlp_fine
-        if getattr(enc, "index_interp", "bilinear") != "bilinear" or getattr(enc, "index_padding", "border") != "border":
-            raise NotImplementedError("only index_interp='bilinear', index_padding='border' (image_encoder.py:24-25)")
+        NeRFRendererDGS._latent_index(model)
         if getattr(mlp, "combine_type", "average") != "average":
             raise NotImplementedError(f"only combine_type='average' (resnetfc.py:9-14), not {mlp.combine_type!r}")
         act = getattr(mlp, "activation", torch.nn.ReLU())
@@ -312,6 +311,20 @@ class NeRFRendererDGS(torch.nn.Module):
             raise NotImplementedError("fusion MLP shape outside what the kernels serve: " + "; ".join(why) +
                                       f" (standard shape {tuple(STANDARD_SHAPE)[:6]} or the shape-general envelope, include/diner_hip.h)")
         return shape
+
+    @staticmethod
+    def _latent_index(model) -> Optional[_lib.DinerLatentIndex]:
+        """The encoder's latent lookup (SpatialEncoder index_interp / index_padding, image_encoder.py:24-25,119-125): None for the
+        default bilinear / border (the entry points and torch ops without _ix), else the DinerLatentIndex of the _ix entry points.
+        Raises ``NotImplementedError`` for a mode no kernel serves (bicubic: 16 taps)."""
+        interp = getattr(model.encoder, "index_interp", "bilinear")
+        padding = getattr(model.encoder, "index_padding", "border")
+        if interp not in _lib.INDEX_INTERP or padding not in _lib.INDEX_PADDING:
+            raise NotImplementedError(f"latent lookup index_interp={interp!r}, index_padding={padding!r} unsupported: index_interp in "
+                                      f"{sorted(_lib.INDEX_INTERP)}, index_padding in {sorted(_lib.INDEX_PADDING)} (image_encoder.py:24-25)")
+        if interp == "bilinear" and padding == "border":
+            return None
+        return _lib.DinerLatentIndex(_lib.INDEX_INTERP[interp], _lib.INDEX_PADDING[padding])
 
     def _route(self, model) -> MlpShape:
         """validate ``model``; for a shape that takes the shape-general kernel, settle the precision (fp32 is what runs)"""
@@ -367,15 +380,25 @@ class NeRFRendererDGS(torch.nn.Module):
         maps, poses, focal, c, ishape = self._maps_pack
         latent = self._latent_pack if need_latent else None
         linz = None
-        linz_bytes = 3 * latent.numel() * 4 if latent is not None else 0
+        ix = self._latent_index(model)
+        ring = 2 if ix is not None and ix.padding == _lib.INDEX_PADDING["zeros"] else 0   # zeros padding: the ringed maps
+        linz_bytes = 3 * latent.numel() // (latent.shape[2] * latent.shape[3]) * (latent.shape[2] + ring) * (latent.shape[3] + ring) * 4 \
+            if latent is not None else 0
         if (need_latent and packed_mlp is not None and self.linz_maps and self.precision == "f16x3"
                 and (self.linz_maps_max_bytes is None or linz_bytes <= self.linz_maps_max_bytes)):
-            zkey = (self._latent_gen, self._mlp_gen)   # generations of the two packs the maps were computed from
+            # generations of the two packs the maps were computed from, and the lookup mode (zeros padding: other maps)
+            zkey = (self._latent_gen, self._mlp_gen, None if ix is None else (ix.interp, ix.padding))
             if zkey != self._linz_key:
                 SB, NV, h, w, Cc = latent.shape
-                out = torch.empty((3, SB, NV, h, w, Cc), dtype=torch.float32, device=dev)
-                check(_lib.lib().diner_pack_linz_maps(_ptr(latent), SB * NV, h, w, _ptr(packed_mlp), _ptr(out), _stream(dev)),
-                      "diner_pack_linz_maps")
+                if ix is None:
+                    out = torch.empty((3, SB, NV, h, w, Cc), dtype=torch.float32, device=dev)
+                    check(_lib.lib().diner_pack_linz_maps(_ptr(latent), SB * NV, h, w, _ptr(packed_mlp), _ptr(out), _stream(dev)),
+                          "diner_pack_linz_maps")
+                else:
+                    out = torch.empty((3, SB, NV, h + ring, w + ring, Cc), dtype=torch.float32, device=dev)
+                    assert out.numel() == int(_lib.lib().diner_linz_maps_floats(SB * NV, h, w, C.byref(ix)))
+                    check(_lib.lib().diner_pack_linz_maps_ix(_ptr(latent), SB * NV, h, w, _ptr(packed_mlp), C.byref(ix), _ptr(out),
+                                                             _stream(dev)), "diner_pack_linz_maps_ix")
                 self._linz_pack, self._linz_key = out, zkey
             linz = self._linz_pack
         SB, NV, H, W, _ = maps.shape
@@ -591,9 +614,13 @@ class NeRFRendererDGS(torch.nn.Module):
             sc, _keep = self._scene(model, need_latent=True)
             assert SB == sc.SB
             out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
-            cs = shape.c_struct()
-            check(_lib.lib().diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out),
-                                                     _stream(r.device)), "diner_render_points_gen")
+            cs, ix = shape.c_struct(), self._latent_index(model)
+            if ix is None:
+                check(_lib.lib().diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out),
+                                                         _stream(r.device)), "diner_render_points_gen")
+            else:
+                check(_lib.lib().diner_render_points_gen_ix(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K,
+                                                            _ptr(out), _stream(r.device)), "diner_render_points_gen_ix")
             self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
             return out
         packed = self._mlp(model)
@@ -603,9 +630,14 @@ class NeRFRendererDGS(torch.nn.Module):
         prec = _lib.PRECISIONS[self.precision]
         n_scr = int(_lib.lib().diner_render_points_scratch_floats(SB, sc.NV, prec))
         scr = torch.empty(n_scr, dtype=torch.float32, device=r.device) if n_scr else None
-        check(_lib.lib().diner_render_points(C.byref(sc), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
-                                             _ptr(out), _stream(r.device)),
-              "diner_render_points")
+        ix = self._latent_index(model)
+        if ix is None:
+            check(_lib.lib().diner_render_points(C.byref(sc), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
+                                                 _ptr(out), _stream(r.device)),
+                  "diner_render_points")
+        else:
+            check(_lib.lib().diner_render_points_ix(C.byref(sc), C.byref(ix), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
+                                                    _ptr(out), _stream(r.device)), "diner_render_points_ix")
         self.last_route, self.last_binding = ("points_mlp_f16" if self.precision == "f16x3" else "points_mlp"), "ctypes"
         return out
 
@@ -680,7 +712,8 @@ class NeRFRendererDGS(torch.nn.Module):
                 L, st, seed = _lib.lib(), _stream(dev), self._next_seed()
                 self._poll_status()
                 status = _ptr(self._status_word(dev))
-                use_ops = self.stage_events is None and noise is None and self.binding == "torch_ops"
+                ix = self._latent_index(model)   # another lookup mode than bilinear / border: the _ix entry points, through ctypes
+                use_ops = self.stage_events is None and noise is None and self.binding == "torch_ops" and ix is None
                 if not use_ops:    # (the op allocates its own workspace and outputs: never both sets at once)
                     ws = torch.empty(int(L.diner_render_workspace_floats(SB, NR, K, sc.NV, prec)), dtype=torch.float32, device=dev)
                     rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
@@ -694,10 +727,14 @@ class NeRFRendererDGS(torch.nn.Module):
                                                         cfg.n_gaussian, cfg.depth_diff_max, bool(self.white_bkgd), prec, seed - (1 << 64) if seed >= (1 << 63) else seed,
                                                         bool(want_weights), self._status_word(dev))
                     weights = w_ if want_weights else None
-                elif self.stage_events is None:
+                elif self.stage_events is None and ix is None:
                     check(L.diner_render(C.byref(sc), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
                                          prec, _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth),
                                          _ptr(weights), status, st), "diner_render")
+                elif self.stage_events is None:
+                    check(L.diner_render_ix(C.byref(sc), C.byref(ix), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                                            prec, _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth),
+                                            _ptr(weights), status, st), "diner_render_ix")
                 else:
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
                     z, c, scr = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5], ws[SB * NR * K * 5:]
@@ -705,9 +742,9 @@ class NeRFRendererDGS(torch.nn.Module):
                     check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
                                                      None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
                     ev[1].record()
-                    check(L.diner_render_points(C.byref(sc), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec,
-                                                _ptr(scr) if scr.numel() else None, _ptr(c), st),
-                          "diner_render_points")
+                    check(L.diner_render_points_ix(C.byref(sc), C.byref(ix) if ix is not None else None, _ptr(packed), _ptr(r), _ptr(z),
+                                                   NR, K, prec, _ptr(scr) if scr.numel() else None, _ptr(c), st),
+                          "diner_render_points_ix")
                     ev[2].record()
                     check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
                                             _ptr(depth), _ptr(weights), status, st), "diner_composite")
@@ -733,7 +770,8 @@ class NeRFRendererDGS(torch.nn.Module):
         sc, _keep = self._scene(model, need_latent=True)
         assert SB == sc.SB
         cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
-        cs = shape.c_struct()
+        cs, ix = shape.c_struct(), self._latent_index(model)
+        ixp = C.byref(ix) if ix is not None else None
         u_c = n_g = u_f = None
         if noise is not None:
             u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
@@ -745,9 +783,14 @@ class NeRFRendererDGS(torch.nn.Module):
         depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
         weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
         if self.stage_events is None:
-            check(L.diner_render_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st),
-                  "diner_render_gen")
+            if ix is None:
+                check(L.diner_render_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st),
+                      "diner_render_gen")
+            else:
+                check(L.diner_render_gen_ix(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                                            _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status,
+                                            st), "diner_render_gen_ix")
         else:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
@@ -755,8 +798,8 @@ class NeRFRendererDGS(torch.nn.Module):
             check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
                                              None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
             ev[1].record()
-            check(L.diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st),
-                  "diner_render_points_gen")
+            check(L.diner_render_points_gen_ix(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st),
+                  "diner_render_points_gen_ix")
             ev[2].record()
             check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
                                     _ptr(depth), _ptr(weights), status, st), "diner_composite")
@@ -797,7 +840,18 @@ class NeRFRendererDGS(torch.nn.Module):
         L = _lib.lib()
         self._poll_status()
         seed = self._next_seed()
-        if gen:
+        ix = self._latent_index(model)   # another lookup mode than bilinear / border: the _ix entry points, through ctypes
+        if gen and ix is not None:
+            cs = shape.c_struct()
+            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
+                             dtype=torch.float32, device=dev)
+            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
+            check(L.diner_render_image_gen_ix(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg),
+                                              int(bool(self.white_bkgd)), seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None,
+                                              _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image_gen_ix")
+            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+        elif gen:
             cs = shape.c_struct()
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
                              dtype=torch.float32, device=dev)
@@ -807,6 +861,13 @@ class NeRFRendererDGS(torch.nn.Module):
                                            seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
                   "diner_render_image_gen")
             self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+        elif ix is not None:
+            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, prec)), dtype=torch.float32, device=dev)
+            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
+            check(L.diner_render_image_ix(C.byref(sc), C.byref(ix), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec,
+                                          seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
+                  "diner_render_image_ix")
         elif self.binding == "torch_ops":
             from . import ops as _ops
             maps_t, poses_t, focal_t, c_t, latent_t, linz_t = _keep
@@ -822,7 +883,7 @@ class NeRFRendererDGS(torch.nn.Module):
                                        _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image")
         if not gen:
             self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
-            self.last_binding = self.binding
+            self.last_binding = self.binding if ix is None else "ctypes"
         self._after_launch(dev, sync=self.finite_check != "off")    # once per frame: a NaN image never leaves this function
         rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
         if return_depth:

@@ -186,7 +186,7 @@ class _RenderFn(torch.autograd.Function):
     """(latent, *mlp_params) -> (rgb, depth, weights) for fixed rays / samples."""
 
     @staticmethod
-    def forward(ctx, renderer, scene, rays, z, latent, *params):
+    def forward(ctx, renderer, scene, ix, rays, z, latent, *params):
         L = _lib.lib()
         dev = rays.device
         st = _st(dev)
@@ -213,8 +213,12 @@ class _RenderFn(torch.autograd.Function):
         wp[0] = cache.get(0, params[0], w_in56, False, prec)
         for sb in range(SB):
             in56, zl, taps = f(R, 56), f(R, HID), f(R, 8)
-            check(L.diner_train_point_inputs(C.byref(scene), _p(lat_nhwc), 1, _p(rays), _p(z), NR, K, sb, _p(in56), _p(zl), _p(taps), st),
-                  "diner_train_point_inputs")
+            if ix is None:
+                check(L.diner_train_point_inputs(C.byref(scene), _p(lat_nhwc), 1, _p(rays), _p(z), NR, K, sb, _p(in56), _p(zl), _p(taps), st),
+                      "diner_train_point_inputs")
+            else:   # another latent lookup mode: its taps, which are also where the latent's gradient goes (the scatter is unchanged)
+                check(L.diner_train_point_inputs_ix(C.byref(scene), C.byref(ix), _p(lat_nhwc), 1, _p(rays), _p(z), NR, K, sb, _p(in56), _p(zl),
+                                                    _p(taps), st), "diner_train_point_inputs_ix")
             x = f(R, HID)
             linear_fwd(in56, w_in56, prm[1], x, prec=prec, panel=wp[0])                          # resnetfc.py:139
             xs, nets = [], []
@@ -326,10 +330,11 @@ class _RenderFn(torch.autograd.Function):
         check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
         g[0] = g_in56[:, :55].contiguous()
         g[1] = g[3].clone()  # lin_in's bias sees the same dY as lin_z[0]'s: x = lin_in(..) + lin_z[0](z)
-        return (None, None, None, None, d_lat) + tuple(g)
+        return (None, None, None, None, None, d_lat) + tuple(g)
 
 
 def render_with_grad(renderer, model, rays, z, scene):
     """rgb, depth, weights = composite(model, rays, z) with gradients to the MLP parameters and encoder.latent."""
     params = _mlp_params(model.mlp_fine)
-    return _RenderFn.apply(renderer, scene, rays, z, model.encoder.latent, *params)
+    ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
+    return _RenderFn.apply(renderer, scene, ix, rays, z, model.encoder.latent, *params)

@@ -93,6 +93,24 @@ typedef struct DinerTargetCam {
     int32_t H, W;            /* target image size: rays per scene = H*W, ray r = pixel (r / W, r % W) */
 } DinerTargetCam;
 
+/* SpatialEncoder.index's grid_sample settings (src/models/image_encoder.py:24-25,119-125: align_corners=False, mode=index_interp,
+ * padding_mode=index_padding), the lookup of the latent features of every point.  Every mode is a footprint of at most 4 texels with
+ * weights, evaluated like ATen's grid_sample after the feature_padding rescale of the coordinate:
+ *   border     (default): ix clipped to [0, w-1];
+ *   reflection: ix reflected over [-0.5, w-0.5] (ATen's reflect_coordinates), then clipped to [0, w-1];
+ *   zeros:      ix not clipped; a tap outside the map has weight 0 (the others are not renormalised);
+ *   nearest:    one tap of weight 1 at rint(ix), rint(iy) (half to even) of the padded coordinate (zeros: 0 outside the map).
+ * The entry points without the _ix suffix are the bilinear / border case of their _ix form.  Unknown values: DINER_E_INVALID. */
+#define DINER_INDEX_BILINEAR 0
+#define DINER_INDEX_NEAREST 1
+#define DINER_INDEX_PAD_BORDER 0
+#define DINER_INDEX_PAD_ZEROS 1
+#define DINER_INDEX_PAD_REFLECTION 2
+typedef struct DinerLatentIndex {
+    int32_t interp;          /* DINER_INDEX_BILINEAR | DINER_INDEX_NEAREST */
+    int32_t padding;         /* DINER_INDEX_PAD_BORDER | _ZEROS | _REFLECTION */
+} DinerLatentIndex;
+
 /* Version of THIS ABI (argument lists, struct layouts).  Bumped by every incompatible change; a binding compiled or written
  * against another value must refuse to call in: diner_version() returns the value the loaded library was built with, the
  * torch-ops extension checks it at every op entry, diner_amd/_lib.py at load time.  (2: diner_render / diner_composite gained
@@ -142,6 +160,14 @@ int diner_pack_mlp(const DinerMlpRaw *raw, float *packed_out, void *stream);
  * latent_packed [N,h,w,512] from diner_pack_latent, mlp_packed from diner_pack_mlp -> out [3][N,h,w,512]. */
 int diner_pack_linz_maps(const float *latent_packed, int64_t N, int32_t h, int32_t w, const float *mlp_packed,
                          float *out, void *stream);
+/* The maps for a lookup mode.  With DINER_INDEX_PAD_ZEROS the convex-combination argument above fails near the border (the weights
+ * of the in-map taps sum to less than 1, and the folded biases would shrink with them), so the maps get a one-texel ring of texels
+ * that hold lin_z[b](0) + the folded biases, i.e. the biases alone: out [3][N,h+2,w+2,512], the interior at (y+1, x+1).  The F16X3
+ * kernel then sends the taps outside the map to the ring with their full weight, and the weights again sum to 1.  Every other
+ * mode: exactly diner_pack_linz_maps.  diner_linz_maps_floats gives the size of `out`. */
+int64_t diner_linz_maps_floats(int64_t N, int32_t h, int32_t w, const DinerLatentIndex *index);
+int diner_pack_linz_maps_ix(const float *latent_packed, int64_t N, int32_t h, int32_t w, const float *mlp_packed,
+                            const DinerLatentIndex *index, float *out, void *stream);
 
 /* ---- the hot path ---------------------------------------------------------------------- */
 /* Stage entry points with the reference's stage boundaries (for stage-level parity tests and for
@@ -182,6 +208,14 @@ int64_t diner_render_points_scratch_floats(int64_t SB, int32_t NV, int32_t preci
 int diner_render_points(const DinerScene *scene, const float *mlp_packed, const float *rays,
                         const float *z, int64_t NR, int32_t K, int32_t precision, float *scratch,
                         float *rgbsigma_out, void *stream);
+/* with the latent lookup `index` (NULL = bilinear / border).
+ * F16X3 with scene->linz_maps and DINER_INDEX_PAD_ZEROS: linz_maps MUST be the ringed maps of diner_pack_linz_maps_ix for that mode
+ * ([3][SB,NV,h+2,w+2,C], diner_linz_maps_floats); the kernel reads that many texels.  DinerScene does not record the layout: a
+ * buffer whose allocation ends before the ringed size is refused (DINER_E_INVALID), plain maps inside a larger allocation would be
+ * read as ringed ones (wrong values).  Every other mode reads the plain maps of diner_pack_linz_maps. */
+int diner_render_points_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const float *rays,
+                           const float *z, int64_t NR, int32_t K, int32_t precision, float *scratch, float *rgbsigma_out,
+                           void *stream);
 
 /* Replaces the alpha compositing of composite() (src/models/nerf_renderer.py:299-301,341-360).
  * N rays (= SB*NR).  weights_out [N,K] optional.
@@ -201,6 +235,10 @@ int diner_render(const DinerScene *scene, const float *mlp_packed, const float *
                  const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, const float *u_coarse,
                  const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace,
                  float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
+int diner_render_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const float *rays, int64_t NR,
+                    const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, const float *u_coarse,
+                    const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace,
+                    float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
 
 /* Replaces the render half of DINER.predict_imgs_from_batch (src/models/diner.py:75-97): gen_rays
  * (src/util/cam_geometry.py:36-79) is evaluated INSIDE the sampler kernel -- a wave computes its ray from the pixel index and
@@ -212,6 +250,9 @@ int diner_render_image(const DinerScene *scene, const float *mlp_packed, const D
                        const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, uint64_t seed,
                        float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
                        uint32_t *status, void *stream);
+int diner_render_image_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *mlp_packed, const DinerTargetCam *cam,
+                          const DinerSamplerCfg *cfg, int32_t white_bkgd, int32_t precision, uint64_t seed, float *workspace,
+                          float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
 
 /* ---- shape-general inference path ----------------------------------------------------------------------------------------
  * The entry points above serve the one model the configs ship (DINER_D_* above).  The reference renders any ResnetFC /
@@ -257,6 +298,17 @@ int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const 
 int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const DinerTargetCam *cam,
                            const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out,
                            float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
+/* the same with a latent lookup mode (NULL = bilinear / border) */
+int diner_render_points_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
+                               const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out,
+                               void *stream);
+int diner_render_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                        const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                        const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                        float *weights_out, uint32_t *status, void *stream);
+int diner_render_image_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
+                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
 
 /* ---- training path: building blocks of the forward-with-saved-activations and
  * the backward of composite (src/models/nerf_renderer.py:286-365) + PixelNeRF.forward
@@ -315,6 +367,12 @@ int diner_train_colsum(const float *dY, int64_t M, int32_t N, int64_t ld, float 
 int diner_train_point_inputs(const DinerScene *scene, const float *latent, int32_t latent_is_nhwc, const float *rays,
                              const float *z, int64_t NR, int32_t K, int32_t sb, float *in56, float *zlat, float *taps,
                              void *stream);
+/* the same with a latent lookup mode (NULL = bilinear / border): taps then hold that mode's footprint (nearest: one texel, weight 1;
+ * zeros: weight 0 outside the map), which is also where grid_sample's input gradient goes -- diner_train_bilinear_scatter serves
+ * every mode unchanged */
+int diner_train_point_inputs_ix(const DinerScene *scene, const DinerLatentIndex *index, const float *latent, int32_t latent_is_nhwc,
+                                const float *rays, const float *z, int64_t NR, int32_t K, int32_t sb, float *in56, float *zlat,
+                                float *taps, void *stream);
 /* dlatent_nhwc[sb][v][texel][ch] += dz[row][ch] * weight (float atomics on 256-byte contiguous rows; the
  * caller zeroes the [SB,NV,h,w,C] buffer), then diner_train_nhwc_to_nchw gives encoder.latent's layout */
 int diner_train_bilinear_scatter(const float *dz, const float *taps, int64_t P, int32_t C, int32_t h, int32_t w,

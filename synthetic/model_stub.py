@@ -72,10 +72,12 @@ class PixelNeRFState(nn.Module):
         raise RuntimeError("model stub: points are evaluated by diner_amd.NeRFRendererDGS")
 
 
-def model_from_scene(scene, weights, device="cuda", latent: torch.Tensor | None = None, num_freqs=6, **mlp_dims) -> PixelNeRFState:
+def model_from_scene(scene, weights, device="cuda", latent: torch.Tensor | None = None, num_freqs=6, index_interp="bilinear",
+                     index_padding="border", **mlp_dims) -> PixelNeRFState:
     """Build the stand-in from a ``synthetic.synth.Scene`` and a ``make_mlp_weights`` dict.
     ``latent`` may be passed as a device tensor [SB,NV,C,h,w] for scenes generated on the GPU.
-    ``num_freqs`` / ``mlp_dims`` (d_latent, d_hidden, n_blocks, combine_layer, beta) describe a non-default model."""
+    ``num_freqs`` / ``mlp_dims`` (d_latent, d_hidden, n_blocks, combine_layer, beta) describe a non-default model;
+    ``index_interp`` / ``index_padding`` the encoder's latent lookup (image_encoder.py:24-25)."""
     m = PixelNeRFState(feature_padding=scene.feature_padding, num_freqs=num_freqs, **mlp_dims)
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.items()}
     m.mlp_fine.load_state_dict(sd, strict=True)
@@ -88,4 +90,5 @@ def model_from_scene(scene, weights, device="cuda", latent: torch.Tensor | None 
     e.depths, e.depths_std, e.normals = t(scene.depths), t(scene.depths_std), t(scene.normals)
     e.latent = latent if latent is not None else (t(scene.latent) if scene.latent is not None else None)
     e.nviews, e.nobjects = scene.NV, scene.poses.shape[0]
+    e.index_interp, e.index_padding = index_interp, index_padding
     return m.eval()
