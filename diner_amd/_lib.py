@@ -136,6 +136,11 @@ SYMBOLS = {
                                             C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "diner_train_point_inputs_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _I32, _P, _P, _I64, _I32, _I32, _P,
                                               _P, _P, _P]),
+    # camera / ray / depth-map gradients of the training path
+    "diner_composite_backward_far": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "diner_train_camera_workspace_floats": (_I64, [_I64, _I32, _I32]),
+    "diner_train_point_inputs_backward": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32, _P,
+                                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

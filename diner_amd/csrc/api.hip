@@ -92,6 +92,12 @@ int launch_train_nhwc_to_nchw(const float *, int64_t, int, int, int, float *, hi
 int launch_train_head(const float *, const float *, const float *, int64_t, float *, int, hipStream_t);
 int launch_train_composite_bwd(const float *, const float *, const float *, const float *, const float *, const float *, int64_t, int,
                                int, float *, hipStream_t);
+int launch_train_composite_bwd_far(const float *, const float *, const float *, const float *, const float *, const float *, int64_t, int,
+                                   int, float *, float *, hipStream_t);
+int64_t train_camera_workspace_floats(int64_t, int, int);
+int launch_train_point_inputs_bwd(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, int,
+                                  const float *, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
+                                  hipStream_t);
 int launch_gen_rays(const float *, const float *, const float *, const float *, int, int, int, float *, hipStream_t);
 int launch_depth2normal(const float *, const float *, int, int, int, float *, hipStream_t);
 int launch_pack_maps_from_depth(const float *, const float *, const float *, int, int, int, float *, hipStream_t);
@@ -463,6 +469,43 @@ int diner_composite_backward(const float *rays, const float *z, const float *rgb
     if (N < 0 || K < 1) return bad("composite_backward: bad N / K");
     if (N > 0 && (!rays || !z || !rgbsigma || !d_rgb || !d_rgbsigma)) return bad("composite_backward: NULL pointer");
     return launch_train_composite_bwd(rays, z, rgbsigma, d_rgb, d_depth, d_weights, N, K, white_bkgd, d_rgbsigma, (hipStream_t)stream);
+}
+
+int diner_composite_backward_far(const float *rays, const float *z, const float *rgbsigma, const float *d_rgb, const float *d_depth,
+                                 const float *d_weights, int64_t N, int32_t K, int32_t white_bkgd, float *d_rgbsigma, float *d_far,
+                                 void *stream)
+{
+    if (N < 0 || K < 1) return bad("composite_backward_far: bad N / K");
+    if (N > 0 && (!rays || !z || !rgbsigma || !d_rgb || !d_rgbsigma || !d_far)) return bad("composite_backward_far: NULL pointer");
+    return launch_train_composite_bwd_far(rays, z, rgbsigma, d_rgb, d_depth, d_weights, N, K, white_bkgd, d_rgbsigma, d_far,
+                                          (hipStream_t)stream);
+}
+
+int64_t diner_train_camera_workspace_floats(int64_t NR, int32_t K, int32_t NV)
+{
+    if (NR < 0 || K < 1 || NV < 1) return -1;
+    return train_camera_workspace_floats(NR, K, NV);
+}
+
+int diner_train_point_inputs_backward(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const float *rays,
+                                      const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in56, const float *d_zlat,
+                                      const float *d_far, float *workspace, float *d_rays, float *d_poses, float *d_focal, float *d_c,
+                                      float *d_image_shape, float *d_depths, void *stream)
+{
+    int rc;
+    if ((rc = check_scene(scene, false)) || (rc = check_index(index, "train_point_inputs_backward"))) return rc;
+    if (!latent_nhwc || !rays || !z || !d_in56 || !d_zlat || !workspace) return bad("train_point_inputs_backward: NULL pointer");
+    if (scene->C != DINER_D_LATENT || scene->h <= 0 || scene->w <= 0) {
+        set_error("train_point_inputs_backward: bad scene (latent C %d, h %d, w %d)", scene->C, scene->h, scene->w);
+        return DINER_E_INVALID;
+    }
+    if (sb < 0 || sb >= scene->SB) {
+        set_error("train_point_inputs_backward: sb %d outside [0, %d)", sb, scene->SB);
+        return DINER_E_INVALID;
+    }
+    if (NR < 0 || K < 1) return bad("train_point_inputs_backward: bad NR / K");
+    return launch_train_point_inputs_bwd(*scene, index ? *index : k_default_index, latent_nhwc, rays, z, NR, K, sb, d_in56, d_zlat, d_far,
+                                         workspace, d_rays, d_poses, d_focal, d_c, d_image_shape, d_depths, (hipStream_t)stream);
 }
 
 int64_t diner_render_workspace_floats(int64_t SB, int64_t NR, int32_t K, int32_t NV, int32_t precision)

@@ -2,8 +2,9 @@
 //   NeRFRendererDGS.composite   reference src/models/nerf_renderer.py:286-365
 //   PixelNeRF.forward           reference src/models/pixelnerf.py:55-145
 //   ResnetFC.forward            reference src/models/resnetfc.py:129-159
-// as used by DINER.calc_losses (src/models/diner.py:217-290): gradients w.r.t. the fusion-MLP parameters and
-// the encoder's latent maps (the sampler is @torch.no_grad in the reference, points/viewdirs carry no grad).
+// as used by DINER.calc_losses (src/models/diner.py:217-290): gradients w.r.t. the fusion-MLP parameters, the
+// encoder's latent maps and (point_inputs_bwd_kernel) the rays, source cameras and depth maps (the sampler is
+// @torch.no_grad in the reference: the samples z carry no grad).
 //
 // Unlike the fused inference kernels this path is layer by layer: every layer's input must be kept for the
 // weight gradients anyway, so activations live in HBM as row-major [rows, 512] fp32 matrices (rows = point x
@@ -1084,6 +1085,222 @@ __global__ __launch_bounds__(64) void bilinear_scatter_kernel(const float *__res
     }
 }
 
+// ---- camera / ray / depth-map gradients: the transpose of point_inputs_kernel, one wave per (view, point) row -------------------
+// Recomputes the row's forward geometry with the same helpers and chains d_in56 (the gradient of the 55 MLP inputs, lin_in's
+// input-gradient GEMM) and d_zlat (the latent's) back to the leaves of pixelnerf.py:91-121 and nerf_renderer.py:304-305:
+//   in56 = [x_cam, sin(f x_cam + phi), R d_w, depth_dist, sin(f depth_dist + phi)],  x_cam = R (o + z d) + t,
+//   uv = ((x_cam.xy / x_cam.z) f + c) / image_shape * 2 - 1,  depth_dist = depth[nearest(uv)] - x_cam.z,  zlat = grid_sample(latent, uv).
+// Writes one record of CAMG_COLS floats per row (the reductions below sum them in a fixed order) and scatters d_depth_dist into
+// d_depths [SB,NV,H,W] (float atomics, as bilinear_scatter_kernel: several rows share a texel).
+constexpr int CAMG_COLS = 24;   // d_o 3, d_d 3, d_R 9 (row-major), d_t 3, d_focal 2, d_c 2, d_image_shape 2
+constexpr int CAMG_BLOCKS = 256;   // per-view partial sums of the pose / intrinsics reduction (at most)
+
+// ATen's clip_coordinates_set_grad + reflect_coordinates_set_grad (align_corners=False): the source coordinate of one axis after the
+// padding mode, and the factor its gradient picks up on the way back (border: 0 where clipped; reflection: the sign flips)
+__device__ __forceinline__ float pad_coord_grad(float x, int size, int padding, float &g)
+{
+    g = 1.0f;
+    if (padding == DINER_INDEX_PAD_REFLECTION) {
+        float in = x + 0.5f;                  // reflect over [-0.5, size - 0.5]
+        float m = 1.0f;
+        if (in < 0.0f) { m = -1.0f; in = -in; }
+        const float span = (float)size, extra = fmodf(in, span);
+        const int flips = (int)floorf(in / span);
+        if (flips % 2 == 0) { g = m; x = extra - 0.5f; }
+        else { g = -m; x = span - extra - 0.5f; }
+    }
+    if (padding != DINER_INDEX_PAD_ZEROS) {
+        if (x <= 0.0f || x >= (float)(size - 1)) g = 0.0f;
+        x = clipf(x, (float)(size - 1));
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(64) void point_inputs_bwd_kernel(DinerScene s, const float *__restrict__ latent_nhwc,
+                                                              const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                              int64_t NR, int K, int sb, int ix_interp, int ix_padding,
+                                                              const float *__restrict__ d_in56, const float *__restrict__ d_zlat,
+                                                              float *__restrict__ rowg, float *__restrict__ d_depths)
+{
+    const int64_t P = NR * (int64_t)K, row = blockIdx.x;
+    const int v = (int)(row / P);
+    const int64_t p = row - (int64_t)v * P;
+    const int lane = threadIdx.x;
+    const float *rp = rays + ((int64_t)sb * NR + p / K) * 8;
+    const float zz = zsamp[(int64_t)sb * P + p];
+    const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
+    const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
+    const View vw = load_view(s, sb, v);
+    float px, py, pz, u, w;
+    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // pixelnerf.py:91-93,105-108
+    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
+    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
+    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
+    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;
+
+    // positional encodings: d sin(f a + phi) / d a = f cos(f a + phi) (positional_encoding.py:45-49), one input per lane
+    const float *gin = d_in56 + row * 56;
+    float t_p[4] = {0.f, 0.f, 0.f, 0.f};   // -> x_cam.x, x_cam.y, x_cam.z, depth_dist
+    if (lane < 55) {
+        const int e = lane;
+        const float g = gin[e], half_pi = 1.5707963267948966f;
+        if (e < 3) { t_p[0] = e == 0 ? g : 0.f; t_p[1] = e == 1 ? g : 0.f; t_p[2] = e == 2 ? g : 0.f; }
+        else if (e < 39) {
+            const int j = (e - 3) / 3, i = (e - 3) % 3;
+            const float f = s.freq_factor * (float)(1 << (j >> 1)), a = i == 0 ? px : i == 1 ? py : pz;
+            const float d = g * cosf(__builtin_fmaf(a, f, (j & 1) ? half_pi : 0.0f)) * f;
+            t_p[0] = i == 0 ? d : 0.f; t_p[1] = i == 1 ? d : 0.f; t_p[2] = i == 2 ? d : 0.f;
+        } else if (e == 42) t_p[3] = g;
+        else if (e > 42) {
+            const int j = e - 43;
+            const float f = s.freq_factor * (float)(1 << (j >> 1));
+            t_p[3] = g * cosf(__builtin_fmaf(delta, f, (j & 1) ? half_pi : 0.0f)) * f;
+        }
+    }
+
+    // grid_sample's gradient with respect to the grid (ATen, align_corners=False; nearest: 0): the dot products of d_zlat with the
+    // footprint's texels, weighted by the bilinear weights' derivatives
+    float gix = 0.f, giy = 0.f, mx = 0.f, my = 0.f;
+    if (ix_interp == DINER_INDEX_BILINEAR) {
+        const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+        float gx, gy;
+        const float ix = pad_coord_grad(unnorm(u * sxl, (float)s.w / 2.0f), s.w, ix_padding, gx);
+        const float iy = pad_coord_grad(unnorm(w * syl, (float)s.h / 2.0f), s.h, ix_padding, gy);
+        mx = gx * ((float)s.w / 2.0f) * sxl;   // d ix / d u
+        my = gy * ((float)s.h / 2.0f) * syl;
+        const float x0f = floorf(ix), y0f = floorf(iy);
+        const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
+        const bool xa = x0f >= 0.0f && x0f <= (float)(s.w - 1), xb = x0f + 1.0f >= 0.0f && x0f + 1.0f <= (float)(s.w - 1);
+        const bool ya = y0f >= 0.0f && y0f <= (float)(s.h - 1), yb = y0f + 1.0f >= 0.0f && y0f + 1.0f <= (float)(s.h - 1);
+        const int x0 = safe_idx(x0f, s.w), x1 = safe_idx(x0f + 1.0f, s.w), y0 = safe_idx(y0f, s.h), y1 = safe_idx(y0f + 1.0f, s.h);
+        // per-tap factors: d(weight)/d ix, d(weight)/d iy; 0 for a tap outside the map (ATen reads 0 there)
+        const float kx[4] = {(xa && ya) ? -ey : 0.f, (xb && ya) ? ey : 0.f, (xa && yb) ? -fy : 0.f, (xb && yb) ? fy : 0.f};
+        const float ky[4] = {(xa && ya) ? -ex : 0.f, (xb && ya) ? -fx : 0.f, (xa && yb) ? ex : 0.f, (xb && yb) ? fx : 0.f};
+        const bool in[4] = {xa && ya, xb && ya, xa && yb, xb && yb};
+        const int o[4] = {y0 * s.w + x0, y0 * s.w + x1, y1 * s.w + x0, y1 * s.w + x1};
+        const float *lat = latent_nhwc + ((int64_t)sb * s.NV + v) * (int64_t)s.h * s.w * s.C;
+        const float *dz = d_zlat + row * s.C;
+        for (int ch = lane * 4; ch < s.C; ch += 256) {
+            const float4 g = *(const float4 *)(dz + ch);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (!in[i]) continue;   // (wave-uniform)
+                const float4 t = *(const float4 *)(lat + (int64_t)o[i] * s.C + ch);
+                const float d = g.x * t.x + g.y * t.y + g.z * t.z + g.w * t.w;
+                gix += kx[i] * d; giy += ky[i] * d;
+            }
+        }
+    }
+    const float S0 = wave_sum(t_p[0]), S1 = wave_sum(t_p[1]), S2 = wave_sum(t_p[2]), Sd = wave_sum(t_p[3]);
+    gix = wave_sum(gix); giy = wave_sum(giy);
+    if (lane != 0) return;
+
+    if (d_depths) atomicAdd(d_depths + (((int64_t)sb * s.NV + v) * s.H + ddy) * s.W + ddx, Sd);   // the nearest depth texel
+    float gpx = S0, gpy = S1, gpz = S2 - Sd;                 // depth_dist = depth - x_cam.z
+    // uv = ((x_cam.xy / x_cam.z) f + c) / image_shape * 2 - 1
+    const float qu = px / pz, qw = py / pz;
+    const float Uu = qu * vw.fx + vw.cx, Uw = qw * vw.fy + vw.cy;
+    const float gu = gix * mx, gw = giy * my;
+    const float gUu = gu * 2.0f / s.image_w, gUw = gw * 2.0f / s.image_h;
+    const float g_iw = -gu * 2.0f * Uu / (s.image_w * s.image_w), g_ih = -gw * 2.0f * Uw / (s.image_h * s.image_h);
+    const float gqu = gUu * vw.fx, gqw = gUw * vw.fy;
+    gpx += gqu / pz; gpy += gqw / pz; gpz -= (gqu * qu + gqw * qw) / pz;
+    // x_cam = R x_w + t, dir_cam = R d_w (pixelnerf.py:92-101), x_w = o + z d (nerf_renderer.py:304-305)
+    const float gp[3] = {gpx, gpy, gpz}, gd[3] = {gin[39], gin[40], gin[41]}, xw[3] = {wx, wy, wz}, dw[3] = {dwx, dwy, dwz};
+    float *out = rowg + row * CAMG_COLS;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float gx = vw.r[j] * gp[0] + vw.r[3 + j] * gp[1] + vw.r[6 + j] * gp[2];
+        const float gdd = vw.r[j] * gd[0] + vw.r[3 + j] * gd[1] + vw.r[6 + j] * gd[2];
+        out[j] = gx;                      // d_o
+        out[3 + j] = gdd + zz * gx;       // d_d
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[6 + i * 3 + j] = gp[i] * xw[j] + gd[i] * dw[j];
+        out[15 + i] = gp[i];
+    }
+    out[18] = gUu * qu; out[19] = gUw * qw;   // focal
+    out[20] = gUu; out[21] = gUw;             // c
+    out[22] = g_iw; out[23] = g_ih;           // image_shape
+}
+
+// d_rays[sb][ray] = (sum over views and samples of d_o, d_d;  0 (near: sampler only);  d_far or 0) -- one thread per ray, fixed order
+__global__ __launch_bounds__(256) void camg_ray_reduce_kernel(const float *__restrict__ rowg, int64_t NR, int K, int NV, int sb,
+                                                              const float *__restrict__ d_far, float *__restrict__ d_rays)
+{
+    const int64_t ray = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= NR) return;
+    const int64_t P = NR * K;
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int v = 0; v < NV; ++v)
+        for (int k = 0; k < K; ++k) {
+            const float *g = rowg + ((int64_t)v * P + ray * K + k) * CAMG_COLS;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) acc[c] += g[c];
+        }
+    float *o = d_rays + ((int64_t)sb * NR + ray) * 8;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o[c] = acc[c];
+    o[6] = 0.0f;
+    o[7] = d_far ? d_far[(int64_t)sb * NR + ray] : 0.0f;
+}
+
+// per-view partial sums of the camera columns (6..23) over a contiguous chunk of the view's P rows: grid (blocks, NV)
+__global__ __launch_bounds__(256) void camg_view_partial_kernel(const float *__restrict__ rowg, int64_t P, float *__restrict__ partial)
+{
+    constexpr int NC = CAMG_COLS - 6;
+    __shared__ float red[NC][256];
+    const int v = blockIdx.y, t = threadIdx.x;
+    const int64_t chunk = (P + gridDim.x - 1) / gridDim.x, beg = blockIdx.x * chunk, end = beg + chunk < P ? beg + chunk : P;
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+    for (int64_t p = beg + t; p < end; p += 256) {
+        const float *g = rowg + ((int64_t)v * P + p) * CAMG_COLS + 6;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[c] += g[c];
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) red[c][t] = acc[c];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) red[c][t] += red[c][t + h];
+        __syncthreads();
+    }
+    if (t < NC) partial[((int64_t)v * gridDim.x + blockIdx.x) * NC + t] = red[t][0];
+}
+
+// final sums (fixed order): poses[sb][v] rows 0..2 (d_R | d_t), focal, c; image_shape += over all views (the caller zeroes it once)
+__global__ __launch_bounds__(256) void camg_view_final_kernel(const float *__restrict__ partial, int NV, int nblk, int sb,
+                                                              float *__restrict__ d_poses, float *__restrict__ d_focal,
+                                                              float *__restrict__ d_c, float *__restrict__ d_ishape)
+{
+    constexpr int NC = CAMG_COLS - 6;
+    for (int t = threadIdx.x; t < NV * NC; t += blockDim.x) {
+    const int v = t / NC, c = t - v * NC;
+    float sum = 0.f;
+    for (int b = 0; b < nblk; ++b) sum += partial[((int64_t)v * nblk + b) * NC + c];
+    const int64_t sv = (int64_t)sb * NV + v;
+    if (c < 9) { if (d_poses) d_poses[sv * 16 + (c / 3) * 4 + c % 3] = sum; }
+    else if (c < 12) { if (d_poses) d_poses[sv * 16 + (c - 9) * 4 + 3] = sum; }
+    else if (c < 14) { if (d_focal) d_focal[sv * 2 + c - 12] = sum; }
+    else if (c < 16) { if (d_c) d_c[sv * 2 + c - 14] = sum; }
+    else if (v == 0 && d_ishape) {
+        float tot = sum;
+        for (int u = 1; u < NV; ++u) {
+            float su = 0.f;
+            for (int b = 0; b < nblk; ++b) su += partial[((int64_t)u * nblk + b) * NC + c];
+            tot += su;
+        }
+        d_ishape[c - 16] += tot;
+    }
+    }
+}
+
 // [N,h*w,C] -> [N,C,h*w] (the layout of encoder.latent and of its gradient), tiled through LDS
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float *__restrict__ in, int64_t hw, int C, float *__restrict__ out)
 {
@@ -1170,6 +1387,49 @@ __global__ void composite_bwd_kernel(const float *__restrict__ rays, const float
         const float dLdalpha = dLdw * Tk - S / keep;
         // alpha = 1 - exp(-delta * relu(sigma)) -> d alpha / d sigma = delta * e  (0 where sigma <= 0)
         dr[k * 4 + 3] = sraw > 0.0f ? dLdalpha * delta * e : 0.0f;
+        S += dLdw * w;
+    }
+}
+// The same, and d_far [N]: the gradient of rays[..., 7] through delta_inf = far - z_K (nerf_renderer.py:300-301).  A copy rather
+// than a template parameter of the kernel above: that kernel's symbol and instructions stay as they were (a shared inline body
+// measurably changed its schedule).
+__global__ void composite_bwd_far_kernel(const float *__restrict__ rays, const float *__restrict__ z, const float *__restrict__ rgbsigma,
+                                         const float *__restrict__ d_rgb, const float *__restrict__ d_depth,
+                                         const float *__restrict__ d_weights, int64_t N, int K, int white_bkgd,
+                                         float *__restrict__ d_rgbsigma, float *__restrict__ d_far)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const float far = rays[r * 8 + 7];
+    const float *zr = z + r * K, *cr = rgbsigma + r * K * 4;
+    float *dr = d_rgbsigma + r * K * 4;
+    const float gr = d_rgb[r * 3 + 0], gg = d_rgb[r * 3 + 1], gb = d_rgb[r * 3 + 2], gd = d_depth ? d_depth[r] : 0.0f;
+    // dL/dw_k = g.c_k + gd z_k - white*(gr+gg+gb) + d_weights_k
+    // w_k = alpha_k T_k;  T_{k+1} = T_k (1 - alpha_k + eps)
+    // reverse sweep with S_k = sum_{j>k} dL/dw_j w_j  (dT_j/dalpha_k = -T_j/(1-alpha_k+eps) for j > k)
+    // forward sweep: park T_k in the sigma slot of the output (overwritten by the reverse sweep); recomputing
+    // T_k backwards by division would lose it once the transmittance underflows behind an opaque sample
+    float T = 1.0f;
+    for (int k = 0; k < K; ++k) {
+        const float delta = (k + 1 < K) ? zr[k + 1] - zr[k] : far - zr[k];
+        const float sg = cr[k * 4 + 3] > 0.0f ? cr[k * 4 + 3] : 0.0f;
+        dr[k * 4 + 3] = T;
+        T = T * (1.0f - (1.0f - expf(-delta * sg)) + 1e-10f);
+    }
+    float S = 0.0f;  // sum_{j>k} dLdw_j * w_j
+    const float gwhite = white_bkgd ? (gr + gg + gb) : 0.0f;
+    for (int k = K - 1; k >= 0; --k) {
+        const float delta = (k + 1 < K) ? zr[k + 1] - zr[k] : far - zr[k];
+        const float sraw = cr[k * 4 + 3], sg = sraw > 0.0f ? sraw : 0.0f;
+        const float e = expf(-delta * sg), alpha = 1.0f - e, keep = 1.0f - alpha + 1e-10f;
+        const float Tk = dr[k * 4 + 3];
+        const float w = alpha * Tk;
+        const float dLdw = gr * cr[k * 4 + 0] + gg * cr[k * 4 + 1] + gb * cr[k * 4 + 2] + gd * zr[k] - gwhite + (d_weights ? d_weights[r * K + k] : 0.0f);
+        dr[k * 4 + 0] = gr * w; dr[k * 4 + 1] = gg * w; dr[k * 4 + 2] = gb * w;
+        const float dLdalpha = dLdw * Tk - S / keep;
+        // alpha = 1 - exp(-delta * relu(sigma)) -> d alpha / d sigma = delta * e  (0 where sigma <= 0)
+        dr[k * 4 + 3] = sraw > 0.0f ? dLdalpha * delta * e : 0.0f;
+        if (k == K - 1) d_far[r] = sraw > 0.0f ? dLdalpha * sg * e : 0.0f;   // d alpha / d delta = relu(sigma) e
         S += dLdw * w;
     }
 }
@@ -1291,6 +1551,47 @@ int launch_train_composite_bwd(const float *rays, const float *z, const float *r
     hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, rays, z, rgbsigma, d_rgb, d_depth,
                        d_weights, N, K, white_bkgd, d_rgbsigma);
     return check_launch("train::composite_bwd_kernel");
+}
+
+int launch_train_composite_bwd_far(const float *rays, const float *z, const float *rgbsigma, const float *d_rgb, const float *d_depth,
+                                   const float *d_weights, int64_t N, int K, int white_bkgd, float *d_rgbsigma, float *d_far, hipStream_t st)
+{
+    if (N == 0) return DINER_OK;
+    hipLaunchKernelGGL(composite_bwd_far_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, rays, z, rgbsigma, d_rgb, d_depth,
+                       d_weights, N, K, white_bkgd, d_rgbsigma, d_far);
+    return check_launch("train::composite_bwd_far_kernel");
+}
+
+int64_t train_camera_workspace_floats(int64_t NR, int K, int NV)
+{
+    return NR * (int64_t)K * NV * CAMG_COLS + (int64_t)NV * CAMG_BLOCKS * (CAMG_COLS - 6);
+}
+
+int launch_train_point_inputs_bwd(const DinerScene &s, const DinerLatentIndex &ix, const float *latent_nhwc, const float *rays, const float *z,
+                                  int64_t NR, int K, int sb, const float *d_in56, const float *d_zlat, const float *d_far, float *workspace,
+                                  float *d_rays, float *d_poses, float *d_focal, float *d_c, float *d_image_shape, float *d_depths,
+                                  hipStream_t st)
+{
+    const int64_t P = NR * (int64_t)K, R = P * s.NV;
+    if (R == 0) return DINER_OK;
+    float *rowg = workspace, *partial = workspace + R * CAMG_COLS;
+    hipLaunchKernelGGL(point_inputs_bwd_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp, ix.padding,
+                       d_in56, d_zlat, rowg, d_depths);
+    int rc = check_launch("train::point_inputs_bwd_kernel");
+    if (rc) return rc;
+    if (d_rays) {
+        hipLaunchKernelGGL(camg_ray_reduce_kernel, dim3((unsigned)((NR + 255) / 256)), dim3(256), 0, st, rowg, NR, K, s.NV, sb, d_far, d_rays);
+        if ((rc = check_launch("train::camg_ray_reduce_kernel"))) return rc;
+    }
+    if (d_poses || d_focal || d_c || d_image_shape) {
+        const int64_t per = (P + 255) / 256;
+        const int nblk = (int)(per < CAMG_BLOCKS ? per : CAMG_BLOCKS);
+        hipLaunchKernelGGL(camg_view_partial_kernel, dim3((unsigned)nblk, (unsigned)s.NV), dim3(256), 0, st, rowg, P, partial);
+        if ((rc = check_launch("train::camg_view_partial_kernel"))) return rc;
+        hipLaunchKernelGGL(camg_view_final_kernel, dim3(1), dim3(256), 0, st, partial, s.NV, nblk, sb, d_poses, d_focal, d_c, d_image_shape);
+        if ((rc = check_launch("train::camg_view_final_kernel"))) return rc;
+    }
+    return DINER_OK;
 }
 
 }  // namespace diner

@@ -646,8 +646,7 @@ class NeRFRendererDGS(torch.nn.Module):
         r = self._check_rays(rays)
         z = _f32c(z_samp)
         SB, NR, K = z.shape
-        if rgbsigma is None and torch.is_grad_enabled() and (any(p.requires_grad for p in model.mlp_fine.parameters())
-                                                             or model.encoder.latent.requires_grad):
+        if rgbsigma is None and self._wants_grad(model, rays):
             shape = self._validate_model(model)
             if not shape.standard:
                 self._gen_training_unsupported(shape)
@@ -665,6 +664,17 @@ class NeRFRendererDGS(torch.nn.Module):
                                          _ptr(depth), _ptr(weights), _ptr(self._status_word(dev)), _stream(dev)), "diner_composite")
         self._after_launch(dev, sync=_sync)
         return weights, rgb, depth
+
+    @staticmethod
+    def _wants_grad(model, rays) -> bool:
+        """True when autograd needs the training path: an MLP parameter, ``encoder.latent``, the rays, a camera tensor
+        (poses, focal, c, image_shape) or ``encoder.depths`` requires grad."""
+        if not torch.is_grad_enabled():
+            return False
+        if any(p.requires_grad for p in model.mlp_fine.parameters()) or model.encoder.latent.requires_grad:
+            return True
+        from .training import camera_leaves
+        return any(t is not None and t.requires_grad for t in camera_leaves(model, rays))
 
     @staticmethod
     def _require_no_grad(model):
@@ -685,7 +695,7 @@ class NeRFRendererDGS(torch.nn.Module):
         """
         assert len(rays.shape) == 3
         shape = self._validate_model(model)
-        if torch.is_grad_enabled() and (any(p.requires_grad for p in model.mlp_fine.parameters()) or model.encoder.latent.requires_grad):
+        if self._wants_grad(model, rays):
             if not shape.standard:
                 self._gen_training_unsupported(shape)
             return self._forward_train(model, rays, want_weights, noise=noise, z_samples=z_samples)
@@ -893,7 +903,8 @@ class NeRFRendererDGS(torch.nn.Module):
     def _forward_train(self, model, rays, want_weights, noise=None, z_samples=None):
         """Training path (reference DINER.calc_losses, src/models/diner.py:217-290): sampler under no_grad
         (src/models/nerf_renderer.py:65), then the differentiable point evaluation + compositing of
-        diner_amd/training.py (HIP building blocks; gradients to the MLP parameters and encoder.latent)."""
+        diner_amd/training.py (HIP building blocks; gradients to the MLP parameters, encoder.latent, the rays, the source
+        cameras and encoder.depths)."""
         from . import training
         r = self._check_rays(rays)
         SB, NR, _ = r.shape
@@ -908,7 +919,7 @@ class NeRFRendererDGS(torch.nn.Module):
         lat = model.encoder.latent
         assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == 512
         sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
-        rgb, depth, weights = training.render_with_grad(self, model, r, z, sc)
+        rgb, depth, weights = training.render_with_grad(self, model, rays, z, sc, keep=_keep)
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     # alias asked for by the north_star text; the reference itself has no render_rays

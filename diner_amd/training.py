@@ -5,8 +5,8 @@ The reference trains through ``NeRFRendererDGS.composite`` and ``PixelNeRF.forwa
 src/models/nerf_renderer.py:65).  Here the same graph is evaluated by the HIP building blocks of
 ``diner_amd/csrc/train.hip`` (MFMA GEMM kernels in the renderer's precision + small per-point kernels, all through
 the C ABI); this module only orchestrates them the way autograd orchestrates ATen ops: a forward that keeps every
-layer's input, and a hand-written backward producing gradients for the fusion-MLP parameters and
-``encoder.latent``.  PyTorch supplies buffers and the autograd hook -- no arithmetic of the path.
+layer's input, and a hand-written backward producing gradients for the fusion-MLP parameters, ``encoder.latent`` and
+(when they require grad) the rays, the source cameras and ``encoder.depths``.  PyTorch supplies buffers and the autograd hook -- no arithmetic of the path.
 """
 from __future__ import annotations
 
@@ -182,12 +182,20 @@ def _mlp_params(mlp):
     return ps
 
 
+CAMERA_INPUTS = ("rays", "poses", "focal", "c", "image_shape", "depths")
+
+
 class _RenderFn(torch.autograd.Function):
-    """(latent, *mlp_params) -> (rgb, depth, weights) for fixed rays / samples."""
+    """(rays, latent, poses, focal, c, image_shape, depths, *mlp_params) -> (rgb, depth, weights) for fixed samples.
+
+    ``cams`` = the caller's (rays, poses, focal, c, image_shape, depths) leaves, whose versions backward() checks; the tensors
+    passed in their place are their fp32 contiguous copies (graph-preserving casts).  The scene's camera and map pointers are
+    the renderer's packs of the same values (``keep`` holds them alive until backward)."""
 
     @staticmethod
-    def forward(ctx, renderer, scene, ix, rays, z, latent, *params):
+    def forward(ctx, renderer, scene, ix, keep, cams, z, rays, latent, poses, focal, c_, image_shape, depths, *params):
         L = _lib.lib()
+        rays = rays.detach()
         dev = rays.device
         st = _st(dev)
         SB, NR, K = z.shape
@@ -203,6 +211,8 @@ class _RenderFn(torch.autograd.Function):
         # ctx.save_for_backward would, so that an in-place update between forward and backward is an error instead of a
         # silently wrong dX (optimizer.step / EMA copy_ under gradient accumulation)
         ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
+        # the geometric leaves: held (as the reference's graph holds them), so that a caller's temporary rays stay checkable
+        ctx.cam_versions = [(t, t._version) for t in cams]
         w_in56 = torch.zeros((HID, 56), dtype=torch.float32, device=dev)
         w_in56[:, :55] = prm[0]
         rgbsigma = f(SB, NR, K, 4)
@@ -252,19 +262,24 @@ class _RenderFn(torch.autograd.Function):
               "diner_composite")
         ctx.renderer, ctx.scene, ctx.rays, ctx.z, ctx.rgbsigma = renderer, scene, rays, z, rgbsigma
         ctx.saved_acts, ctx.prm, ctx.w_in56, ctx.lat_shape = saved, prm, w_in56, tuple(latent.shape)
-        ctx.keep = (lat,)
+        ctx.keep = (lat, lat_nhwc, keep)
         ctx.prec = prec
         ctx.params = params
+        ctx.cam_shapes = [tuple(t.shape) for t in (poses, focal, c_, image_shape, depths)]
+        ctx.ix = ix
         return rgb, depth, weights
 
     @staticmethod
     def backward(ctx, d_rgb, d_depth, d_weights):
         L = _lib.lib()
-        for ref, ver in ctx.versions:
-            t = ref()
+        for t, ver in [(ref(), ver) for ref, ver in ctx.versions] + ctx.cam_versions:
             if t is None or t._version != ver:
-                raise RuntimeError("diner_amd.training: one of the variables needed for gradient computation (an MLP parameter or "
-                                   "encoder.latent) has been modified by an inplace operation between forward and backward")
+                raise RuntimeError("diner_amd.training: one of the variables needed for gradient computation (an MLP parameter, "
+                                   "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
+                                   "between forward and backward")
+        # which geometric leaves want a gradient (inputs 6 and 8..12: rays, poses, focal, c, image_shape, depths)
+        want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[6],) + tuple(ctx.needs_input_grad[8:13])))
+        cam_any = any(want.values())
         scene, rays, z, rgbsigma, prm = ctx.scene, ctx.rays, ctx.z, ctx.rgbsigma, ctx.prm
         dev = rays.device
         st = _st(dev)
@@ -278,8 +293,26 @@ class _RenderFn(torch.autograd.Function):
         if d_rgb is None:
             d_rgb = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev)
         d_rgbsigma = f(SB, NR, K, 4)
-        check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K,
-                                         int(bool(ctx.renderer.white_bkgd)), _p(d_rgbsigma), st), "diner_composite_backward")
+        d_far = None
+        if want["rays"]:   # the same, and far's gradient (delta_inf = far - z_K)
+            d_far = f(SB, NR)
+            check(L.diner_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K,
+                                                 int(bool(ctx.renderer.white_bkgd)), _p(d_rgbsigma), _p(d_far), st), "diner_composite_backward_far")
+        else:
+            check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K,
+                                             int(bool(ctx.renderer.white_bkgd)), _p(d_rgbsigma), st), "diner_composite_backward")
+        if cam_any:
+            sh_poses, sh_focal, sh_c, sh_ishape, sh_depths = ctx.cam_shapes
+            z0 = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+            g_rays = f(SB, NR, 8) if want["rays"] else None
+            g_poses = z0((SB, NV, 4, 4)) if want["poses"] else None
+            g_focal = f(SB, NV, 2) if want["focal"] else None
+            g_c = f(SB, NV, 2) if want["c"] else None
+            g_ishape = z0(2) if want["image_shape"] else None
+            g_depths = z0((SB, NV, scene.H, scene.W)) if want["depths"] else None
+            ws = f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
+            lat_nhwc = ctx.keep[1]
+            ix = ctx.ix if ctx.ix is not None else _lib.DinerLatentIndex(0, 0)
         g = [torch.zeros_like(p) for p in prm]          # parameter gradients (fp32, accumulated atomically)
         g_in56 = torch.zeros_like(ctx.w_in56)
         SBl, NVl, Cl, hl, wl = ctx.lat_shape
@@ -324,17 +357,39 @@ class _RenderFn(torch.autograd.Function):
                 linear_bwd_x(d_xs, prm[2 + 2 * b], None, d_zl, addend=None if b == 2 else d_zl, prec=prec, amax=a_xs, panel=wt[2 + 2 * b])
                 d_xv, a_xv = d_xs, a_xs
             linear_bwd_w(d_xv, in56, g_in56, None, prec=prec, amax=a_xs)           # lin_in (its d_xv is lin_z[0]'s d_xs)
+            if cam_any:   # lin_in's input gradient, then the transpose of the point inputs to the geometric leaves
+                d_in56 = f(R, 56)
+                linear_bwd_x(d_xv, ctx.w_in56, None, d_in56, prec=prec, amax=a_xs)
+                check(L.diner_train_point_inputs_backward(C.byref(scene), C.byref(ix), _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in56),
+                                                          _p(d_zl), _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c),
+                                                          _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward")
             check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, HID, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                   "diner_train_bilinear_scatter")
         d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
         check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
         g[0] = g_in56[:, :55].contiguous()
         g[1] = g[3].clone()  # lin_in's bias sees the same dY as lin_z[0]'s: x = lin_in(..) + lin_z[0](z)
-        return (None, None, None, None, None, d_lat) + tuple(g)
+        cam = (None,) * 6
+        if cam_any:
+            cam = (g_rays,
+                   None if g_poses is None else g_poses[..., :sh_poses[-2], :].reshape(sh_poses),   # ([.., 3, 4] poses: rows 0..2)
+                   None if g_focal is None else g_focal.reshape(sh_focal),
+                   None if g_c is None else g_c.reshape(sh_c),
+                   None if g_ishape is None else g_ishape.reshape(sh_ishape),
+                   None if g_depths is None else g_depths.reshape(sh_depths))
+        return (None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
 
 
-def render_with_grad(renderer, model, rays, z, scene):
-    """rgb, depth, weights = composite(model, rays, z) with gradients to the MLP parameters and encoder.latent."""
+def camera_leaves(model, rays):
+    """The geometric tensors autograd can differentiate the render with respect to (CAMERA_INPUTS order)."""
+    return (rays, model.poses, model.focal, model.c, model.image_shape, model.encoder.depths)
+
+
+def render_with_grad(renderer, model, rays, z, scene, keep=None):
+    """rgb, depth, weights = composite(model, rays, z) with gradients to the MLP parameters, encoder.latent, and the rays, cameras
+    (poses, focal, c, image_shape) and depth maps (encoder.depths) when they require grad."""
     params = _mlp_params(model.mlp_fine)
     ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
-    return _RenderFn.apply(renderer, scene, ix, rays, z, model.encoder.latent, *params)
+    cams = camera_leaves(model, rays)
+    f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
+    return _RenderFn.apply(renderer, scene, ix, keep, cams, z, *f32[:1], model.encoder.latent, *f32[1:], *params)

@@ -388,6 +388,30 @@ int diner_train_head(const float *out, const float *rgbsigma, const float *d_rgb
 int diner_composite_backward(const float *rays, const float *z, const float *rgbsigma, const float *d_rgb,
                              const float *d_depth, const float *d_weights, int64_t N, int32_t K,
                              int32_t white_bkgd, float *d_rgbsigma, void *stream);
+/* diner_composite_backward, and d_far [N]: the gradient of rays[..., 7] through delta_inf = far - z_K (nerf_renderer.py:300-301, the
+ * transpose of alpha_K = 1 - exp(-delta_inf relu(sigma_K)), :344).  d_far must not be NULL. */
+int diner_composite_backward_far(const float *rays, const float *z, const float *rgbsigma, const float *d_rgb,
+                                 const float *d_depth, const float *d_weights, int64_t N, int32_t K, int32_t white_bkgd,
+                                 float *d_rgbsigma, float *d_far, void *stream);
+/* floats of the workspace diner_train_point_inputs_backward needs (-1 for bad arguments) */
+int64_t diner_train_camera_workspace_floats(int64_t NR, int32_t K, int32_t NV);
+/* Backward of diner_train_point_inputs(_ix) (index NULL = bilinear / border) to the geometric leaves, for scene sb: the transpose of
+ * nerf_renderer.py:304-305 (points = o + z d, viewdirs = d), pixelnerf.py:92-101 (x_cam = R x + t, R d), :105-108 (uv),
+ * image_encoder.py:97-127 (grid_sample's gradient with respect to the grid: ATen's, align_corners=False, every DINER_INDEX_* mode;
+ * nearest: 0), image_encoder.py:129-151 + pixelnerf.py:116-117 (depth_dist = depth[nearest(uv)] - x_cam.z: to the depth texel only) and
+ * the positional encodings (positional_encoding.py:45-49).
+ *   d_in56 [R,56]: gradient of the MLP inputs (lin_in's input gradient);  d_zlat [R,512]: gradient of the latent lookup;
+ *   d_far [SB*NR] | NULL: diner_composite_backward_far's, copied to d_rays[..., 7] (0 when NULL);  latent_nhwc: diner_pack_latent's copy.
+ * Outputs, each NULL when not wanted:
+ *   d_rays [SB,NR,8]: rows of sb written (origin, direction summed over the K samples and NV views; near: 0; far: d_far);
+ *   d_poses [SB,NV,4,4]: rows 0..2 of sb's views written (row 3 untouched: the caller zeroes it);  d_focal, d_c [SB,NV,2]: sb's written;
+ *   d_image_shape [2]: += (summed over every view; the caller zeroes it before sb 0);
+ *   d_depths [SB,NV,H,W]: += at each row's nearest depth texel (float atomics; the caller zeroes it).
+ * The reductions run in a fixed order; workspace: diner_train_camera_workspace_floats(NR, K, NV) floats. */
+int diner_train_point_inputs_backward(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc,
+                                      const float *rays, const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in56,
+                                      const float *d_zlat, const float *d_far, float *workspace, float *d_rays, float *d_poses,
+                                      float *d_focal, float *d_c, float *d_image_shape, float *d_depths, void *stream);
 
 #ifdef __cplusplus
 }
