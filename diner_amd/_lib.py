@@ -20,6 +20,8 @@ N_BLOCKS, COMBINE = 5, 3
 # the ABI version THIS binding (the argument lists in SYMBOLS below) is written against = DINER_ABI_VERSION of include/diner_hip.h
 ABI_VERSION = 3
 PRECISIONS = {"fp32": 0, "f16x3": 1}
+# DINER_ACT_* of include/diner_hip.h (diner_train_gemm_act)
+ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
 
 
 class DinerScene(C.Structure):
@@ -141,6 +143,13 @@ SYMBOLS = {
     "diner_train_camera_workspace_floats": (_I64, [_I64, _I32, _I32]),
     "diner_train_point_inputs_backward": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32, _P,
                                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the shape-general training path (DINER_ACT_*; the ABI version stays 3: new entry points only)
+    "diner_train_gemm_act": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, C.c_float,
+                                       _I32, _I32, _I64, _P]),
+    "diner_train_point_inputs_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32, _P, _I64,
+                                               _P, _P, _P]),
+    "diner_train_point_inputs_backward_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32,
+                                                        _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

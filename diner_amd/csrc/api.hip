@@ -121,6 +121,14 @@ int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipS
 int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
 }
 
+int launch_train_gemm_act(const float *, const float *, const float *, const float *, float *, int64_t, int, int, int64_t, int64_t, int64_t,
+                          int64_t, int64_t, int64_t, int, int, int, float, int, int, int64_t, hipStream_t);
+int launch_train_point_inputs_gen(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, int,
+                                  float *, int64_t, float *, float *, hipStream_t);
+int launch_train_point_inputs_bwd_gen(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int,
+                                      int, const float *, int64_t, const float *, const float *, float *, float *, float *, float *, float *,
+                                      float *, float *, hipStream_t);
+
 static int bad(const char *msg)
 {
     set_error("%s", msg);
@@ -506,6 +514,86 @@ int diner_train_point_inputs_backward(const DinerScene *scene, const DinerLatent
     if (NR < 0 || K < 1) return bad("train_point_inputs_backward: bad NR / K");
     return launch_train_point_inputs_bwd(*scene, index ? *index : k_default_index, latent_nhwc, rays, z, NR, K, sb, d_in56, d_zlat, d_far,
                                          workspace, d_rays, d_poses, d_focal, d_c, d_image_shape, d_depths, (hipStream_t)stream);
+}
+
+/* ---- shape-general training path (train_gen.hip) ---------------------------------------------------------------------------- */
+static bool act_known(int32_t a) { return a == DINER_ACT_NONE || a == DINER_ACT_RELU || a == DINER_ACT_SOFTPLUS; }
+
+int diner_train_gemm_act(const float *A, const float *B, const float *bias, const float *S, float *C, int64_t M, int32_t N, int32_t K,
+                         int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int64_t ldc, int64_t lds, int32_t act_a, int32_t act_b,
+                         int32_t act_s, float beta, int32_t accumulate, int32_t atomic, int64_t k_chunk, void *stream)
+{
+    if (!A || !B || !C) return bad("train_gemm_act: NULL pointer");
+    if (!act_known(act_a) || !act_known(act_b) || !act_known(act_s)) {
+        set_error("train_gemm_act: unknown activation code (act_a %d, act_b %d, act_s %d; DINER_ACT_NONE 0, _RELU 1, _SOFTPLUS 2)", act_a,
+                  act_b, act_s);
+        return DINER_E_INVALID;
+    }
+    if ((act_a == DINER_ACT_SOFTPLUS || act_b == DINER_ACT_SOFTPLUS || act_s == DINER_ACT_SOFTPLUS) && !(beta > 0.0f && beta < __builtin_inff()))
+        return bad("train_gemm_act: Softplus needs a finite beta > 0");
+    if (M < 0 || N <= 0 || K <= 0 || (N & 3) || k_chunk < 0 || (k_chunk & 31)) return bad("train_gemm_act: bad size (N % 4, k_chunk % 32 must be 0)");
+    if (sak != 1 && sam != 1) return bad("train_gemm_act: A must be contiguous along m or k");
+    if (sbn != 1 && sbk != 1) return bad("train_gemm_act: B must be contiguous along k or n");
+    if ((sak == 1 ? (K & 3) || (sam & 3) : (M & 3) || (sak & 3)) || (sbn == 1 ? (sbk & 3) : (K & 3) || (sbn & 3)))
+        return bad("train_gemm_act: the contiguous extent and the other stride of each operand must be multiples of 4");
+    return launch_train_gemm_act(A, B, bias, S, C, M, N, K, sam, sak, sbk, sbn, ldc, lds, act_a, act_b, act_s, beta, accumulate, atomic, k_chunk,
+                                 (hipStream_t)stream);
+}
+
+// scene, lookup mode, F, C and ld_in of the two point-input entry points
+static int check_train_gen_inputs(const DinerScene *scene, const DinerLatentIndex *index, int64_t NR, int32_t K, int32_t sb, int64_t ld_in,
+                                  const char *who)
+{
+    int rc;
+    if ((rc = check_scene(scene, false)) || (rc = check_index(index, who))) return rc;
+    if (scene->num_freqs < 1 || scene->num_freqs > 63) {
+        set_error("%s: num_freqs %d outside 1..63", who, scene->num_freqs);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (scene->C < 8 || scene->C > 1024 || scene->C % 8) {
+        set_error("%s: latent width C %d unsupported (a multiple of 8 in [8, 1024])", who, scene->C);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (ld_in < 7 + 8 * (int64_t)scene->num_freqs || (ld_in & 3)) {
+        set_error("%s: ld_in %lld must be >= 7 + 8 * num_freqs = %d and a multiple of 4", who, (long long)ld_in, 7 + 8 * scene->num_freqs);
+        return DINER_E_INVALID;
+    }
+    if (scene->h <= 0 || scene->w <= 0) {
+        set_error("%s: bad latent size (h %d, w %d)", who, scene->h, scene->w);
+        return DINER_E_INVALID;
+    }
+    if (sb < 0 || sb >= scene->SB) {
+        set_error("%s: sb %d outside [0, %d)", who, sb, scene->SB);
+        return DINER_E_INVALID;
+    }
+    if (NR < 0 || K < 1) {
+        set_error("%s: bad NR / K", who);
+        return DINER_E_INVALID;
+    }
+    return DINER_OK;
+}
+
+int diner_train_point_inputs_gen(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const float *rays,
+                                 const float *z, int64_t NR, int32_t K, int32_t sb, float *in_out, int64_t ld_in, float *zlat, float *taps,
+                                 void *stream)
+{
+    int rc;
+    if ((rc = check_train_gen_inputs(scene, index, NR, K, sb, ld_in, "train_point_inputs_gen"))) return rc;
+    if (!latent_nhwc || !rays || !z || !in_out || !zlat || !taps) return bad("train_point_inputs_gen: NULL pointer");
+    return launch_train_point_inputs_gen(*scene, index ? *index : k_default_index, latent_nhwc, rays, z, NR, K, sb, in_out, ld_in, zlat, taps,
+                                         (hipStream_t)stream);
+}
+
+int diner_train_point_inputs_backward_gen(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const float *rays,
+                                          const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in, int64_t ld_in,
+                                          const float *d_zlat, const float *d_far, float *workspace, float *d_rays, float *d_poses,
+                                          float *d_focal, float *d_c, float *d_image_shape, float *d_depths, void *stream)
+{
+    int rc;
+    if ((rc = check_train_gen_inputs(scene, index, NR, K, sb, ld_in, "train_point_inputs_backward_gen"))) return rc;
+    if (!latent_nhwc || !rays || !z || !d_in || !d_zlat || !workspace) return bad("train_point_inputs_backward_gen: NULL pointer");
+    return launch_train_point_inputs_bwd_gen(*scene, index ? *index : k_default_index, latent_nhwc, rays, z, NR, K, sb, d_in, ld_in, d_zlat,
+                                             d_far, workspace, d_rays, d_poses, d_focal, d_c, d_image_shape, d_depths, (hipStream_t)stream);
 }
 
 int64_t diner_render_workspace_floats(int64_t SB, int64_t NR, int32_t K, int32_t NV, int32_t precision)

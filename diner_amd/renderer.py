@@ -198,7 +198,7 @@ class NeRFRendererDGS(torch.nn.Module):
     """
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000,
-                 white_bkgd=True):
+                 white_bkgd=True, train_any_shape=False):
         super().__init__()
         self.n_samples = n_samples
         self.n_depth_candidates = n_depth_candidates
@@ -241,6 +241,11 @@ class NeRFRendererDGS(torch.nn.Module):
         self.last_route = self.last_binding = self.effective_precision = None
         self._warned_precision = False
         self._force_gen = False      # test-only: run the standard shape on the shape-general kernel as well
+        # Training (autograd through forward() / composite()) of a model of any shape of the shape-general envelope: the exact fp32
+        # path of diner_amd/training_gen.py (last_route "train_gen").  Opt-in: when False a non-standard model under autograd raises,
+        # as before.  A plain attribute, so that a config can set it (renderer.kwargs.train_any_shape).
+        self.train_any_shape = bool(train_any_shape)
+        self._force_gen_train = False   # test-only: train the standard shape on that path as well
         self._latent_gen = self._mlp_gen = 0         # bumped by every re-pack; the lin_z maps depend on both
         # Non-finite guard.  The compositing kernel ORs DINER_STATUS_NONFINITE into a device word when an rgb-sigma
         # sample is inf/NaN (in f16x3 mode: an MLP activation beyond the fp16 range, |x| >= ~1e6).  The word is copied
@@ -330,23 +335,31 @@ class NeRFRendererDGS(torch.nn.Module):
         """validate ``model``; for a shape that takes the shape-general kernel, settle the precision (fp32 is what runs)"""
         shape = self._validate_model(model)
         if self._use_gen(shape):
-            if self.precision != "fp32" and not self._warned_precision:
-                warnings.warn(f"diner_amd.NeRFRendererDGS: precision={self.precision!r} is available for the standard model only; "
-                              f"the fusion MLP {tuple(shape)} runs in exact fp32 (renderer.effective_precision)", stacklevel=3)
-                self._warned_precision = True
-            self.effective_precision = "fp32"
+            self._settle_fp32(shape, stacklevel=4)
         else:
             self.effective_precision = self.precision
         return shape
 
+    def _settle_fp32(self, shape: MlpShape, stacklevel=3):
+        """the shape-general paths run in exact fp32: say so once when another precision was asked for"""
+        if self.precision != "fp32" and not self._warned_precision:
+            warnings.warn(f"diner_amd.NeRFRendererDGS: precision={self.precision!r} is available for the standard model only; "
+                          f"the fusion MLP {tuple(shape)} runs in exact fp32 (renderer.effective_precision)", stacklevel=stacklevel)
+            self._warned_precision = True
+        self.effective_precision = "fp32"
+
     def _use_gen(self, shape: MlpShape) -> bool:
         return self._force_gen or not shape.standard
 
+    def _use_gen_train(self, shape: MlpShape) -> bool:
+        return self._force_gen_train or (self.train_any_shape and not shape.standard)
+
     @staticmethod
     def _gen_training_unsupported(shape: MlpShape):
-        raise NotImplementedError(f"training (autograd through the renderer) supports the standard fusion MLP {tuple(STANDARD_SHAPE)[:6]} only; "
-                                  f"the shape {tuple(shape)} is supported for inference: call it under torch.no_grad() or with "
-                                  "parameters that do not require grad")
+        raise NotImplementedError(f"training (autograd through the renderer) supports the standard fusion MLP {tuple(STANDARD_SHAPE)[:6]} only "
+                                  f"unless train_any_shape is set; the shape {tuple(shape)} is supported for inference: call it under "
+                                  "torch.no_grad() or with parameters that do not require grad, or construct the renderer with "
+                                  "train_any_shape=True (renderer.train_any_shape: the shape-general fp32 training path)")
 
     def _scene(self, model, need_latent=True, packed_mlp=None) -> Tuple[DinerScene, tuple]:
         enc = model.encoder
@@ -648,6 +661,9 @@ class NeRFRendererDGS(torch.nn.Module):
         SB, NR, K = z.shape
         if rgbsigma is None and self._wants_grad(model, rays):
             shape = self._validate_model(model)
+            if self._use_gen_train(shape):
+                out = self._forward_train_gen(model, rays, True, shape, z_samples=z).fine
+                return out.weights, out.rgb, out.depth
             if not shape.standard:
                 self._gen_training_unsupported(shape)
             out = self._forward_train(model, rays, True, z_samples=z).fine   # differentiable like the reference's composite
@@ -696,6 +712,8 @@ class NeRFRendererDGS(torch.nn.Module):
         assert len(rays.shape) == 3
         shape = self._validate_model(model)
         if self._wants_grad(model, rays):
+            if self._use_gen_train(shape):
+                return self._forward_train_gen(model, rays, want_weights, shape, noise=noise, z_samples=z_samples)
             if not shape.standard:
                 self._gen_training_unsupported(shape)
             return self._forward_train(model, rays, want_weights, noise=noise, z_samples=z_samples)
@@ -920,6 +938,27 @@ class NeRFRendererDGS(torch.nn.Module):
         assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == 512
         sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
         rgb, depth, weights = training.render_with_grad(self, model, rays, z, sc, keep=_keep)
+        return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
+
+    def _forward_train_gen(self, model, rays, want_weights, shape: MlpShape, noise=None, z_samples=None):
+        """_forward_train for a model of any shape of the envelope (train_any_shape): the exact fp32 path of diner_amd/training_gen.py"""
+        from . import training_gen
+        self._settle_fp32(shape, stacklevel=4)
+        r = self._check_rays(rays)
+        SB, NR, _ = r.shape
+        K = int(self.n_samples)
+        with torch.no_grad():
+            if z_samples is not None:
+                z = _f32c(z_samples)
+            else:
+                z = self._sample(r, model, K, self.n_depth_candidates, self.n_gaussian, 0.05, noise, None)["z"]
+            sc, _keep = self._scene(model, need_latent=False)
+        assert SB == sc.SB
+        lat = model.encoder.latent
+        assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == shape.d_latent
+        sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
+        rgb, depth, weights = training_gen.render_with_grad(self, model, rays, z, sc, shape, keep=_keep)
+        self.last_route, self.last_binding = "train_gen", "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     # alias asked for by the north_star text; the reference itself has no render_rays

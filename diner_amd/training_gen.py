@@ -1,0 +1,287 @@
+"""Differentiable render path for any fusion-MLP shape of the shape-general envelope (include/diner_hip.h): the training path of
+``diner_amd/training.py`` for ResnetFC / PositionalEncoding shapes other than the standard one, in exact fp32.
+
+The reference trains any model its constructors accept (``ResnetFC.from_conf`` reads d_hidden, n_blocks, combine_layer and beta from
+``mlp_fine_conf``, num_freqs comes from ``poscode_conf``, d_latent from the encoder's ``num_layers``).  This module runs the layer
+schedule of ResnetFC.forward (reference src/models/resnetfc.py:139-158) for any ``n_blocks`` / ``combine_layer`` on the HIP building
+blocks of ``diner_amd/csrc/train_gen.hip`` (the fp32 MFMA GEMM with activation codes, the point inputs of any num_freqs and latent width
+and their transpose) plus the shape-agnostic ones of ``train.hip`` (view mean, head, column sums, latent scatter, compositing
+backward).  Gradients: every fusion-MLP parameter, ``encoder.latent``, and the rays, source cameras and depth maps when they require
+grad.  PyTorch supplies buffers and the autograd hook -- no arithmetic of the path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import weakref
+
+import torch
+
+from . import _lib
+from ._lib import check
+from .training import CAMERA_INPUTS, camera_leaves
+
+K_CHUNK = 4096  # rows per split of the weight-gradient GEMMs (multiple of 32)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _st(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class Act:
+    """activation code + beta of a shape (DINER_ACT_*)"""
+    __slots__ = ("code", "beta")
+
+    def __init__(self, beta):
+        self.code = _lib.ACT_SOFTPLUS if beta > 0 else _lib.ACT_RELU
+        self.beta = float(beta) if beta > 0 else 1.0
+
+
+def _gemm(A, B, bias, S, Cm, M, N, K, sam, sak, sbk, sbn, ldc, lds, act_a=0, act_b=0, act_s=0, beta=1.0, accumulate=0, atomic=0, k_chunk=0):
+    check(_lib.lib().diner_train_gemm_act(_p(A), _p(B), _p(bias), _p(S), _p(Cm), M, N, K, sam, sak, sbk, sbn, ldc, lds, act_a, act_b, act_s,
+                                          beta, accumulate, atomic, k_chunk, _st(Cm.device)), "diner_train_gemm_act")
+
+
+def linear_fwd(X, W, b, out, act=None, accumulate=False):
+    """out[M,N] (+)= act?(X[M,K]) W[N,K]^T + b"""
+    M, K = X.shape
+    N = W.shape[0]
+    a = act.code if act is not None else _lib.ACT_NONE
+    _gemm(X, W, b, None, out, M, N, K, X.stride(0), 1, 1, W.stride(0), out.stride(0), 0, act_a=a, beta=act.beta if act else 1.0,
+          accumulate=int(accumulate))
+
+
+def linear_bwd_x(dY, W, S, out, act=None, accumulate=False):
+    """out[M,K] (+)= (dY[M,N] W[N,K]) * act'(S)   (S None: no derivative)"""
+    M, N = dY.shape
+    K = W.shape[1]
+    _gemm(dY, W, None, S, out, M, K, N, dY.stride(0), 1, W.stride(0), 1, out.stride(0), 0 if S is None else S.stride(0),
+          act_s=act.code if (act is not None and S is not None) else _lib.ACT_NONE, beta=act.beta if act else 1.0, accumulate=int(accumulate))
+
+
+def linear_bwd_w(dY, X, dW, db, act=None):
+    """dW[N,K] += dY[M,N]^T act?(X[M,K]);  db[N] += sum_m dY (its own column sums)"""
+    M, N = dY.shape
+    K = X.shape[1]
+    _gemm(dY, X, None, None, dW, N, K, M, 1, dY.stride(0), X.stride(0), 1, dW.stride(0), 0, act_b=act.code if act else _lib.ACT_NONE,
+          beta=act.beta if act else 1.0, atomic=1, k_chunk=K_CHUNK)
+    check(_lib.lib().diner_train_colsum(_p(dY), M, N, dY.stride(0), _p(db), _st(dY.device)), "diner_train_colsum")
+
+
+def mlp_params(mlp):
+    """The fusion MLP's parameters in the order of the autograd function's inputs: lin_in, lin_z[0 .. min(combine_layer, n_blocks) - 1],
+    every block's fc_0 / fc_1, lin_out (weight, bias each)."""
+    nlz = min(int(mlp.combine_layer), int(mlp.n_blocks))
+    ps = [mlp.lin_in.weight, mlp.lin_in.bias]
+    for b in range(nlz):
+        ps += [mlp.lin_z[b].weight, mlp.lin_z[b].bias]
+    for b in range(int(mlp.n_blocks)):
+        ps += [mlp.blocks[b].fc_0.weight, mlp.blocks[b].fc_0.bias, mlp.blocks[b].fc_1.weight, mlp.blocks[b].fc_1.bias]
+    ps += [mlp.lin_out.weight, mlp.lin_out.bias]
+    return ps
+
+
+class _Layout:
+    """indices of a shape's parameters in ``mlp_params`` order"""
+
+    def __init__(self, shape):
+        self.nb, self.cl = shape.n_blocks, shape.combine_layer
+        self.nlz = min(self.cl, self.nb)
+
+    def lz(self, b):
+        return 2 + 2 * b
+
+    def blk(self, b):
+        return 2 + 2 * self.nlz + 4 * b
+
+    @property
+    def out(self):
+        return 2 + 2 * self.nlz + 4 * self.nb
+
+
+class _RenderGenFn(torch.autograd.Function):
+    """(rays, latent, poses, focal, c, image_shape, depths, *mlp_params) -> (rgb, depth, weights) for fixed samples, any shape of the
+    envelope.  Same contract as ``training._RenderFn`` (``cams``: the caller's leaves, whose versions backward() checks)."""
+
+    @staticmethod
+    def forward(ctx, renderer, scene, ix, keep, cams, shape, z, rays, latent, poses, focal, c_, image_shape, depths, *params):
+        L = _lib.lib()
+        rays = rays.detach()
+        dev = rays.device
+        st = _st(dev)
+        SB, NR, K = z.shape
+        NV, P = scene.NV, NR * K
+        R = NV * P
+        lay, act = _Layout(shape), Act(shape.beta)
+        H, F = shape.d_hidden, shape.num_freqs
+        ld_in = 8 * (F + 1)
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        lat = latent.detach().to(torch.float32).contiguous()
+        SBl, NVl, Cl, hl, wl = lat.shape
+        lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
+        check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+        prm = [p.detach().to(torch.float32).contiguous() for p in params]
+        # backward() re-reads these tensors: an in-place update between forward and backward must be an error (training._RenderFn)
+        ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
+        ctx.cam_versions = [(t, t._version) for t in cams]
+        w_in = torch.zeros((H, ld_in), dtype=torch.float32, device=dev)   # lin_in's weight, zero-padded to the input's ld_in columns
+        w_in[:, :shape.d_in] = prm[0]
+        rgbsigma = f(SB, NR, K, 4)
+        ixp = C.byref(ix) if ix is not None else None
+        saved = []
+        for sb in range(SB):
+            inp, zl, taps = f(R, ld_in), f(R, scene.C), f(R, 8)
+            check(L.diner_train_point_inputs_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
+                                                 _p(taps), st), "diner_train_point_inputs_gen")
+            x = f(R, H)
+            linear_fwd(inp, w_in, prm[1], x)                                                   # resnetfc.py:139
+            blocks = []
+            for b in range(lay.nb):
+                if b == lay.cl:                                                                # :146-149 (mean over views)
+                    xbar = f(P, H)
+                    check(L.diner_train_view_mean(_p(x), P * H, NV, _p(xbar), 0, st), "diner_train_view_mean")
+                    x = xbar
+                if b < lay.cl:                                                                 # :151-153, x += lin_z[b](z) in place
+                    linear_fwd(zl, prm[lay.lz(b)], prm[lay.lz(b) + 1], x, accumulate=True)
+                i = lay.blk(b)
+                net = torch.empty_like(x)
+                linear_fwd(x, prm[i], prm[i + 1], net, act=act)                                # :62
+                y = x.clone()
+                linear_fwd(net, prm[i + 2], prm[i + 3], y, act=act, accumulate=True)           # :63, :69
+                blocks.append((x, net))
+                x = y
+            out = f(x.shape[0], 4)
+            linear_fwd(x, prm[lay.out], prm[lay.out + 1], out, act=act)                       # :158
+            check(L.diner_train_head(_p(out), None, None, P * 4, _p(rgbsigma[sb]), 0, st), "diner_train_head")  # pixelnerf.py:139-143
+            saved.append((inp, zl, taps, blocks, x, out))
+        N = SB * NR
+        rgb, depth, weights = f(SB, NR, 3), f(SB, NR), f(SB, NR, K)
+        check(L.diner_composite(_p(rays), _p(z), _p(rgbsigma), N, K, int(bool(renderer.white_bkgd)), _p(rgb), _p(depth), _p(weights), None, st),
+              "diner_composite")
+        ctx.renderer, ctx.scene, ctx.rays, ctx.z, ctx.rgbsigma = renderer, scene, rays, z, rgbsigma
+        ctx.saved_acts, ctx.prm, ctx.w_in, ctx.lat_shape = saved, prm, w_in, tuple(latent.shape)
+        ctx.keep = (lat, lat_nhwc, keep)
+        ctx.shape, ctx.ix = shape, ix
+        ctx.cam_shapes = [tuple(t.shape) for t in (poses, focal, c_, image_shape, depths)]
+        return rgb, depth, weights
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_weights):
+        L = _lib.lib()
+        for t, ver in [(ref(), ver) for ref, ver in ctx.versions] + ctx.cam_versions:
+            if t is None or t._version != ver:
+                raise RuntimeError("diner_amd.training_gen: one of the variables needed for gradient computation (an MLP parameter, "
+                                   "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
+                                   "between forward and backward")
+        # which geometric leaves want a gradient (inputs 7 and 9..13: rays, poses, focal, c, image_shape, depths)
+        want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[7],) + tuple(ctx.needs_input_grad[9:14])))
+        cam_any = any(want.values())
+        scene, rays, z, rgbsigma, prm, shape = ctx.scene, ctx.rays, ctx.z, ctx.rgbsigma, ctx.prm, ctx.shape
+        lay, act = _Layout(shape), Act(shape.beta)
+        H, ld_in = shape.d_hidden, ctx.w_in.shape[1]
+        dev = rays.device
+        st = _st(dev)
+        SB, NR, K = z.shape
+        NV, P = scene.NV, NR * K
+        R = NV * P
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+        d_rgb, d_depth, d_weights = c(d_rgb), c(d_depth), c(d_weights)
+        if d_rgb is None:
+            d_rgb = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev)
+        d_rgbsigma = f(SB, NR, K, 4)
+        d_far = None
+        white = int(bool(ctx.renderer.white_bkgd))
+        if want["rays"]:
+            d_far = f(SB, NR)
+            check(L.diner_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
+                                                 _p(d_rgbsigma), _p(d_far), st), "diner_composite_backward_far")
+        else:
+            check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
+                                             _p(d_rgbsigma), st), "diner_composite_backward")
+        if cam_any:
+            sh_poses, sh_focal, sh_c, sh_ishape, sh_depths = ctx.cam_shapes
+            z0 = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+            g_rays = f(SB, NR, 8) if want["rays"] else None
+            g_poses = z0((SB, NV, 4, 4)) if want["poses"] else None
+            g_focal = f(SB, NV, 2) if want["focal"] else None
+            g_c = f(SB, NV, 2) if want["c"] else None
+            g_ishape = z0(2) if want["image_shape"] else None
+            g_depths = z0((SB, NV, scene.H, scene.W)) if want["depths"] else None
+            ws = f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
+        ixp = C.byref(ctx.ix) if ctx.ix is not None else None
+        lat_nhwc = ctx.keep[1]
+        g = [torch.zeros_like(p) for p in prm]          # parameter gradients (fp32, accumulated atomically)
+        g_in = torch.zeros_like(ctx.w_in)
+        SBl, NVl, Cl, hl, wl = ctx.lat_shape
+        d_lat_nhwc = torch.zeros((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
+        for sb in range(SB):
+            inp, zl, taps, blocks, x_last, out = ctx.saved_acts[sb]
+            out_rows = x_last.shape[0]
+            d_out = f(out_rows, 4)
+            check(L.diner_train_head(_p(out), _p(rgbsigma[sb]), _p(d_rgbsigma[sb]), P * 4, _p(d_out), 1, st), "diner_train_head(bwd)")
+            linear_bwd_w(d_out, x_last, g[lay.out], g[lay.out + 1], act=act)                  # lin_out
+            d_x = f(out_rows, H)
+            linear_bwd_x(d_out, prm[lay.out], x_last, d_x, act=act)
+            d_zl = torch.zeros((R, scene.C), dtype=torch.float32, device=dev) if (lay.nlz == 0 and cam_any) else None
+            for b in reversed(range(lay.nb)):
+                xb, net = blocks[b]
+                i = lay.blk(b)
+                d_y = d_x                                                                      # gradient of the block's output
+                linear_bwd_w(d_y, net, g[i + 2], g[i + 3], act=act)                            # fc_1
+                d_net = torch.empty_like(net)
+                linear_bwd_x(d_y, prm[i + 2], net, d_net, act=act)
+                linear_bwd_w(d_net, xb, g[i], g[i + 1], act=act)                               # fc_0
+                linear_bwd_x(d_net, prm[i], xb, d_y, act=act, accumulate=True)                 # d_xb = d_y + (d_net W0) act'(xb), in place
+                d_xb = d_y
+                if b < lay.cl:                                                                 # lin_z[b]: its own dY is d_xb
+                    j = lay.lz(b)
+                    linear_bwd_w(d_xb, zl, g[j], g[j + 1])
+                    if d_zl is None:
+                        d_zl = f(R, scene.C)
+                        linear_bwd_x(d_xb, prm[j], None, d_zl)
+                    else:
+                        linear_bwd_x(d_xb, prm[j], None, d_zl, accumulate=True)
+                if b == lay.cl:                                                                # the mean's transpose: rows P -> R
+                    d_x = f(R, H)
+                    check(L.diner_train_view_mean(_p(d_xb), P * H, NV, _p(d_x), 1, st), "diner_train_view_mean(bwd)")
+                else:
+                    d_x = d_xb
+            linear_bwd_w(d_x, inp, g_in, g[1])                                                 # lin_in
+            if cam_any:   # lin_in's input gradient, then the transpose of the point inputs to the geometric leaves
+                d_in = f(R, ld_in)
+                linear_bwd_x(d_x, ctx.w_in, None, d_in)
+                check(L.diner_train_point_inputs_backward_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in), ld_in,
+                                                              _p(d_zl), _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c),
+                                                              _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward_gen")
+            if lay.nlz:
+                check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
+                      "diner_train_bilinear_scatter")
+        d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
+        check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+        g[0] = g_in[:, :shape.d_in].contiguous()
+        cam = (None,) * 6
+        if cam_any:
+            cam = (g_rays,
+                   None if g_poses is None else g_poses[..., :sh_poses[-2], :].reshape(sh_poses),   # ([.., 3, 4] poses: rows 0..2)
+                   None if g_focal is None else g_focal.reshape(sh_focal),
+                   None if g_c is None else g_c.reshape(sh_c),
+                   None if g_ishape is None else g_ishape.reshape(sh_ishape),
+                   None if g_depths is None else g_depths.reshape(sh_depths))
+        return (None, None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
+
+
+def render_with_grad(renderer, model, rays, z, scene, shape, keep=None):
+    """rgb, depth, weights = composite(model, rays, z) for a model of any shape of the envelope, with gradients to every fusion-MLP
+    parameter, encoder.latent, and the rays, cameras and depth maps when they require grad."""
+    if shape.combine_layer >= shape.n_blocks and scene.NV != 1:
+        raise NotImplementedError(f"combine_layer={shape.combine_layer} >= n_blocks={shape.n_blocks} (no mean over views) with NV={scene.NV}: "
+                                  "the reference supports it for one view only (pixelnerf.py:137)")
+    params = mlp_params(model.mlp_fine)
+    ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
+    cams = camera_leaves(model, rays)
+    f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
+    return _RenderGenFn.apply(renderer, scene, ix, keep, cams, shape, z, *f32[:1], model.encoder.latent, *f32[1:], *params)

@@ -114,7 +114,9 @@ typedef struct DinerLatentIndex {
 /* Version of THIS ABI (argument lists, struct layouts).  Bumped by every incompatible change; a binding compiled or written
  * against another value must refuse to call in: diner_version() returns the value the loaded library was built with, the
  * torch-ops extension checks it at every op entry, diner_amd/_lib.py at load time.  (2: diner_render / diner_composite gained
- * `status`.  3: the shape-general inference path, the *_gen entry points below.) */
+ * `status`.  3: the shape-general inference path, the *_gen entry points below.)  New entry points that leave every existing argument
+ * list and struct layout as it was do not bump it (the shape-general training blocks, diner_train_gemm_act and
+ * diner_train_point_inputs(_backward)_gen, came under 3). */
 #define DINER_ABI_VERSION 3
 
 const char *diner_last_error(void);
@@ -412,6 +414,37 @@ int diner_train_point_inputs_backward(const DinerScene *scene, const DinerLatent
                                       const float *rays, const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in56,
                                       const float *d_zlat, const float *d_far, float *workspace, float *d_rays, float *d_poses,
                                       float *d_focal, float *d_c, float *d_image_shape, float *d_depths, void *stream);
+
+/* ---- shape-general training path: building blocks of diner_amd/training_gen.py, which trains any shape of the shape-general
+ * inference envelope above in exact fp32 (v_mfma_f32_32x32x2_f32).  The shape-agnostic entry points above (view mean, head,
+ * colsum, bilinear scatter, nhwc_to_nchw, composite backward) serve it unchanged. ------------------------------------------- */
+#define DINER_ACT_NONE 0
+#define DINER_ACT_RELU 1
+#define DINER_ACT_SOFTPLUS 2     /* Softplus(beta, threshold 20): beta*x > 20 ? x : log1p(exp(beta*x)) / beta */
+/* C[m][n] (+)= sum_k actA(A[m*sam + k*sak]) * actB(B[k*sbk + n*sbn]) (+ bias[n]), then * act_s'(S[m*lds + n]) when S is not NULL:
+ * diner_train_gemm's fp32 mode with activation codes (DINER_ACT_*) in place of the relu flags.  act_a / act_b transform an operand
+ * while it is staged (forward: act(X) W^T; weight gradient: dY^T act(X)); act_s' is the activation's derivative as autograd
+ * evaluates it at the saved pre-activation S (ReLU: [S > 0]; Softplus: z / (z + 1) with z = exp(beta S), 1 where beta S > 20).
+ * beta: the Softplus beta (> 0 when any code is DINER_ACT_SOFTPLUS).  Each operand must be contiguous along one of its two indices,
+ * with the contiguous extent a multiple of 4; N % 4 == 0; k_chunk (0 = no split, else a multiple of 32) splits the contraction over
+ * blockIdx.z (use with atomic = 1); accumulate = 1 adds to C. */
+int diner_train_gemm_act(const float *A, const float *B, const float *bias, const float *S, float *C, int64_t M, int32_t N, int32_t K,
+                         int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int64_t ldc, int64_t lds, int32_t act_a, int32_t act_b,
+                         int32_t act_s, float beta, int32_t accumulate, int32_t atomic, int64_t k_chunk, void *stream);
+/* diner_train_point_inputs_ix for any num_freqs F = scene->num_freqs (1..63) and latent width C = scene->C (a multiple of 8 in
+ * [8, 1024]): in_out [R, ld_in] = the 7 + 8F inputs of pixelnerf.py:128 in diner_train_point_inputs' column order, zero-padded to
+ * ld_in (>= 7 + 8F, a multiple of 4) columns; zlat [R, C]; taps [R, 8].  The encodings use sinf (the shape-general inference
+ * kernel's arithmetic).  latent_nhwc: diner_pack_latent's copy; index NULL = bilinear / border. */
+int diner_train_point_inputs_gen(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const float *rays,
+                                 const float *z, int64_t NR, int32_t K, int32_t sb, float *in_out, int64_t ld_in, float *zlat, float *taps,
+                                 void *stream);
+/* diner_train_point_inputs_backward for diner_train_point_inputs_gen: d_in [R, ld_in] (columns >= 7 + 8F ignored), d_zlat [R, C];
+ * same outputs, same workspace (diner_train_camera_workspace_floats), same fixed-order reductions. */
+int diner_train_point_inputs_backward_gen(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc,
+                                          const float *rays, const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in,
+                                          int64_t ld_in, const float *d_zlat, const float *d_far, float *workspace, float *d_rays,
+                                          float *d_poses, float *d_focal, float *d_c, float *d_image_shape, float *d_depths,
+                                          void *stream);
 
 #ifdef __cplusplus
 }
