@@ -78,6 +78,8 @@ SYMBOLS = {
     "diner_last_error": (C.c_char_p, []),
     "diner_version": (C.c_int, []),
     "diner_gen_rays": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "diner_gen_rays_backward_workspace_floats": (_I64, [_I32, _I32, _I32]),
+    "diner_gen_rays_backward": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "diner_depth2normal": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "diner_pack_maps": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),
     "diner_pack_maps_from_depth": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),

@@ -100,6 +100,8 @@ int launch_train_point_inputs_bwd(const DinerScene &, const DinerLatentIndex &, 
                                   hipStream_t);
 int launch_gen_rays(const float *, const float *, const float *, const float *, int, int, int, float *, hipStream_t);
 int launch_depth2normal(const float *, const float *, int, int, int, float *, hipStream_t);
+int64_t gen_rays_bwd_workspace_floats(int, int, int);
+int launch_gen_rays_bwd(const float *, const float *, const float *, int, int, int, float *, float *, float *, float *, float *, hipStream_t);
 int launch_pack_maps_from_depth(const float *, const float *, const float *, int, int, int, float *, hipStream_t);
 int launch_decode_depth(const unsigned short *, const unsigned short *, const unsigned short *, int64_t, int, int, int, float, float, float,
                         float, float, float *, float *, float *, hipStream_t);
@@ -189,6 +191,24 @@ int diner_gen_rays(const float *extrinsics, const float *intrinsics, const float
     if (B < 0 || H <= 0 || W <= 0) return bad("gen_rays: bad size");
     if (B > 0 && (!extrinsics || !intrinsics || !z_near || !z_far || !rays_out)) return bad("gen_rays: NULL pointer");
     return launch_gen_rays(extrinsics, intrinsics, z_near, z_far, B, H, W, rays_out, (hipStream_t)stream);
+}
+
+int64_t diner_gen_rays_backward_workspace_floats(int32_t B, int32_t H, int32_t W)
+{
+    if (B < 0 || H <= 0 || W <= 0) return -1;
+    return gen_rays_bwd_workspace_floats(B, H, W);
+}
+
+int diner_gen_rays_backward(const float *extrinsics, const float *intrinsics, const float *d_rays, int32_t B, int32_t H, int32_t W,
+                            float *d_extrinsics, float *d_intrinsics, float *d_near, float *d_far, float *workspace, void *stream)
+{
+    if (B < 0 || H <= 0 || W <= 0) return bad("gen_rays_backward: bad size");
+    if (B == 0) return DINER_OK;
+    if (!extrinsics || !intrinsics || !d_rays || !d_extrinsics || !d_intrinsics || !d_near || !d_far || !workspace)
+        return bad("gen_rays_backward: NULL pointer");
+    if ((uintptr_t)workspace % 8) return bad("gen_rays_backward: workspace not 8-byte aligned");
+    return launch_gen_rays_bwd(extrinsics, intrinsics, d_rays, B, H, W, d_extrinsics, d_intrinsics, d_near, d_far, workspace,
+                               (hipStream_t)stream);
 }
 
 int diner_depth2normal(const float *dmap, const float *intrinsics, int32_t N, int32_t H, int32_t W, float *normals_out,

@@ -34,6 +34,136 @@ __global__ void gen_rays_kernel(const float *__restrict__ extr, const float *__r
     o[7] = z_far[b];
 }
 
+// ---- backward of gen_rays: d_rays [B,H,W,8] -> d_extr [B,4,4], d_intr [B,3,3], d_near [B], d_far [B] ----------------------
+// Per pixel (the forward above, with R = E[:3,:3], t = E[:3,3], p = ((x+.5-cx)/fx, (y+.5-cy)/fy, 1), d^ = p/|p|):
+//   dir_r = sum_k R[k][r] d^_k   ->  dR[k][r] += g_dir[r] d^_k,   g^_k = sum_r R[k][r] g_dir[r]
+//   d^ = p/|p|                   ->  g_p = (g^ - d^ (d^ . g^)) / |p|
+//   p_x = (x+.5-cx)/fx           ->  dcx += -g_px / fx,  dfx += -g_px p_x / fx   (y alike)
+//   o_r = -sum_k R[k][r] t_k     ->  dR[k][r] -= G_o[r] t_k,  dt_k = -sum_r R[k][r] G_o[r],  G_o = sum over pixels of g_o
+// so a camera needs GR_SUMS sums over its pixels: sum g_dir[r] d^_k (9), sum g_px, g_px p_x, g_py, g_py p_y (4), G_o (3), near, far.
+// Store-and-sum, no atomics: pass 1 writes one partial per (camera, block) to the workspace, pass 2 adds them in block order.
+// Everything after the loads is fp64 (the sums of up to 1024^2 terms cancel), so the result is bitwise reproducible.
+constexpr int GR_SUMS = 18, GR_THREADS = 256, GR_MAX_BLOCKS = 256;
+
+// blocks per camera of pass 1: a function of the image size only (the summation order must not depend on anything else)
+static int gen_rays_bwd_blocks(int H, int W)
+{
+    const int64_t n = ((int64_t)H * W + 4 * GR_THREADS - 1) / (4 * GR_THREADS);
+    return n < 1 ? 1 : (n > GR_MAX_BLOCKS ? GR_MAX_BLOCKS : (int)n);
+}
+
+int64_t gen_rays_bwd_workspace_floats(int B, int H, int W)
+{
+    return (int64_t)B * gen_rays_bwd_blocks(H, W) * GR_SUMS * 2;   // doubles
+}
+
+__global__ __launch_bounds__(GR_THREADS) void gen_rays_bwd_partial_kernel(const float *__restrict__ extr, const float *__restrict__ intr,
+                                                                          const float *__restrict__ d_rays, int H, int W, int nblk,
+                                                                          double *__restrict__ part)
+{
+    __shared__ double red[GR_SUMS][GR_THREADS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t npix = (int64_t)H * W;
+    const float *E = extr + b * 16, *Kk = intr + b * 9;
+    double R[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) R[k][r] = (double)E[k * 4 + r];
+    const double fx = Kk[0], fy = Kk[4], cx = Kk[2], cy = Kk[5];
+    double acc[GR_SUMS];
+#pragma unroll
+    for (int q = 0; q < GR_SUMS; ++q) acc[q] = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * GR_THREADS + tid; p < npix; p += (int64_t)nblk * GR_THREADS) {
+        const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+        const double px = ((double)x + 0.5 - cx) / fx, py = ((double)y + 0.5 - cy) / fy;
+        const double n = sqrt(px * px + py * py + 1.0);
+        const double dh[3] = {px / n, py / n, 1.0 / n};
+        const float *g = d_rays + ((int64_t)b * npix + p) * 8;
+        const double gd[3] = {(double)g[3], (double)g[4], (double)g[5]};
+        double gh[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) acc[k * 3 + r] += gd[r] * dh[k];
+            gh[k] = R[k][0] * gd[0] + R[k][1] * gd[1] + R[k][2] * gd[2];
+        }
+        const double dot = dh[0] * gh[0] + dh[1] * gh[1] + dh[2] * gh[2];
+        const double gpx = (gh[0] - dh[0] * dot) / n, gpy = (gh[1] - dh[1] * dot) / n;
+        acc[9] += gpx;
+        acc[10] += gpx * px;
+        acc[11] += gpy;
+        acc[12] += gpy * py;
+        acc[13] += (double)g[0];
+        acc[14] += (double)g[1];
+        acc[15] += (double)g[2];
+        acc[16] += (double)g[6];
+        acc[17] += (double)g[7];
+    }
+#pragma unroll
+    for (int q = 0; q < GR_SUMS; ++q) red[q][tid] = acc[q];
+    __syncthreads();
+    for (int s = GR_THREADS / 2; s > 0; s >>= 1) {   // fixed tree
+        if (tid < s)
+#pragma unroll
+            for (int q = 0; q < GR_SUMS; ++q) red[q][tid] += red[q][tid + s];
+        __syncthreads();
+    }
+    if (tid < GR_SUMS) part[((int64_t)b * nblk + blockIdx.x) * GR_SUMS + tid] = red[tid][0];
+}
+
+__global__ __launch_bounds__(64) void gen_rays_bwd_final_kernel(const float *__restrict__ extr, const float *__restrict__ intr, int nblk,
+                                                                const double *__restrict__ part, float *__restrict__ d_extr,
+                                                                float *__restrict__ d_intr, float *__restrict__ d_near,
+                                                                float *__restrict__ d_far)
+{
+    __shared__ double s[GR_SUMS];
+    const int b = blockIdx.x, q = threadIdx.x;
+    if (q < GR_SUMS) {
+        double a = 0.0;
+        for (int i = 0; i < nblk; ++i) a += part[((int64_t)b * nblk + i) * GR_SUMS + q];   // block order
+        s[q] = a;
+    }
+    __syncthreads();
+    if (q != 0) return;
+    const float *E = extr + b * 16, *Kk = intr + b * 9;
+    float *dE = d_extr + b * 16, *dK = d_intr + b * 9;
+    const double Go[3] = {s[13], s[14], s[15]};
+    for (int k = 0; k < 3; ++k) {
+        const double tk = (double)E[k * 4 + 3];
+        double dt = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            dE[k * 4 + r] = (float)(s[k * 3 + r] - Go[r] * tk);
+            dt -= (double)E[k * 4 + r] * Go[r];
+        }
+        dE[k * 4 + 3] = (float)dt;
+    }
+    for (int j = 12; j < 16; ++j) dE[j] = 0.0f;                 // E[3,:] is not read
+    const double fx = Kk[0], fy = Kk[4];
+    for (int j = 0; j < 9; ++j) dK[j] = 0.0f;                   // only fx, fy, cx, cy are read
+    dK[0] = (float)(-s[10] / fx);
+    dK[4] = (float)(-s[12] / fy);
+    dK[2] = (float)(-s[9] / fx);
+    dK[5] = (float)(-s[11] / fy);
+    d_near[b] = (float)s[16];
+    d_far[b] = (float)s[17];
+}
+
+int launch_gen_rays_bwd(const float *extr, const float *intr, const float *d_rays, int B, int H, int W, float *d_extr, float *d_intr,
+                        float *d_near, float *d_far, float *workspace, hipStream_t st)
+{
+    if (B == 0) return DINER_OK;
+    const int nblk = gen_rays_bwd_blocks(H, W);
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(gen_rays_bwd_partial_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(GR_THREADS), 0, st, extr, intr, d_rays, H, W,
+                       nblk, part);
+    int rc = check_launch("gen_rays_bwd_partial_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(gen_rays_bwd_final_kernel, dim3((unsigned)B), dim3(64), 0, st, extr, intr, nblk, (const double *)part, d_extr, d_intr,
+                       d_near, d_far);
+    return check_launch("gen_rays_bwd_final_kernel");
+}
+
 // One thread per OUTPUT pixel.  out(y, x) = in(y*stride, x*stride): torchvision's NEAREST resize for a downsample
 // of 1/stride (dtu.py:113-117).  depth = ((u16 * mul0) / div) * mul1 with one rounding per operation, the order of
 // dtu.py:104-105,119 (Facescape: div = mul1 = 1, facescape.py:80-91); std = a * conf + b with conf decoded the

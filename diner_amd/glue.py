@@ -1,7 +1,8 @@
 """HIP versions of the two per-image producers next to the render path,
 with the reference's own function signatures so they can replace them in place:
 
-* :func:`gen_rays`      -- reference ``src/util/cam_geometry.py:36-79``
+* :func:`gen_rays`      -- reference ``src/util/cam_geometry.py:36-79`` (differentiable in the cameras, near and far, like the
+  reference's plain-torch version: the backward is ``diner_gen_rays_backward``)
 * :func:`depth2normal`  -- reference ``src/util/depth2normal.py:7-87``
 """
 from __future__ import annotations
@@ -22,18 +23,93 @@ def _st(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-@torch.no_grad()
-def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far):
-    """extrinsics [B,4,4], intrinsics [B,3,3], z_near/z_far [B] -> rays [B,H,W,8]
-    (origin, unit direction, near, far; pixel centres, OpenCV convention)."""
-    e, k, zn, zf = _f(extrinsics), _f(intrinsics), _f(z_near).reshape(-1), _f(z_far).reshape(-1)
-    if not e.is_cuda:
-        raise RuntimeError("diner_amd.glue.gen_rays runs on the GPU only")
+def _per_camera(v, B, dev):
+    """z_near / z_far as B contiguous fp32 values: a tensor of B elements, or one value (a scalar, a 1-element tensor) for all"""
+    t = _f(torch.as_tensor(v, device=dev)).reshape(-1)
+    if t.numel() == 1 and B != 1:
+        t = t.expand(B).contiguous()
+    if t.numel() != B:
+        raise ValueError(f"gen_rays: z_near / z_far must hold 1 or B={B} values, not {t.numel()}")
+    return t
+
+
+def _gen_rays(e, k, zn, zf, W, H):
     B = e.shape[0]
     out = torch.empty((B, int(H), int(W), 8), dtype=torch.float32, device=e.device)
     check(_lib.lib().diner_gen_rays(e.data_ptr(), k.data_ptr(), zn.data_ptr(), zf.data_ptr(), B, int(H), int(W),
                                     out.data_ptr(), _st(e.device)), "diner_gen_rays")
     return out
+
+
+def gen_rays_backward(e, k, d_rays, H, W):
+    """Backward of :func:`gen_rays` on fp32 contiguous cameras e [B,4,4], k [B,3,3] and d_rays [B,H*W,8] (or [B,H,W,8]):
+    -> d_extrinsics [B,4,4], d_intrinsics [B,3,3], d_near [B], d_far [B] in fp32 (diner_gen_rays_backward: fixed-order sums,
+    bitwise reproducible)."""
+    B, dev = e.shape[0], e.device
+    g = _f(d_rays)
+    assert g.numel() == B * int(H) * int(W) * 8, "gen_rays_backward: d_rays must be [B, H, W, 8]"
+    L = _lib.lib()
+    n = int(L.diner_gen_rays_backward_workspace_floats(B, int(H), int(W)))
+    if n < 0:
+        raise ValueError(f"gen_rays_backward: bad sizes B={B}, H={H}, W={W}")
+    ws = torch.empty(max(n, 2), dtype=torch.float32, device=dev)
+    d_e = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    d_k = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    d_n = torch.empty(B, dtype=torch.float32, device=dev)
+    d_f = torch.empty(B, dtype=torch.float32, device=dev)
+    check(L.diner_gen_rays_backward(e.data_ptr(), k.data_ptr(), g.data_ptr(), B, int(H), int(W), d_e.data_ptr(), d_k.data_ptr(),
+                                    d_n.data_ptr(), d_f.data_ptr(), ws.data_ptr(), _st(dev)), "diner_gen_rays_backward")
+    return d_e, d_k, d_n, d_f
+
+
+def _like(g, t):
+    """a gradient computed for B per-camera values, in the shape / dtype / device of the input ``t`` it belongs to"""
+    if not isinstance(t, torch.Tensor):
+        return None
+    if t.numel() == 1 and g.numel() != 1:
+        g = g.sum()
+    return g.reshape(t.shape).to(dtype=t.dtype, device=t.device)
+
+
+class _GenRaysFn(torch.autograd.Function):
+    """gen_rays with a backward: forward = diner_gen_rays (the no-grad call's values, bit for bit), backward = diner_gen_rays_backward"""
+
+    @staticmethod
+    def forward(ctx, extrinsics, intrinsics, z_near, z_far, W, H):
+        e, k = _f(extrinsics), _f(intrinsics)
+        B = e.shape[0]
+        out = _gen_rays(e, k, _per_camera(z_near, B, e.device), _per_camera(z_far, B, e.device), W, H)
+        ctx.save_for_backward(extrinsics, intrinsics)    # (version-checked by autograd: an in-place edit before backward raises)
+        ctx.e, ctx.k, ctx.HW = e, k, (int(H), int(W))
+        ctx.zs = (z_near, z_far)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rays):
+        extrinsics, intrinsics = ctx.saved_tensors
+        H, W = ctx.HW
+        d_e, d_k, d_n, d_f = gen_rays_backward(ctx.e, ctx.k, d_rays, H, W)
+        z_near, z_far = ctx.zs
+        return (_like(d_e, extrinsics) if ctx.needs_input_grad[0] else None,
+                _like(d_k, intrinsics) if ctx.needs_input_grad[1] else None,
+                _like(d_n, z_near) if ctx.needs_input_grad[2] else None,
+                _like(d_f, z_far) if ctx.needs_input_grad[3] else None, None, None)
+
+
+def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far):
+    """extrinsics [B,4,4], intrinsics [B,3,3], z_near/z_far [B] (or one value for all) -> rays [B,H,W,8]
+    (origin, unit direction, near, far; pixel centres, OpenCV convention).  Differentiable with respect to every tensor input, as the
+    reference's gen_rays is: the gradient reaches extrinsics rows 0..2, the intrinsics entries fx, fy, cx, cy (the others get exactly 0),
+    near and far; the forward values are those of the no-grad call, bit for bit."""
+    if not extrinsics.is_cuda:
+        raise RuntimeError("diner_amd.glue.gen_rays runs on the GPU only")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                       for t in (extrinsics, intrinsics, z_near, z_far)):
+        return _GenRaysFn.apply(extrinsics, intrinsics, z_near, z_far, W, H)
+    with torch.no_grad():
+        e, k = _f(extrinsics), _f(intrinsics)
+        B = e.shape[0]
+        return _gen_rays(e, k, _per_camera(z_near, B, e.device), _per_camera(z_far, B, e.device), W, H)
 
 
 @torch.no_grad()

@@ -246,6 +246,9 @@ class NeRFRendererDGS(torch.nn.Module):
         # as before.  A plain attribute, so that a config can set it (renderer.kwargs.train_any_shape).
         self.train_any_shape = bool(train_any_shape)
         self._force_gen_train = False   # test-only: train the standard shape on that path as well
+        # render_image under autograd: rays per chunk of its backward, which re-runs the training path chunk by chunk (peak memory = one
+        # chunk's training footprint + the frame's saved rays, samples and outputs).  A plain attribute, so that a config can set it.
+        self.grad_chunk_rays = 4096
         self._latent_gen = self._mlp_gen = 0         # bumped by every re-pack; the lin_z maps depend on both
         # Non-finite guard.  The compositing kernel ORs DINER_STATUS_NONFINITE into a device word when an rgb-sigma
         # sample is inf/NaN (in f16x3 mode: an MLP activation beyond the fp16 range, |x| >= ~1e6).  The word is copied
@@ -837,14 +840,41 @@ class NeRFRendererDGS(torch.nn.Module):
         self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
-    @torch.no_grad()
     def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False):
         """The render half of ``DINER.predict_imgs_from_batch`` (reference src/models/diner.py:75-97) without the
         ray-batch loop and without a rays tensor round trip: ``gen_rays`` (src/util/cam_geometry.py:36-79) is evaluated
         inside the sampler kernel (``diner_render_image``), the whole target image is ONE launch per stage (no 4096-ray
         chunks, no ``torch.cat``), output in the reference's image layout.  Bit-identical to ``forward(gen_rays(...))``.
+        Under autograd -- grad mode on and ``forward()``'s predicate (an MLP parameter, ``encoder.latent``, a source camera or
+        ``encoder.depths`` requiring grad) or one of the four target-camera arguments requiring grad -- the same frame, bit for bit,
+        gets a ``grad_fn``: its backward re-runs the training path (``forward()``'s arithmetic under autograd) on the saved rays and
+        samples in chunks of ``grad_chunk_rays`` rays and takes the rays' gradient on to the target cameras (``_RenderImageFn``).
         :param target_extrinsics: [SB,4,4] world->cam;  target_intrinsics: [SB,3,3];  z_near, z_far: [SB] or scalars
         :return: rgb [SB,3,H,W] (, depth [SB,1,H,W])"""
+        if torch.is_grad_enabled() and (self._wants_grad(model, None) or any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in (target_extrinsics, target_intrinsics, z_near, z_far))):
+            return self._render_image_grad(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth)
+        return self._render_image(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth)
+
+    def _render_image_grad(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth):
+        shape = self._validate_model(model)
+        if not shape.standard and not self._use_gen_train(shape):
+            self._gen_training_unsupported(shape)          # before any device work, as forward() raises it
+        from .training import camera_leaves
+        leaves = [model.encoder.latent, *camera_leaves(model, None)[1:], *model.mlp_fine.parameters()]
+        H, W = int(H), int(W)
+        rgb, depth = _RenderImageFn.apply(self, model, shape, (H, W), target_extrinsics, target_intrinsics, z_near, z_far, *leaves)
+        SB = rgb.shape[0]
+        rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
+        if return_depth:
+            return rgb, depth.view(SB, H, W, 1).permute(0, 3, 1, 2)
+        return rgb
+
+    @torch.no_grad()
+    def _render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False, saved=None):
+        """render_image's inference launch.  ``saved`` (a dict): take the ctypes binding (the torch op gives no access to its workspace)
+        and hand out the generated rays [SB,H*W,8], the samples the compositing used [SB,H*W,K] (workspace layout rays | z | ..., here
+        z only: the rays go to rays_out) and the flat rgb [SB,H*W,3] / depth [SB,H*W]."""
         shape = self._route(model)
         gen = self._use_gen(shape)
         dev = target_extrinsics.device
@@ -869,6 +899,7 @@ class NeRFRendererDGS(torch.nn.Module):
         self._poll_status()
         seed = self._next_seed()
         ix = self._latent_index(model)   # another lookup mode than bilinear / border: the _ix entry points, through ctypes
+        rays_out = None if saved is None else torch.empty((SB, H * W, 8), dtype=torch.float32, device=dev)
         if gen and ix is not None:
             cs = shape.c_struct()
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
@@ -876,7 +907,7 @@ class NeRFRendererDGS(torch.nn.Module):
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
             check(L.diner_render_image_gen_ix(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg),
-                                              int(bool(self.white_bkgd)), seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None,
+                                              int(bool(self.white_bkgd)), seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None,
                                               _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image_gen_ix")
             self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
         elif gen:
@@ -886,7 +917,7 @@ class NeRFRendererDGS(torch.nn.Module):
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
             check(L.diner_render_image_gen(C.byref(sc), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)),
-                                           seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
+                                           seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
                   "diner_render_image_gen")
             self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
         elif ix is not None:
@@ -894,9 +925,9 @@ class NeRFRendererDGS(torch.nn.Module):
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
             check(L.diner_render_image_ix(C.byref(sc), C.byref(ix), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec,
-                                          seed, _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
+                                          seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
                   "diner_render_image_ix")
-        elif self.binding == "torch_ops":
+        elif self.binding == "torch_ops" and saved is None:
             from . import ops as _ops
             maps_t, poses_t, focal_t, c_t, latent_t, linz_t = _keep
             rgb, depth = _ops.load().render_image(maps_t, poses_t, focal_t, c_t, latent_t, linz_t, packed, E, Ki, zn, zf, int(H), int(W), sc.image_w,
@@ -908,10 +939,13 @@ class NeRFRendererDGS(torch.nn.Module):
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
             check(L.diner_render_image(C.byref(sc), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec, seed,
-                                       _ptr(ws), None, _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image")
+                                       _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image")
         if not gen:
             self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
-            self.last_binding = self.binding if ix is None else "ctypes"
+            self.last_binding = self.binding if ix is None and saved is None else "ctypes"
+        if saved is not None:
+            n = SB * H * W
+            saved.update(rays=rays_out, z=ws[n * 8:n * (8 + K)].view(SB, H * W, K).clone(), rgb=rgb, depth=depth)
         self._after_launch(dev, sync=self.finite_check != "off")    # once per frame: a NaN image never leaves this function
         rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
         if return_depth:
@@ -969,3 +1003,78 @@ class NeRFRendererDGS(torch.nn.Module):
         if want_weights:
             out.weights = weights
         return out
+
+
+class _RenderImageFn(torch.autograd.Function):
+    """(target_extrinsics, target_intrinsics, z_near, z_far, encoder.latent, poses, focal, c, image_shape, encoder.depths, *MLP parameters)
+    -> rgb [SB,H*W,3], depth [SB,H*W] of ``NeRFRendererDGS.render_image``.
+
+    forward: the inference entry point of the model's route (the no-grad frame, bit for bit), keeping the generated rays and the samples.
+    backward: the training path -- what ``forward(model, rays, z_samples=z)`` runs under autograd -- re-run on the saved rays and samples in
+    chunks of ``renderer.grad_chunk_rays`` rays; ``torch.autograd.grad`` of each chunk against its slice of the incoming gradient, summed in
+    chunk order; then the rays' gradient through ``diner_gen_rays_backward`` to the target cameras.  The gradients are those of ``forward()``
+    under autograd (the training path's arithmetic), not of the inference kernel's rounding.  The samples are constants, as in the training
+    path: z_near gets 0 and z_far only the delta_inf term."""
+
+    @staticmethod
+    def forward(ctx, renderer, model, shape, HW, E, Kt, z_near, z_far, *leaves):
+        H, W = HW
+        saved = {}
+        renderer._render_image(model, E, Kt, H, W, z_near, z_far, return_depth=True, saved=saved)
+        ctx.renderer, ctx.model, ctx.shape, ctx.HW, ctx.precision = renderer, model, shape, HW, renderer.precision
+        ctx.rays, ctx.z = saved["rays"], saved["z"]
+        ctx.tcams, ctx.e32, ctx.k32 = (E, Kt, z_near, z_far), _f32c(E), _f32c(Kt)
+        ctx.leaves = leaves
+        # backward() re-reads all of these: an in-place update between forward and backward is an error, as in training._RenderFn
+        ctx.versions = [(t, t._version) for t in (E, Kt, z_near, z_far, *leaves) if isinstance(t, torch.Tensor)]
+        return saved["rgb"], saved["depth"]
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth):
+        r, model, shape = ctx.renderer, ctx.model, ctx.shape
+        from .training import camera_leaves
+        current = [model.encoder.latent, *camera_leaves(model, None)[1:], *model.mlp_fine.parameters()]
+        if (any(t._version != v for t, v in ctx.versions) or len(current) != len(ctx.leaves)
+                or any(a is not b for a, b in zip(current, ctx.leaves))):
+            raise RuntimeError("diner_amd.NeRFRendererDGS.render_image: one of the variables needed for gradient computation (a target "
+                               "camera, an MLP parameter, encoder.latent, or a source camera / depth-map tensor) has been modified by an "
+                               "inplace operation, or re-bound on the model, between forward and backward")
+        want_t = any(ctx.needs_input_grad[4:8])
+        idx = [i for i in range(len(ctx.leaves)) if ctx.needs_input_grad[8 + i]]
+        leaves = [ctx.leaves[i] for i in idx]
+        cot = [(i, g) for i, g in ((0, d_rgb), (1, d_depth)) if g is not None]
+        rays, z = ctx.rays, ctx.z
+        SB, NR, _ = rays.shape
+        acc = [None] * len(idx)
+        d_rays = torch.zeros_like(rays) if want_t else None
+        step = max(1, int(r.grad_chunk_rays))
+        gen = r._use_gen_train(shape)
+        prec, r.precision = r.precision, ctx.precision
+        try:
+            with torch.enable_grad():
+                for a in range(0, NR if cot and (leaves or want_t) else 0, step):
+                    b = min(NR, a + step)
+                    rc = rays[:, a:b].contiguous().requires_grad_(want_t)
+                    zc = z[:, a:b].contiguous()
+                    fine = (r._forward_train_gen(model, rc, False, shape, z_samples=zc) if gen else
+                            r._forward_train(model, rc, False, z_samples=zc)).fine
+                    outs = [(fine.rgb, fine.depth)[i] for i, _ in cot]
+                    gs = torch.autograd.grad(outs, leaves + ([rc] if want_t else []), [g[:, a:b] for _, g in cot], allow_unused=True)
+                    for j in range(len(leaves)):
+                        if gs[j] is not None:
+                            acc[j] = gs[j] if acc[j] is None else acc[j].add_(gs[j])
+                    if want_t and gs[-1] is not None:
+                        d_rays[:, a:b] = gs[-1]
+        finally:
+            r.precision = prec
+        t_grads = [None] * 4
+        if want_t:
+            from .glue import _like, gen_rays_backward
+            H, W = ctx.HW
+            for i, g in enumerate(gen_rays_backward(ctx.e32, ctx.k32, d_rays, H, W)):
+                if ctx.needs_input_grad[4 + i]:
+                    t_grads[i] = _like(g, ctx.tcams[i])
+        leaf_grads = [None] * len(ctx.leaves)
+        for j, i in enumerate(idx):
+            leaf_grads[i] = acc[j] if acc[j] is not None else torch.zeros_like(ctx.leaves[i])
+        return (None, None, None, None, *t_grads, *leaf_grads)

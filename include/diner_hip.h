@@ -127,6 +127,14 @@ int diner_version(void);
  * z_near/z_far [B] -> rays [B,H,W,8] (pixel-centre rays: origin, unit direction, near, far). */
 int diner_gen_rays(const float *extrinsics, const float *intrinsics, const float *z_near, const float *z_far,
                    int32_t B, int32_t H, int32_t W, float *rays_out, void *stream);
+/* Backward of diner_gen_rays (the reference's gen_rays under autograd): d_rays [B,H,W,8] -> d_extrinsics [B,4,4] (row 3: 0),
+ * d_intrinsics [B,3,3] (only fx, fy, cx, cy, i.e. [0,0], [1,1], [0,2], [1,2], are non-zero: the entries gen_rays reads), d_near [B],
+ * d_far [B] (sums of d_rays[..., 6] and [..., 7]).  Every output is written (not accumulated).  Per-block partial sums go to the
+ * workspace (diner_gen_rays_backward_workspace_floats(B, H, W) floats, 8-byte aligned) and are added in a fixed order, in fp64: the
+ * result is bitwise reproducible.  The workspace query returns -1 for bad sizes. */
+int64_t diner_gen_rays_backward_workspace_floats(int32_t B, int32_t H, int32_t W);
+int diner_gen_rays_backward(const float *extrinsics, const float *intrinsics, const float *d_rays, int32_t B, int32_t H, int32_t W,
+                            float *d_extrinsics, float *d_intrinsics, float *d_near, float *d_far, float *workspace, void *stream);
 /* depth2normal (src/util/depth2normal.py:7-87): dmap [N,1,H,W], K [N,3,3] -> normals [N,3,H,W]
  * (central differences of the re-projected depth map + the reference's hole clean-up). */
 int diner_depth2normal(const float *dmap, const float *intrinsics, int32_t N, int32_t H, int32_t W,
