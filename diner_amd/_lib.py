@@ -138,6 +138,21 @@ SYMBOLS = {
                                       C.POINTER(DinerSamplerCfg), _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "diner_render_image_gen_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P,
                                             C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    # the shape-general f16x3 inference path: the argument lists of the *_gen functions (the ABI version stays 3: new entry points only)
+    "diner_mlp_gen_f16_packed_floats": (_I64, [C.POINTER(DinerMlpShape)]),
+    "diner_pack_mlp_gen_f16": (C.c_int, [C.POINTER(DinerMlpShape), C.POINTER(DinerMlpGenRaw), _P, _P]),
+    "diner_render_points_gen_f16": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, _P, _P, _I64, _I32, _P, _P]),
+    "diner_render_gen_f16": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, _P, _I64, C.POINTER(DinerSamplerCfg), _I32,
+                                       _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen_f16": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, C.POINTER(DinerTargetCam),
+                                             C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "diner_render_points_gen_f16_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _P,
+                                                 _I64, _I32, _P, _P]),
+    "diner_render_gen_f16_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _I64,
+                                          C.POINTER(DinerSamplerCfg), _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen_f16_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P,
+                                                C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P,
+                                                _P]),
     "diner_train_point_inputs_ix": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _I32, _P, _P, _I64, _I32, _I32, _P,
                                               _P, _P, _P]),
     # camera / ray / depth-map gradients of the training path

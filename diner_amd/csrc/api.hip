@@ -122,6 +122,11 @@ int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
 int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
 }
+namespace genf16 {
+int64_t packed_floats(const DinerMlpShape &);
+int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+}
 
 int launch_train_gemm_act(const float *, const float *, const float *, const float *, float *, int64_t, int, int, int64_t, int64_t, int64_t,
                           int64_t, int64_t, int64_t, int, int, int, float, int, int, int64_t, hipStream_t);
@@ -683,7 +688,20 @@ int diner_render_image_ix(const DinerScene *scene, const DinerLatentIndex *index
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
-/* ---- shape-general inference path (points_mlp_gen.hip) ---------------------------------------------------------------- */
+/* ---- shape-general inference path (points_mlp_gen.hip; the *_f16 entry points: points_mlp_gen_f16.hip) -------------------- */
+static int check_gen_raw(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, const char *who)
+{
+    const auto fail = [&](const char *what) { set_error("%s: %s", who, what); return (int)DINER_E_INVALID; };
+    const int nlz = shape->combine_layer < shape->n_blocks ? shape->combine_layer : shape->n_blocks;
+    if (!raw->lin_in_w || !raw->lin_in_b || !raw->lin_out_w || !raw->lin_out_b) return fail("NULL weight pointer");
+    if ((nlz && (!raw->lin_z_w || !raw->lin_z_b)) || !raw->fc0_w || !raw->fc0_b || !raw->fc1_w || !raw->fc1_b) return fail("NULL layer array");
+    for (int b = 0; b < nlz; ++b)
+        if (!raw->lin_z_w[b] || !raw->lin_z_b[b]) return fail("NULL lin_z pointer");
+    for (int b = 0; b < shape->n_blocks; ++b)
+        if (!raw->fc0_w[b] || !raw->fc0_b[b] || !raw->fc1_w[b] || !raw->fc1_b[b]) return fail("NULL block pointer");
+    return DINER_OK;
+}
+
 int64_t diner_mlp_gen_packed_floats(const DinerMlpShape *shape)
 {
     if (!shape) return bad("mlp_gen_packed_floats: shape is NULL");
@@ -695,25 +713,30 @@ int diner_pack_mlp_gen(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, fl
 {
     if (!shape || !raw || !packed_out) return bad("pack_mlp_gen: NULL pointer");
     int rc;
-    if ((rc = gen::check_shape(*shape))) return rc;
-    const int nlz = shape->combine_layer < shape->n_blocks ? shape->combine_layer : shape->n_blocks;
-    if (!raw->lin_in_w || !raw->lin_in_b || !raw->lin_out_w || !raw->lin_out_b) return bad("pack_mlp_gen: NULL weight pointer");
-    if ((nlz && (!raw->lin_z_w || !raw->lin_z_b)) || !raw->fc0_w || !raw->fc0_b || !raw->fc1_w || !raw->fc1_b) return bad("pack_mlp_gen: NULL layer array");
-    for (int b = 0; b < nlz; ++b)
-        if (!raw->lin_z_w[b] || !raw->lin_z_b[b]) return bad("pack_mlp_gen: NULL lin_z pointer");
-    for (int b = 0; b < shape->n_blocks; ++b)
-        if (!raw->fc0_w[b] || !raw->fc0_b[b] || !raw->fc1_w[b] || !raw->fc1_b[b]) return bad("pack_mlp_gen: NULL block pointer");
+    if ((rc = gen::check_shape(*shape)) || (rc = check_gen_raw(shape, raw, "pack_mlp_gen"))) return rc;
     return gen::launch_pack_mlp(*shape, *raw, packed_out, (hipStream_t)stream);
 }
 
-int diner_render_points_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, const float *z,
-                            int64_t NR, int32_t K, float *rgbsigma_out, void *stream)
+int64_t diner_mlp_gen_f16_packed_floats(const DinerMlpShape *shape)
 {
-    return diner_render_points_gen_ix(scene, nullptr, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream);
+    if (!shape) return bad("mlp_gen_f16_packed_floats: shape is NULL");
+    const int rc = gen::check_shape(*shape);
+    return rc ? rc : genf16::packed_floats(*shape);
 }
 
-int diner_render_points_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
-                               const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)
+int diner_pack_mlp_gen_f16(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, float *packed_out, void *stream)
+{
+    if (!shape || !raw || !packed_out) return bad("pack_mlp_gen_f16: NULL pointer");
+    if ((uintptr_t)packed_out % 16) return bad("pack_mlp_gen_f16: packed_out not 16-byte aligned");
+    int rc;
+    if ((rc = gen::check_shape(*shape)) || (rc = check_gen_raw(shape, raw, "pack_mlp_gen_f16"))) return rc;
+    return genf16::launch_pack_mlp(*shape, *raw, packed_out, (hipStream_t)stream);
+}
+
+/* the three stages of a shape-general render, on the fp32 (f16 = false) or the f16x3 (f16 = true) point kernel */
+static int render_points_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
+                             const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out,
+                             void *stream)
 {
     int rc;
     if (!shape) return bad("render_points_gen: shape is NULL");
@@ -722,22 +745,16 @@ int diner_render_points_gen_ix(const DinerScene *scene, const DinerLatentIndex *
     if ((rc = check_scene(scene, shape->combine_layer > 0))) return rc;
     if (NR < 0 || K < 1) return bad("render_points_gen: bad NR / K");
     if (!mlp_packed) return bad("render_points_gen: mlp_packed is NULL");
+    if (f16 && (uintptr_t)mlp_packed % 16) return bad("render_points_gen_f16: mlp_packed not 16-byte aligned");
     if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points_gen: NULL rays / z / out");
-    return gen::launch_points_mlp(*scene, index ? *index : k_default_index, *shape, mlp_packed, rays, z, NR, K, rgbsigma_out, (hipStream_t)stream);
+    return (f16 ? genf16::launch_points_mlp : gen::launch_points_mlp)(*scene, index ? *index : k_default_index, *shape, mlp_packed, rays, z,
+                                                                       NR, K, rgbsigma_out, (hipStream_t)stream);
 }
 
-int diner_render_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, int64_t NR,
-                     const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss, const float *u_fill,
-                     uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
-{
-    return diner_render_gen_ix(scene, nullptr, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss, u_fill, seed, workspace, rgb_out,
-                               depth_out, weights_out, status, stream);
-}
-
-int diner_render_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
-                        const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
-                        const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
-                        float *weights_out, uint32_t *status, void *stream)
+static int render_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                      const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                      const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                      float *weights_out, uint32_t *status, void *stream)
 {
     int rc;
     if (!shape) return bad("render_gen: shape is NULL");
@@ -749,21 +766,14 @@ int diner_render_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, 
     const int64_t N = (int64_t)scene->SB * NR;
     float *z = workspace, *rgbsigma = workspace + N * cfg->n_samples;
     if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr, nullptr, stream))) return rc;
-    if ((rc = diner_render_points_gen_ix(scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
-int diner_render_image_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const DinerTargetCam *cam,
-                           const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out, float *rgb_out,
-                           float *depth_out, float *weights_out, uint32_t *status, void *stream)
-{
-    return diner_render_image_gen_ix(scene, nullptr, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace, rays_out, rgb_out, depth_out,
-                                     weights_out, status, stream);
-}
-
-int diner_render_image_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
-                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
-                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream)
+static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
+                            const float *mlp_packed, const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd,
+                            uint64_t seed, float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
+                            uint32_t *status, void *stream)
 {
     int rc;
     if (!shape) return bad("render_image_gen: shape is NULL");
@@ -779,8 +789,58 @@ int diner_render_image_gen_ix(const DinerScene *scene, const DinerLatentIndex *i
     if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
                              (hipStream_t)stream)))
         return rc;
-    if ((rc = diner_render_points_gen_ix(scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
+
+#define DINER_GEN_ENTRY_POINTS(SUFFIX, F16)                                                                                                  \
+    int diner_render_points_gen##SUFFIX(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,     \
+                                        const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)                            \
+    {                                                                                                                                        \
+        return render_points_gen(F16, scene, nullptr, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream);                              \
+    }                                                                                                                                        \
+    int diner_render_points_gen##SUFFIX##_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,             \
+                                             const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K,              \
+                                             float *rgbsigma_out, void *stream)                                                              \
+    {                                                                                                                                        \
+        return render_points_gen(F16, scene, index, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream);                                \
+    }                                                                                                                                        \
+    int diner_render_gen##SUFFIX(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,            \
+                                 int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss,    \
+                                 const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,                     \
+                                 float *weights_out, uint32_t *status, void *stream)                                                         \
+    {                                                                                                                                        \
+        return render_gen(F16, scene, nullptr, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss, u_fill, seed, workspace,     \
+                          rgb_out, depth_out, weights_out, status, stream);                                                                  \
+    }                                                                                                                                        \
+    int diner_render_gen##SUFFIX##_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,                    \
+                                      const float *mlp_packed, const float *rays, int64_t NR, const DinerSamplerCfg *cfg,                    \
+                                      int32_t white_bkgd, const float *u_coarse, const float *n_gauss, const float *u_fill, uint64_t seed,   \
+                                      float *workspace, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status,              \
+                                      void *stream)                                                                                          \
+    {                                                                                                                                        \
+        return render_gen(F16, scene, index, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss, u_fill, seed, workspace,       \
+                          rgb_out, depth_out, weights_out, status, stream);                                                                  \
+    }                                                                                                                                        \
+    int diner_render_image_gen##SUFFIX(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed,                         \
+                                       const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed,             \
+                                       float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,              \
+                                       uint32_t *status, void *stream)                                                                       \
+    {                                                                                                                                        \
+        return render_image_gen(F16, scene, nullptr, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace, rays_out, rgb_out,            \
+                                depth_out, weights_out, status, stream);                                                                     \
+    }                                                                                                                                        \
+    int diner_render_image_gen##SUFFIX##_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,              \
+                                            const float *mlp_packed, const DinerTargetCam *cam, const DinerSamplerCfg *cfg,                  \
+                                            int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out, float *rgb_out,            \
+                                            float *depth_out, float *weights_out, uint32_t *status, void *stream)                            \
+    {                                                                                                                                        \
+        return render_image_gen(F16, scene, index, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace, rays_out, rgb_out, depth_out,   \
+                                weights_out, status, stream);                                                                                \
+    }
+
+DINER_GEN_ENTRY_POINTS(, false)
+DINER_GEN_ENTRY_POINTS(_f16, true)
+#undef DINER_GEN_ENTRY_POINTS
 
 }  // extern "C"

@@ -198,7 +198,7 @@ class NeRFRendererDGS(torch.nn.Module):
     """
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000,
-                 white_bkgd=True, train_any_shape=False):
+                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False):
         super().__init__()
         self.n_samples = n_samples
         self.n_depth_candidates = n_depth_candidates
@@ -236,7 +236,7 @@ class NeRFRendererDGS(torch.nn.Module):
         self._mlp_pack = None
         # Models of any other shape (MlpShape) run on the shape-general fp32 kernel (points_mlp_gen.hip) through the *_gen entry
         # points, always through ctypes.  After every inference call: `last_route` = the point kernel that ran ("points_mlp_f16",
-        # "points_mlp" or "points_mlp_gen"), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
+        # "points_mlp", "points_mlp_gen" or "points_mlp_gen_f16"), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
         self._mlp_gen_key = self._mlp_gen_pack = None
         self.last_route = self.last_binding = self.effective_precision = None
         self._warned_precision = False
@@ -246,6 +246,13 @@ class NeRFRendererDGS(torch.nn.Module):
         # as before.  A plain attribute, so that a config can set it (renderer.kwargs.train_any_shape).
         self.train_any_shape = bool(train_any_shape)
         self._force_gen_train = False   # test-only: train the standard shape on that path as well
+        # Inference of a non-standard model in f16x3: with precision == "f16x3" such a model takes the shape-general split-fp16 kernel
+        # (points_mlp_gen_f16.hip, last_route "points_mlp_gen_f16", effective_precision "f16x3", no warning) instead of the exact fp32
+        # one.  Opt-in: when False the model runs in fp32 behind the precision warning, as before.  The standard model keeps its own
+        # kernels and training stays exact fp32 either way.  A plain attribute, so that a config can set it
+        # (renderer.kwargs.f16x3_any_shape).
+        self.f16x3_any_shape = bool(f16x3_any_shape)
+        self._mlp_gen_f16_key = self._mlp_gen_f16_pack = None
         # render_image under autograd: rays per chunk of its backward, which re-runs the training path chunk by chunk (peak memory = one
         # chunk's training footprint + the frame's saved rays, samples and outputs).  A plain attribute, so that a config can set it.
         self.grad_chunk_rays = 4096
@@ -334,10 +341,13 @@ class NeRFRendererDGS(torch.nn.Module):
             return None
         return _lib.DinerLatentIndex(_lib.INDEX_INTERP[interp], _lib.INDEX_PADDING[padding])
 
-    def _route(self, model) -> MlpShape:
-        """validate ``model``; for a shape that takes the shape-general kernel, settle the precision (fp32 is what runs)"""
+    def _route(self, model, f16_ok=True) -> MlpShape:
+        """validate ``model``; for a shape that takes a shape-general kernel, settle the precision (fp32 is what runs, unless
+        f16x3_any_shape sends this inference call -- ``f16_ok`` -- to the split-fp16 kernel)"""
         shape = self._validate_model(model)
-        if self._use_gen(shape):
+        if f16_ok and self._use_gen_f16(shape):
+            self.effective_precision = "f16x3"
+        elif self._use_gen(shape):
             self._settle_fp32(shape, stacklevel=4)
         else:
             self.effective_precision = self.precision
@@ -353,6 +363,15 @@ class NeRFRendererDGS(torch.nn.Module):
 
     def _use_gen(self, shape: MlpShape) -> bool:
         return self._force_gen or not shape.standard
+
+    def _use_gen_f16(self, shape: MlpShape) -> bool:
+        """inference of a non-standard model on the shape-general f16x3 kernel (f16x3_any_shape) instead of the fp32 one"""
+        return bool(self.f16x3_any_shape) and self.precision == "f16x3" and not shape.standard and not self._force_gen
+
+    def _gen_entry(self, name: str, f16: bool):
+        """the C entry point ``diner_<name>`` of the shape-general path, its _f16 form for the split-fp16 kernel: -> (function, its name)"""
+        full = "diner_" + (name.replace("_gen", "_gen_f16") if f16 else name)
+        return getattr(_lib.lib(), full), full
 
     def _use_gen_train(self, shape: MlpShape) -> bool:
         return self._force_gen_train or (self.train_any_shape and not shape.standard)
@@ -442,7 +461,7 @@ class NeRFRendererDGS(torch.nn.Module):
         nb = lambda t: 0 if t is None else t.numel() * t.element_size()
         maps = self._maps_pack[0] if self._maps_pack is not None else None
         rep = {"cached": {"maps": nb(maps), "latent_nhwc": nb(self._latent_pack), "linz_maps": nb(self._linz_pack), "mlp_packed": nb(self._mlp_pack),
-                         "mlp_gen_packed": nb(self._mlp_gen_pack)}}
+                         "mlp_gen_packed": nb(self._mlp_gen_pack), "mlp_gen_f16_packed": nb(self._mlp_gen_f16_pack)}}
         rep["cached"]["total"] = sum(rep["cached"].values())
         rep["linz_maps_max_bytes"] = self.linz_maps_max_bytes
         if rays_per_call is not None:
@@ -483,8 +502,9 @@ class NeRFRendererDGS(torch.nn.Module):
             self._mlp_gen += 1
         return self._mlp_pack
 
-    def _mlp_shape_general(self, model, shape: MlpShape) -> torch.Tensor:
-        """the packed image of diner_pack_mlp_gen, cached like _mlp() (and on the shape)"""
+    def _mlp_shape_general(self, model, shape: MlpShape, f16=False) -> torch.Tensor:
+        """the packed image of diner_pack_mlp_gen (``f16``: of diner_pack_mlp_gen_f16, in a cache of its own), cached like _mlp() (and
+        on the shape)"""
         mlp = model.mlp_fine
         nlz = min(shape.combine_layer, shape.n_blocks)
         params = [mlp.lin_in.weight, mlp.lin_in.bias, mlp.lin_out.weight, mlp.lin_out.bias]
@@ -492,7 +512,8 @@ class NeRFRendererDGS(torch.nn.Module):
             params += [mlp.lin_z[b].weight, mlp.lin_z[b].bias]
         for b in range(shape.n_blocks):
             params += [mlp.blocks[b].fc_0.weight, mlp.blocks[b].fc_0.bias, mlp.blocks[b].fc_1.weight, mlp.blocks[b].fc_1.bias]
-        if self._mlp_gen_key is None or self._mlp_gen_key[0] != shape or not self._mlp_gen_key[1].valid_for(params):
+        key = self._mlp_gen_f16_key if f16 else self._mlp_gen_key
+        if key is None or key[0] != shape or not key[1].valid_for(params):
             keep = [_f32c(p) for p in params]
             ptrs = [t.data_ptr() for t in keep]
             arr = lambda xs: (C.c_void_p * max(1, len(xs)))(*xs)
@@ -501,15 +522,20 @@ class NeRFRendererDGS(torch.nn.Module):
             pp = lambda a: C.cast(a, C.POINTER(C.c_void_p))
             raw = _lib.DinerMlpGenRaw(ptrs[0], ptrs[1], *[pp(a) for a in arrays], ptrs[2], ptrs[3])
             cs = shape.c_struct()
-            n = int(_lib.lib().diner_mlp_gen_packed_floats(C.byref(cs)))
+            size_fn, size_name = self._gen_entry("mlp_gen_packed_floats", f16)
+            pack_fn, pack_name = self._gen_entry("pack_mlp_gen", f16)
+            n = int(size_fn(C.byref(cs)))
             if n < 0:
-                check(n, "diner_mlp_gen_packed_floats")
+                check(n, size_name)
             dev = keep[0].device
             packed = torch.empty(n, dtype=torch.float32, device=dev)
-            check(_lib.lib().diner_pack_mlp_gen(C.byref(cs), C.byref(raw), _ptr(packed), _stream(dev)), "diner_pack_mlp_gen")
+            check(pack_fn(C.byref(cs), C.byref(raw), _ptr(packed), _stream(dev)), pack_name)
             torch.cuda.current_stream(dev).synchronize()  # `keep` may be temporaries: finish before they die
-            self._mlp_gen_pack, self._mlp_gen_key = packed, (shape, _Sources(params))
-        return self._mlp_gen_pack
+            if f16:
+                self._mlp_gen_f16_pack, self._mlp_gen_f16_key = packed, (shape, _Sources(params))
+            else:
+                self._mlp_gen_pack, self._mlp_gen_key = packed, (shape, _Sources(params))
+        return self._mlp_gen_f16_pack if f16 else self._mlp_gen_pack
 
     # ------------------------------------------------------------------------------------------
     # non-finite guard
@@ -626,18 +652,19 @@ class NeRFRendererDGS(torch.nn.Module):
         SB, NR, K = z.shape
         shape = self._route(model)
         if self._use_gen(shape):
-            packed = self._mlp_shape_general(model, shape)
+            f16 = self._use_gen_f16(shape)
+            packed = self._mlp_shape_general(model, shape, f16)
             sc, _keep = self._scene(model, need_latent=True)
             assert SB == sc.SB
             out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
             cs, ix = shape.c_struct(), self._latent_index(model)
             if ix is None:
-                check(_lib.lib().diner_render_points_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out),
-                                                         _stream(r.device)), "diner_render_points_gen")
+                fn, name = self._gen_entry("render_points_gen", f16)
+                check(fn(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
             else:
-                check(_lib.lib().diner_render_points_gen_ix(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K,
-                                                            _ptr(out), _stream(r.device)), "diner_render_points_gen_ix")
-            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+                fn, name = self._gen_entry("render_points_gen_ix", f16)
+                check(fn(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
+            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
             return out
         packed = self._mlp(model)
         sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
@@ -797,7 +824,8 @@ class NeRFRendererDGS(torch.nn.Module):
         K = int(self.n_samples)
         dev = r.device
         big = want_weights or SB * NR > int(self.finite_sync_rays)
-        packed = self._mlp_shape_general(model, shape)
+        f16 = self._use_gen_f16(shape)
+        packed = self._mlp_shape_general(model, shape, f16)
         sc, _keep = self._scene(model, need_latent=True)
         assert SB == sc.SB
         cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
@@ -815,13 +843,13 @@ class NeRFRendererDGS(torch.nn.Module):
         weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
         if self.stage_events is None:
             if ix is None:
-                check(L.diner_render_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st),
-                      "diner_render_gen")
+                fn, name = self._gen_entry("render_gen", f16)
+                check(fn(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
             else:
-                check(L.diner_render_gen_ix(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                                            _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status,
-                                            st), "diner_render_gen_ix")
+                fn, name = self._gen_entry("render_gen_ix", f16)
+                check(fn(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
         else:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
@@ -829,15 +857,15 @@ class NeRFRendererDGS(torch.nn.Module):
             check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
                                              None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
             ev[1].record()
-            check(L.diner_render_points_gen_ix(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st),
-                  "diner_render_points_gen_ix")
+            fn, name = self._gen_entry("render_points_gen_ix", f16)
+            check(fn(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st), name)
             ev[2].record()
             check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
                                     _ptr(depth), _ptr(weights), status, st), "diner_composite")
             ev[3].record()
             self.stage_events.append(ev)
         self._after_launch(dev, sync=big)
-        self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+        self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False):
@@ -875,15 +903,16 @@ class NeRFRendererDGS(torch.nn.Module):
         """render_image's inference launch.  ``saved`` (a dict): take the ctypes binding (the torch op gives no access to its workspace)
         and hand out the generated rays [SB,H*W,8], the samples the compositing used [SB,H*W,K] (workspace layout rays | z | ..., here
         z only: the rays go to rays_out) and the flat rgb [SB,H*W,3] / depth [SB,H*W]."""
-        shape = self._route(model)
+        shape = self._route(model, f16_ok=saved is None)   # under autograd (``saved``) the frame is the training path's: exact fp32
         gen = self._use_gen(shape)
+        f16 = saved is None and self._use_gen_f16(shape)
         dev = target_extrinsics.device
         SB = target_extrinsics.shape[0]
         E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
         zn = torch.as_tensor(z_near, dtype=torch.float32, device=dev).expand(SB).contiguous()
         zf = torch.as_tensor(z_far, dtype=torch.float32, device=dev).expand(SB).contiguous()
         if gen:
-            packed = self._mlp_shape_general(model, shape)
+            packed = self._mlp_shape_general(model, shape, f16)
             sc, _keep = self._scene(model, need_latent=True)
         else:
             packed = self._mlp(model)
@@ -906,20 +935,20 @@ class NeRFRendererDGS(torch.nn.Module):
                              dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            check(L.diner_render_image_gen_ix(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg),
-                                              int(bool(self.white_bkgd)), seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None,
-                                              _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image_gen_ix")
-            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+            fn, name = self._gen_entry("render_image_gen_ix", f16)
+            check(fn(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed,
+                     _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), name)
+            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
         elif gen:
             cs = shape.c_struct()
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
                              dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            check(L.diner_render_image_gen(C.byref(sc), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)),
-                                           seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
-                  "diner_render_image_gen")
-            self.last_route, self.last_binding = "points_mlp_gen", "ctypes"
+            fn, name = self._gen_entry("render_image_gen", f16)
+            check(fn(C.byref(sc), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed, _ptr(ws),
+                     _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), name)
+            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
         elif ix is not None:
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, prec)), dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)

@@ -116,7 +116,7 @@ typedef struct DinerLatentIndex {
  * torch-ops extension checks it at every op entry, diner_amd/_lib.py at load time.  (2: diner_render / diner_composite gained
  * `status`.  3: the shape-general inference path, the *_gen entry points below.)  New entry points that leave every existing argument
  * list and struct layout as it was do not bump it (the shape-general training blocks, diner_train_gemm_act and
- * diner_train_point_inputs(_backward)_gen, came under 3). */
+ * diner_train_point_inputs(_backward)_gen, and the shape-general f16x3 inference path, the *_gen_f16 entry points, came under 3). */
 #define DINER_ABI_VERSION 3
 
 const char *diner_last_error(void);
@@ -319,6 +319,43 @@ int diner_render_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, 
 int diner_render_image_gen_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
                               const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
                               float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
+
+/* ---- shape-general inference path in split fp16 (points_mlp_gen_f16.hip) -----------------------------------------------------
+ * The *_gen entry points above with the arithmetic of DINER_PRECISION_F16X3 (three fp16 MFMAs per product on hi / lo operand halves,
+ * fp32 accumulation, the hidden state carried * 2^-4; an activation beyond the fp16 range makes the sample non-finite and
+ * diner_composite raises DINER_STATUS_NONFINITE): same envelope, same DinerMlpShape / DinerMlpGenRaw, same argument lists, inference
+ * only.  The packed image is another one: fp16 hi / lo weight fragments followed by fp32 biases and lin_out, 16-byte aligned.
+ * diner_mlp_gen_f16_packed_floats / diner_pack_mlp_gen_f16 replace what ResnetFC.__init__ / load_state_dict leave in nn.Linear
+ * layout (src/models/resnetfc.py:72-127), as diner_pack_mlp_gen does. */
+int64_t diner_mlp_gen_f16_packed_floats(const DinerMlpShape *shape);   /* < 0: the DINER_E_* code of an unsupported shape */
+int diner_pack_mlp_gen_f16(const DinerMlpShape *shape, const DinerMlpGenRaw *raw, float *packed_out, void *stream);
+/* Replaces PixelNeRF.forward + ResnetFC.forward per point (src/models/pixelnerf.py:55-145, src/models/resnetfc.py:129-159), as
+ * diner_render_points_gen does; mlp_packed from diner_pack_mlp_gen_f16 */
+int diner_render_points_gen_f16(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,
+                                const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream);
+/* Replace NeRFRendererDGS.forward (src/models/nerf_renderer.py:399-424) and the render half of DINER.predict_imgs_from_batch
+ * (src/models/diner.py:75-97), as diner_render_gen / diner_render_image_gen do.  workspace: diner_render_workspace_floats /
+ * diner_render_image_workspace_floats with DINER_PRECISION_FP32 (this kernel needs no scratch beyond z and rgbsigma; the
+ * DINER_PRECISION_F16X3 size is that of the standard kernel's view-sum slabs and is not needed here) */
+int diner_render_gen_f16(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays, int64_t NR,
+                         const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss,
+                         const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out,
+                         uint32_t *status, void *stream);
+int diner_render_image_gen_f16(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const DinerTargetCam *cam,
+                               const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace, float *rays_out,
+                               float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
+/* the same with a latent lookup mode (NULL = bilinear / border; SpatialEncoder.index, src/models/image_encoder.py:97-127) */
+int diner_render_points_gen_f16_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
+                                   const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K,
+                                   float *rgbsigma_out, void *stream);
+int diner_render_gen_f16_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                            const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                            const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out,
+                            float *depth_out, float *weights_out, uint32_t *status, void *stream);
+int diner_render_image_gen_f16_ix(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
+                                  const float *mlp_packed, const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd,
+                                  uint64_t seed, float *workspace, float *rays_out, float *rgb_out, float *depth_out,
+                                  float *weights_out, uint32_t *status, void *stream);
 
 /* ---- training path: building blocks of the forward-with-saved-activations and
  * the backward of composite (src/models/nerf_renderer.py:286-365) + PixelNeRF.forward

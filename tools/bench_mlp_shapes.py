@@ -1,9 +1,11 @@
-"""Throughput of the shape-general inference path (points_mlp_gen.hip) on one GPU: rays/s of a whole 512 x 512 frame through
+"""Throughput of the shape-general inference path (points_mlp_gen.hip; --precision f16x3: points_mlp_gen_f16.hip) on one GPU: rays/s of a whole 512 x 512 frame through
 NeRFRendererDGS.forward for a non-standard model, with the event time of each stage (sampler | generic point kernel | compositing).
 A record, not a gate.  Default: case (a) of tools/gen_shape_golden.py (d_hidden 128, 5 blocks, combine_layer 3) at K = 40,
-NV = 2, the reference's renderer defaults otherwise.
+NV = 2, the reference's renderer defaults otherwise.  --num_freqs other than 6 keeps a model with the standard ResnetFC (d_hidden 512,
+5 blocks, combine_layer 3) on the shape-general route.
 
-    python tools/bench_mlp_shapes.py [--res 512] [--K 40] [--NV 2] [--d_hidden 128] [--steps 5] [--warmup 2]
+    python tools/bench_mlp_shapes.py [--res 512] [--K 40] [--NV 2] [--d_hidden 128] [--num_freqs 6] [--precision fp32|f16x3]
+                                     [--steps 5] [--warmup 2]
 """
 from __future__ import annotations
 
@@ -26,6 +28,9 @@ def main():
     ap.add_argument("--d_hidden", type=int, default=128)
     ap.add_argument("--n_blocks", type=int, default=5)
     ap.add_argument("--combine_layer", type=int, default=3)
+    ap.add_argument("--num_freqs", type=int, default=6)
+    ap.add_argument("--precision", choices=["fp32", "f16x3"], default="fp32",
+                    help="fp32: points_mlp_gen (exact fp32 MFMA); f16x3: points_mlp_gen_f16 (renderer.f16x3_any_shape)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     a = ap.parse_args()
@@ -42,11 +47,13 @@ def main():
     h, w = sc.latent_hw
     g = torch.Generator(device=dev).manual_seed(1)
     latent = torch.randn((1, a.NV, 512, h, w), device=dev, generator=g)
-    m = model_from_scene(sc, synth.make_mlp_weights(1, bias_scale=0.1, **dims), device=dev, latent=latent, **dims)
+    m = model_from_scene(sc, synth.make_mlp_weights(1, bias_scale=0.1, d_in=7 + 8 * a.num_freqs, **dims), device=dev, latent=latent,
+                         num_freqs=a.num_freqs, **dims)
     rays = torch.from_numpy(np.ascontiguousarray(sc.target_rays())).to(dev)
     NR = rays.shape[1]
-    r = NeRFRendererDGS(n_samples=a.K, n_gaussian=a.G, white_bkgd=sc.white_bkgd)
-    r.precision = "fp32"
+    r = NeRFRendererDGS(n_samples=a.K, n_gaussian=a.G, white_bkgd=sc.white_bkgd, f16x3_any_shape=a.precision == "f16x3")
+    r.precision = a.precision
+    route = "points_mlp_gen_f16" if a.precision == "f16x3" else "points_mlp_gen"
     with torch.no_grad():
         for _ in range(a.warmup):
             r(m, rays)
@@ -55,10 +62,10 @@ def main():
         for _ in range(a.steps):
             r(m, rays)
         torch.cuda.synchronize()
-    assert r.last_route == "points_mlp_gen"
+    assert r.last_route == route and r.effective_precision == a.precision, (r.last_route, r.effective_precision)
     st = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(3)] for ev in r.stage_events])   # ms
     frame = float(np.median(st.sum(1)))
-    print(json.dumps(dict(path="points_mlp_gen", d_hidden=a.d_hidden, n_blocks=a.n_blocks, combine_layer=a.combine_layer, NV=a.NV, K=a.K,
+    print(json.dumps(dict(path=route, precision=a.precision, num_freqs=a.num_freqs, d_hidden=a.d_hidden, n_blocks=a.n_blocks, combine_layer=a.combine_layer, NV=a.NV, K=a.K,
                           rays=NR, steps=a.steps, rays_per_s=NR / (frame / 1e3), frame_ms=frame,
                           sampler_ms=float(np.median(st[:, 0])), points_mlp_gen_ms=float(np.median(st[:, 1])),
                           composite_ms=float(np.median(st[:, 2])),
