@@ -167,6 +167,13 @@ SYMBOLS = {
                                                _P, _P, _P]),
     "diner_train_point_inputs_backward_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, _P, _P, _I64, _I32, _I32,
                                                         _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the shape-general f16x3 training GEMM (train_gen_f16.hip; the ABI version stays 3: new entry points only)
+    "diner_train_gemm_act_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32,
+                                             C.c_float, _I32, _I32, _I64, _P, _P, _I32, _I32, _P]),
+    "diner_train_split_weight_halfs": (_I64, [_I32, _I32]),
+    "diner_train_split_weight": (C.c_int, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P]),
+    "diner_train_gemm_act_f16x3_w": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, C.c_float, _I32, _P,
+                                               _I32, _I32, _P]),
 }
 
 _lib = None

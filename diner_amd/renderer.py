@@ -198,7 +198,7 @@ class NeRFRendererDGS(torch.nn.Module):
     """
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000,
-                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False):
+                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False, train_f16x3_any_shape=False):
         super().__init__()
         self.n_samples = n_samples
         self.n_depth_candidates = n_depth_candidates
@@ -253,6 +253,13 @@ class NeRFRendererDGS(torch.nn.Module):
         # (renderer.kwargs.f16x3_any_shape).
         self.f16x3_any_shape = bool(f16x3_any_shape)
         self._mlp_gen_f16_key = self._mlp_gen_f16_pack = None
+        # Training of a non-standard model in f16x3: together with train_any_shape and precision == "f16x3" the shape-general training
+        # path runs its GEMMs in the split-fp16 arithmetic of the standard path (csrc/train_gen_f16.hip, last_route "train_gen_f16",
+        # effective_precision "f16x3", no warning) instead of exact fp32.  Opt-in: when False that path trains in fp32 behind the
+        # precision warning, as before.  A plain attribute, so that a config can set it (renderer.kwargs.train_f16x3_any_shape).
+        self.train_f16x3_any_shape = bool(train_f16x3_any_shape)
+        from .training_gen import WeightSplitCache
+        self._weight_split_cache = WeightSplitCache()   # that path's pre-split weights, per parameter version
         # render_image under autograd: rays per chunk of its backward, which re-runs the training path chunk by chunk (peak memory = one
         # chunk's training footprint + the frame's saved rays, samples and outputs).  A plain attribute, so that a config can set it.
         self.grad_chunk_rays = 4096
@@ -375,6 +382,10 @@ class NeRFRendererDGS(torch.nn.Module):
 
     def _use_gen_train(self, shape: MlpShape) -> bool:
         return self._force_gen_train or (self.train_any_shape and not shape.standard)
+
+    def _use_gen_train_f16(self, shape: MlpShape) -> bool:
+        """the shape-general training path in f16x3 (train_f16x3_any_shape) instead of exact fp32"""
+        return self._use_gen_train(shape) and bool(self.train_f16x3_any_shape) and self.precision == "f16x3"
 
     @staticmethod
     def _gen_training_unsupported(shape: MlpShape):
@@ -1004,9 +1015,14 @@ class NeRFRendererDGS(torch.nn.Module):
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     def _forward_train_gen(self, model, rays, want_weights, shape: MlpShape, noise=None, z_samples=None):
-        """_forward_train for a model of any shape of the envelope (train_any_shape): the exact fp32 path of diner_amd/training_gen.py"""
+        """_forward_train for a model of any shape of the envelope (train_any_shape): the path of diner_amd/training_gen.py, in exact fp32
+        or (train_f16x3_any_shape) in f16x3"""
         from . import training_gen
-        self._settle_fp32(shape, stacklevel=4)
+        f16 = self._use_gen_train_f16(shape)
+        if f16:
+            self.effective_precision = "f16x3"
+        else:
+            self._settle_fp32(shape, stacklevel=4)
         r = self._check_rays(rays)
         SB, NR, _ = r.shape
         K = int(self.n_samples)
@@ -1020,8 +1036,9 @@ class NeRFRendererDGS(torch.nn.Module):
         lat = model.encoder.latent
         assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == shape.d_latent
         sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
-        rgb, depth, weights = training_gen.render_with_grad(self, model, rays, z, sc, shape, keep=_keep)
-        self.last_route, self.last_binding = "train_gen", "ctypes"
+        kw = dict(f16=True) if f16 else {}   # (the fp32 call keeps the argument list it had)
+        rgb, depth, weights = training_gen.render_with_grad(self, model, rays, z, sc, shape, keep=_keep, **kw)
+        self.last_route, self.last_binding = ("train_gen_f16" if f16 else "train_gen"), "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     # alias asked for by the north_star text; the reference itself has no render_rays

@@ -1,5 +1,5 @@
 """Differentiable render path for any fusion-MLP shape of the shape-general envelope (include/diner_hip.h): the training path of
-``diner_amd/training.py`` for ResnetFC / PositionalEncoding shapes other than the standard one, in exact fp32.
+``diner_amd/training.py`` for ResnetFC / PositionalEncoding shapes other than the standard one, in exact fp32 or (``renderer.train_f16x3_any_shape``) in f16x3.
 
 The reference trains any model its constructors accept (``ResnetFC.from_conf`` reads d_hidden, n_blocks, combine_layer and beta from
 ``mlp_fine_conf``, num_freqs comes from ``poscode_conf``, d_latent from the encoder's ``num_layers``).  This module runs the layer
@@ -8,6 +8,11 @@ blocks of ``diner_amd/csrc/train_gen.hip`` (the fp32 MFMA GEMM with activation c
 and their transpose) plus the shape-agnostic ones of ``train.hip`` (view mean, head, column sums, latent scatter, compositing
 backward).  Gradients: every fusion-MLP parameter, ``encoder.latent``, and the rays, source cameras and depth maps when they require
 grad.  PyTorch supplies buffers and the autograd hook -- no arithmetic of the path.
+
+f16x3 mode (``f16=True``; csrc/train_gen_f16.hip): every GEMM of the graph runs in the split-fp16 arithmetic of the standard path
+(``diner_amd/training.py``): activations scaled by 2^-4 and weights by 2^4, every gradient operand by its measured max|.|; forward and dX
+read the weight pre-split (``WeightSplitCache``, made once per parameter version), dW streams and splits both operands.  Everything else
+(point inputs, view mean, head, scatter, compositing backward, camera reductions) is the same fp32 kernels.
 """
 from __future__ import annotations
 
@@ -18,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .training import CAMERA_INPUTS, camera_leaves
+from .training import CAMERA_INPUTS, EXP_ACT, EXP_W, camera_leaves
 
 K_CHUNK = 4096  # rows per split of the weight-gradient GEMMs (multiple of 32)
 
@@ -45,30 +50,101 @@ def _gemm(A, B, bias, S, Cm, M, N, K, sam, sak, sbk, sbn, ldc, lds, act_a=0, act
                                           beta, accumulate, atomic, k_chunk, _st(Cm.device)), "diner_train_gemm_act")
 
 
-def linear_fwd(X, W, b, out, act=None, accumulate=False):
-    """out[M,N] (+)= act?(X[M,K]) W[N,K]^T + b"""
+class SplitWeight:
+    """fp16 hi / lo planes of a weight operand (``diner_train_split_weight``) for ``diner_train_gemm_act_f16x3_w``"""
+    __slots__ = ("hi", "lo")
+
+    def __init__(self, W, transpose):
+        n, k = (W.shape[1], W.shape[0]) if transpose else (W.shape[0], W.shape[1])
+        halfs = int(_lib.lib().diner_train_split_weight_halfs(n, k))
+        self.hi = torch.empty(halfs, dtype=torch.float16, device=W.device)
+        self.lo = torch.empty(halfs, dtype=torch.float16, device=W.device)
+        check(_lib.lib().diner_train_split_weight(_p(W), n, k, W.stride(0), int(transpose), EXP_W, _p(self.hi), _p(self.lo), _st(W.device)),
+              "diner_train_split_weight")
+
+
+class WeightSplitCache:
+    """``SplitWeight``s of the MLP weights, kept per (parameter object, orientation) and valid for one ``_version`` like
+    ``training.PanelCache``'s panels: re-split only after an in-place update of the parameter, and two models that share a renderer keep
+    their own entries.  Weak references: no parameter is kept alive; entries of dead parameters go when a new one is made."""
+
+    def __init__(self):
+        self._e = {}
+
+    def get(self, src, W, transpose):
+        """planes of ``W`` (``src``'s fp32 contiguous copy, or lin_in's zero-padded one), B[k][n] = W[n][k] or (transpose) W[k][n]"""
+        key = (id(src), bool(transpose))
+        ent = self._e.get(key)
+        if ent is not None and ent[0]() is src and ent[1] == src._version and ent[2] == tuple(W.shape):
+            return ent[3]
+        for k in [k for k, e in self._e.items() if e[0]() is None]:
+            del self._e[k]
+        sw = SplitWeight(W, transpose)
+        self._e[key] = (weakref.ref(src), src._version, tuple(W.shape), sw)
+        return sw
+
+
+def _gemm_w(A, sw, bias, S, Cm, M, N, K, act_a=0, act_s=0, beta=1.0, accumulate=0, amax=None, exp_a=0):
+    check(_lib.lib().diner_train_gemm_act_f16x3_w(_p(A), A.stride(0), _p(sw.hi), _p(sw.lo), _p(bias), _p(S), 0 if S is None else S.stride(0),
+                                                  _p(Cm), Cm.stride(0), M, N, K, act_a, act_s, beta, accumulate, _p(amax), exp_a, EXP_W,
+                                                  _st(Cm.device)), "diner_train_gemm_act_f16x3_w")
+
+
+def linear_fwd(X, W, b, out, act=None, accumulate=False, sw=None):
+    """out[M,N] (+)= act?(X[M,K]) W[N,K]^T + b   (sw: W's SplitWeight -> the f16x3 GEMM)"""
     M, K = X.shape
     N = W.shape[0]
     a = act.code if act is not None else _lib.ACT_NONE
+    if sw is not None:
+        return _gemm_w(X, sw, b, None, out, M, N, K, act_a=a, beta=act.beta if act else 1.0, accumulate=int(accumulate), exp_a=EXP_ACT)
     _gemm(X, W, b, None, out, M, N, K, X.stride(0), 1, 1, W.stride(0), out.stride(0), 0, act_a=a, beta=act.beta if act else 1.0,
           accumulate=int(accumulate))
 
 
-def linear_bwd_x(dY, W, S, out, act=None, accumulate=False):
-    """out[M,K] (+)= (dY[M,N] W[N,K]) * act'(S)   (S None: no derivative)"""
+def linear_bwd_x(dY, W, S, out, act=None, accumulate=False, sw=None, amax=None):
+    """out[M,K] (+)= (dY[M,N] W[N,K]) * act'(S)   (S None: no derivative; sw: W's transposed SplitWeight, amax: max|dY| -> f16x3)"""
     M, N = dY.shape
     K = W.shape[1]
+    a_s = act.code if (act is not None and S is not None) else _lib.ACT_NONE
+    if sw is not None:
+        return _gemm_w(dY, sw, None, S, out, M, K, N, act_s=a_s, beta=act.beta if act else 1.0, accumulate=int(accumulate), amax=amax)
     _gemm(dY, W, None, S, out, M, K, N, dY.stride(0), 1, W.stride(0), 1, out.stride(0), 0 if S is None else S.stride(0),
-          act_s=act.code if (act is not None and S is not None) else _lib.ACT_NONE, beta=act.beta if act else 1.0, accumulate=int(accumulate))
+          act_s=a_s, beta=act.beta if act else 1.0, accumulate=int(accumulate))
 
 
-def linear_bwd_w(dY, X, dW, db, act=None):
-    """dW[N,K] += dY[M,N]^T act?(X[M,K]);  db[N] += sum_m dY (its own column sums)"""
+def linear_bwd_w(dY, X, dW, db, act=None, amax=None):
+    """dW[N,K] += dY[M,N]^T act?(X[M,K]);  db[N] += sum_m dY (its own column sums).  amax (the device word with max|dY|, from
+    ``grad_reduce``, which has summed the columns into db already): the f16x3 GEMM"""
     M, N = dY.shape
     K = X.shape[1]
-    _gemm(dY, X, None, None, dW, N, K, M, 1, dY.stride(0), X.stride(0), 1, dW.stride(0), 0, act_b=act.code if act else _lib.ACT_NONE,
-          beta=act.beta if act else 1.0, atomic=1, k_chunk=K_CHUNK)
-    check(_lib.lib().diner_train_colsum(_p(dY), M, N, dY.stride(0), _p(db), _st(dY.device)), "diner_train_colsum")
+    if amax is not None:
+        check(_lib.lib().diner_train_gemm_act_f16x3(_p(dY), _p(X), None, None, _p(dW), N, K, M, 1, dY.stride(0), X.stride(0), 1, dW.stride(0), 0,
+                                                    _lib.ACT_NONE, act.code if act else _lib.ACT_NONE, _lib.ACT_NONE,
+                                                    act.beta if act else 1.0, 0, 1, K_CHUNK, _p(amax), None, 0, EXP_ACT, _st(dW.device)),
+              "diner_train_gemm_act_f16x3")
+    else:
+        _gemm(dY, X, None, None, dW, N, K, M, 1, dY.stride(0), X.stride(0), 1, dW.stride(0), 0, act_b=act.code if act else _lib.ACT_NONE,
+              beta=act.beta if act else 1.0, atomic=1, k_chunk=K_CHUNK)
+        check(_lib.lib().diner_train_colsum(_p(dY), M, N, dY.stride(0), _p(db), _st(dY.device)), "diner_train_colsum")
+
+
+def grad_reduce(dY, db, f16):
+    """f16x3 mode: db += column sums of dY (a bias gradient) and the device word with max|dY| that scales dY as a GEMM operand -- one
+    pass (``diner_train_colsum_amax``) where the width allows it ((N / 4) | 256), else ``diner_train_amax`` + ``diner_train_colsum``.
+    fp32 mode: nothing, None (``linear_bwd_w`` sums the columns after its GEMM, as before)."""
+    if not f16:
+        return None
+    L = _lib.lib()
+    M, N = dY.shape
+    word = torch.empty(1, dtype=torch.int32, device=dY.device)
+    st = _st(dY.device)
+    if 256 % (N // 4) == 0:
+        check(L.diner_train_colsum_amax(_p(dY), M, N, dY.stride(0), _p(db), _p(word), st), "diner_train_colsum_amax")
+    else:
+        assert dY.is_contiguous()
+        check(L.diner_train_amax(_p(dY), dY.numel(), _p(word), st), "diner_train_amax")
+        check(L.diner_train_colsum(_p(dY), M, N, dY.stride(0), _p(db), st), "diner_train_colsum")
+    return word
 
 
 def mlp_params(mlp):
@@ -107,7 +183,7 @@ class _RenderGenFn(torch.autograd.Function):
     envelope.  Same contract as ``training._RenderFn`` (``cams``: the caller's leaves, whose versions backward() checks)."""
 
     @staticmethod
-    def forward(ctx, renderer, scene, ix, keep, cams, shape, z, rays, latent, poses, focal, c_, image_shape, depths, *params):
+    def forward(ctx, renderer, scene, ix, keep, cams, shape, f16, z, rays, latent, poses, focal, c_, image_shape, depths, *params):
         L = _lib.lib()
         rays = rays.detach()
         dev = rays.device
@@ -129,6 +205,10 @@ class _RenderGenFn(torch.autograd.Function):
         ctx.cam_versions = [(t, t._version) for t in cams]
         w_in = torch.zeros((H, ld_in), dtype=torch.float32, device=dev)   # lin_in's weight, zero-padded to the input's ld_in columns
         w_in[:, :shape.d_in] = prm[0]
+
+        def sw(i):   # f16x3: the pre-split planes of weight i (mlp_params order); None = the fp32 GEMM
+            return renderer._weight_split_cache.get(params[i], w_in if i == 0 else prm[i], False) if f16 else None
+
         rgbsigma = f(SB, NR, K, 4)
         ixp = C.byref(ix) if ix is not None else None
         saved = []
@@ -137,7 +217,7 @@ class _RenderGenFn(torch.autograd.Function):
             check(L.diner_train_point_inputs_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
                                                  _p(taps), st), "diner_train_point_inputs_gen")
             x = f(R, H)
-            linear_fwd(inp, w_in, prm[1], x)                                                   # resnetfc.py:139
+            linear_fwd(inp, w_in, prm[1], x, sw=sw(0))                                                # resnetfc.py:139
             blocks = []
             for b in range(lay.nb):
                 if b == lay.cl:                                                                # :146-149 (mean over views)
@@ -145,16 +225,16 @@ class _RenderGenFn(torch.autograd.Function):
                     check(L.diner_train_view_mean(_p(x), P * H, NV, _p(xbar), 0, st), "diner_train_view_mean")
                     x = xbar
                 if b < lay.cl:                                                                 # :151-153, x += lin_z[b](z) in place
-                    linear_fwd(zl, prm[lay.lz(b)], prm[lay.lz(b) + 1], x, accumulate=True)
+                    linear_fwd(zl, prm[lay.lz(b)], prm[lay.lz(b) + 1], x, accumulate=True, sw=sw(lay.lz(b)))
                 i = lay.blk(b)
                 net = torch.empty_like(x)
-                linear_fwd(x, prm[i], prm[i + 1], net, act=act)                                # :62
+                linear_fwd(x, prm[i], prm[i + 1], net, act=act, sw=sw(i))                             # :62
                 y = x.clone()
-                linear_fwd(net, prm[i + 2], prm[i + 3], y, act=act, accumulate=True)           # :63, :69
+                linear_fwd(net, prm[i + 2], prm[i + 3], y, act=act, accumulate=True, sw=sw(i + 2))         # :63, :69
                 blocks.append((x, net))
                 x = y
             out = f(x.shape[0], 4)
-            linear_fwd(x, prm[lay.out], prm[lay.out + 1], out, act=act)                       # :158
+            linear_fwd(x, prm[lay.out], prm[lay.out + 1], out, act=act, sw=sw(lay.out))                    # :158
             check(L.diner_train_head(_p(out), None, None, P * 4, _p(rgbsigma[sb]), 0, st), "diner_train_head")  # pixelnerf.py:139-143
             saved.append((inp, zl, taps, blocks, x, out))
         N = SB * NR
@@ -165,6 +245,7 @@ class _RenderGenFn(torch.autograd.Function):
         ctx.saved_acts, ctx.prm, ctx.w_in, ctx.lat_shape = saved, prm, w_in, tuple(latent.shape)
         ctx.keep = (lat, lat_nhwc, keep)
         ctx.shape, ctx.ix = shape, ix
+        ctx.f16, ctx.params = bool(f16), params
         ctx.cam_shapes = [tuple(t.shape) for t in (poses, focal, c_, image_shape, depths)]
         return rgb, depth, weights
 
@@ -176,8 +257,8 @@ class _RenderGenFn(torch.autograd.Function):
                 raise RuntimeError("diner_amd.training_gen: one of the variables needed for gradient computation (an MLP parameter, "
                                    "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
                                    "between forward and backward")
-        # which geometric leaves want a gradient (inputs 7 and 9..13: rays, poses, focal, c, image_shape, depths)
-        want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[7],) + tuple(ctx.needs_input_grad[9:14])))
+        # which geometric leaves want a gradient (inputs 8 and 10..14: rays, poses, focal, c, image_shape, depths)
+        want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[8],) + tuple(ctx.needs_input_grad[10:15])))
         cam_any = any(want.values())
         scene, rays, z, rgbsigma, prm, shape = ctx.scene, ctx.rays, ctx.z, ctx.rgbsigma, ctx.prm, ctx.shape
         lay, act = _Layout(shape), Act(shape.beta)
@@ -218,42 +299,52 @@ class _RenderGenFn(torch.autograd.Function):
         g_in = torch.zeros_like(ctx.w_in)
         SBl, NVl, Cl, hl, wl = ctx.lat_shape
         d_lat_nhwc = torch.zeros((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
+        f16 = ctx.f16   # f16x3: every gradient operand is scaled by its measured max|.| (grad_reduce), dX reads the transposed planes
+
+        def swt(i):
+            return ctx.renderer._weight_split_cache.get(ctx.params[i], ctx.w_in if i == 0 else prm[i], True) if f16 else None
+
         for sb in range(SB):
             inp, zl, taps, blocks, x_last, out = ctx.saved_acts[sb]
             out_rows = x_last.shape[0]
             d_out = f(out_rows, 4)
             check(L.diner_train_head(_p(out), _p(rgbsigma[sb]), _p(d_rgbsigma[sb]), P * 4, _p(d_out), 1, st), "diner_train_head(bwd)")
-            linear_bwd_w(d_out, x_last, g[lay.out], g[lay.out + 1], act=act)                  # lin_out
+            a_out = grad_reduce(d_out, g[lay.out + 1], f16)
+            linear_bwd_w(d_out, x_last, g[lay.out], g[lay.out + 1], act=act, amax=a_out)  # lin_out
             d_x = f(out_rows, H)
-            linear_bwd_x(d_out, prm[lay.out], x_last, d_x, act=act)
+            linear_bwd_x(d_out, prm[lay.out], x_last, d_x, act=act, sw=swt(lay.out), amax=a_out)
             d_zl = torch.zeros((R, scene.C), dtype=torch.float32, device=dev) if (lay.nlz == 0 and cam_any) else None
             for b in reversed(range(lay.nb)):
                 xb, net = blocks[b]
                 i = lay.blk(b)
                 d_y = d_x                                                                      # gradient of the block's output
-                linear_bwd_w(d_y, net, g[i + 2], g[i + 3], act=act)                            # fc_1
+                a_y = grad_reduce(d_y, g[i + 3], f16)
+                linear_bwd_w(d_y, net, g[i + 2], g[i + 3], act=act, amax=a_y)             # fc_1
                 d_net = torch.empty_like(net)
-                linear_bwd_x(d_y, prm[i + 2], net, d_net, act=act)
-                linear_bwd_w(d_net, xb, g[i], g[i + 1], act=act)                               # fc_0
-                linear_bwd_x(d_net, prm[i], xb, d_y, act=act, accumulate=True)                 # d_xb = d_y + (d_net W0) act'(xb), in place
+                linear_bwd_x(d_y, prm[i + 2], net, d_net, act=act, sw=swt(i + 2), amax=a_y)
+                a_net = grad_reduce(d_net, g[i + 1], f16)
+                linear_bwd_w(d_net, xb, g[i], g[i + 1], act=act, amax=a_net)              # fc_0
+                linear_bwd_x(d_net, prm[i], xb, d_y, act=act, accumulate=True, sw=swt(i), amax=a_net)  # d_xb = d_y + (d_net W0) act'(xb), in place
                 d_xb = d_y
                 if b < lay.cl:                                                                 # lin_z[b]: its own dY is d_xb
                     j = lay.lz(b)
-                    linear_bwd_w(d_xb, zl, g[j], g[j + 1])
+                    a_xb = grad_reduce(d_xb, g[j + 1], f16)
+                    linear_bwd_w(d_xb, zl, g[j], g[j + 1], amax=a_xb)
                     if d_zl is None:
                         d_zl = f(R, scene.C)
-                        linear_bwd_x(d_xb, prm[j], None, d_zl)
+                        linear_bwd_x(d_xb, prm[j], None, d_zl, sw=swt(j), amax=a_xb)
                     else:
-                        linear_bwd_x(d_xb, prm[j], None, d_zl, accumulate=True)
+                        linear_bwd_x(d_xb, prm[j], None, d_zl, accumulate=True, sw=swt(j), amax=a_xb)
                 if b == lay.cl:                                                                # the mean's transpose: rows P -> R
                     d_x = f(R, H)
                     check(L.diner_train_view_mean(_p(d_xb), P * H, NV, _p(d_x), 1, st), "diner_train_view_mean(bwd)")
                 else:
                     d_x = d_xb
-            linear_bwd_w(d_x, inp, g_in, g[1])                                                 # lin_in
+            a_x = grad_reduce(d_x, g[1], f16)
+            linear_bwd_w(d_x, inp, g_in, g[1], amax=a_x)                                  # lin_in
             if cam_any:   # lin_in's input gradient, then the transpose of the point inputs to the geometric leaves
                 d_in = f(R, ld_in)
-                linear_bwd_x(d_x, ctx.w_in, None, d_in)
+                linear_bwd_x(d_x, ctx.w_in, None, d_in, sw=swt(0), amax=a_x)
                 check(L.diner_train_point_inputs_backward_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in), ld_in,
                                                               _p(d_zl), _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c),
                                                               _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward_gen")
@@ -271,12 +362,12 @@ class _RenderGenFn(torch.autograd.Function):
                    None if g_c is None else g_c.reshape(sh_c),
                    None if g_ishape is None else g_ishape.reshape(sh_ishape),
                    None if g_depths is None else g_depths.reshape(sh_depths))
-        return (None, None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
+        return (None, None, None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
 
 
-def render_with_grad(renderer, model, rays, z, scene, shape, keep=None):
+def render_with_grad(renderer, model, rays, z, scene, shape, keep=None, f16=False):
     """rgb, depth, weights = composite(model, rays, z) for a model of any shape of the envelope, with gradients to every fusion-MLP
-    parameter, encoder.latent, and the rays, cameras and depth maps when they require grad."""
+    parameter, encoder.latent, and the rays, cameras and depth maps when they require grad.  ``f16``: the GEMMs in f16x3."""
     if shape.combine_layer >= shape.n_blocks and scene.NV != 1:
         raise NotImplementedError(f"combine_layer={shape.combine_layer} >= n_blocks={shape.n_blocks} (no mean over views) with NV={scene.NV}: "
                                   "the reference supports it for one view only (pixelnerf.py:137)")
@@ -284,4 +375,5 @@ def render_with_grad(renderer, model, rays, z, scene, shape, keep=None):
     ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
     cams = camera_leaves(model, rays)
     f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
-    return _RenderGenFn.apply(renderer, scene, ix, keep, cams, shape, z, *f32[:1], model.encoder.latent, *f32[1:], *params)
+    return _RenderGenFn.apply(renderer, scene, ix, keep, cams, shape, bool(f16), z, *f32[:1], model.encoder.latent, *f32[1:], *params)
+

@@ -116,7 +116,9 @@ typedef struct DinerLatentIndex {
  * torch-ops extension checks it at every op entry, diner_amd/_lib.py at load time.  (2: diner_render / diner_composite gained
  * `status`.  3: the shape-general inference path, the *_gen entry points below.)  New entry points that leave every existing argument
  * list and struct layout as it was do not bump it (the shape-general training blocks, diner_train_gemm_act and
- * diner_train_point_inputs(_backward)_gen, and the shape-general f16x3 inference path, the *_gen_f16 entry points, came under 3). */
+ * diner_train_point_inputs(_backward)_gen, and the shape-general f16x3 inference path, the *_gen_f16 entry points, came under 3).
+ * The shape-general f16x3 training GEMM (diner_train_gemm_act_f16x3, _f16x3_w, diner_train_split_weight(_halfs)) adds symbols only and
+ * changes no struct: it came under 3 as well. */
 #define DINER_ABI_VERSION 3
 
 const char *diner_last_error(void);
@@ -490,6 +492,32 @@ int diner_train_point_inputs_backward_gen(const DinerScene *scene, const DinerLa
                                           int64_t ld_in, const float *d_zlat, const float *d_far, float *workspace, float *d_rays,
                                           float *d_poses, float *d_focal, float *d_c, float *d_image_shape, float *d_depths,
                                           void *stream);
+
+/* ---- shape-general training path in f16x3 (train_gen_f16.hip; renderer.train_f16x3_any_shape) ------------------------------- */
+/* diner_train_gemm_act in the arithmetic of diner_train_gemm's DINER_PRECISION_F16X3 mode: the activation is applied in fp32, then each
+ * operand element is multiplied by a power of two -- 2^exp_a / 2^exp_b, or, when amax_a / amax_b is not NULL, the one that maps the
+ * max|.| its device word holds (diner_train_amax, diner_train_colsum_amax) into [2^13, 2^14) -- and split into fp16 hi + lo; three fp16
+ * MFMAs per product (hi*hi, hi*lo, lo*hi), fp32 accumulation, C divided by the two scales; act_s' in fp32 as diner_train_gemm_act
+ * evaluates it.  Same operand rules as diner_train_gemm_act, A and B 16-byte aligned, and a split contraction (0 < k_chunk < K) only
+ * with atomic = 1.  A scaled element beyond the fp16 range
+ * becomes +-inf in its hi half and the products it enters are non-finite (never clamped), as in diner_train_gemm. */
+int diner_train_gemm_act_f16x3(const float *A, const float *B, const float *bias, const float *S, float *C, int64_t M, int32_t N, int32_t K,
+                               int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int64_t ldc, int64_t lds, int32_t act_a, int32_t act_b,
+                               int32_t act_s, float beta, int32_t accumulate, int32_t atomic, int64_t k_chunk, const void *amax_a,
+                               const void *amax_b, int32_t exp_a, int32_t exp_b, void *stream);
+/* Pre-split form of a weight operand B[k][n] (n < N, k < K) for diner_train_gemm_act_f16x3_w: two fp16 planes hi, lo of
+ * diner_train_split_weight_halfs(N, K) = roundup(N, 128) * roundup(K, 32) halfs each, plane[n][k] = the hi / lo half of
+ * B[k][n] * 2^exp, zero in the padding.  B[k][n] = W[n*ld + k] (transpose 0: the forward's W of [N, K]) or W[k*ld + n] (transpose 1:
+ * the input-gradient GEMM's operand, W of [K, N]).  Made once per parameter version (diner_amd/training_gen.py caches it). */
+int64_t diner_train_split_weight_halfs(int32_t N, int32_t K);
+int diner_train_split_weight(const float *W, int32_t N, int32_t K, int64_t ld, int32_t transpose, int32_t exp, void *hi, void *lo,
+                             void *stream);
+/* C[m][n] (+)= sum_k actA(A[m*sam + k]) * B[k][n] (+ bias[n]), then * act_s'(S[m*lds + n]) when S is not NULL, B given by
+ * diner_train_split_weight's planes made with 2^exp_b: diner_train_gemm_act_f16x3 for a row-major A (K % 4 == 0, sam % 4 == 0) without
+ * the in-kernel split of the weight.  amax_a / exp_a as above. */
+int diner_train_gemm_act_f16x3_w(const float *A, int64_t sam, const void *Bhi, const void *Blo, const float *bias, const float *S,
+                                 int64_t lds, float *C, int64_t ldc, int64_t M, int32_t N, int32_t K, int32_t act_a, int32_t act_s,
+                                 float beta, int32_t accumulate, const void *amax_a, int32_t exp_a, int32_t exp_b, void *stream);
 
 #ifdef __cplusplus
 }
