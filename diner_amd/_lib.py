@@ -174,6 +174,22 @@ SYMBOLS = {
     "diner_train_split_weight": (C.c_int, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P]),
     "diner_train_gemm_act_f16x3_w": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, C.c_float, _I32, _P,
                                                _I32, _I32, _P]),
+    # the bicubic latent lookup (index_interp="bicubic"): the *_gen_ix argument lists with an int32 padding (INDEX_PADDING) in place of the
+    # DinerLatentIndex pointer (the ABI version stays 3: new entry points only; INDEX_INTERP and DinerLatentIndex do not carry bicubic)
+    "diner_render_points_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, _P, _P, _I64, _I32, _P, _P]),
+    "diner_render_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, _P, _I64, C.POINTER(DinerSamplerCfg), _I32,
+                                      _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, C.POINTER(DinerTargetCam),
+                                            C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "diner_render_points_gen_f16_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, _P, _P, _I64, _I32, _P, _P]),
+    "diner_render_gen_f16_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, _P, _I64, C.POINTER(DinerSamplerCfg),
+                                          _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "diner_render_image_gen_f16_bc": (C.c_int, [C.POINTER(DinerScene), _I32, C.POINTER(DinerMlpShape), _P, C.POINTER(DinerTargetCam),
+                                                C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "diner_train_point_inputs_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, _P, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P]),
+    "diner_train_point_inputs_backward_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, _P, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P,
+                                                           _P, _P, _P, _P, _P, _P]),
+    "diner_train_bicubic_scatter": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -120,14 +120,22 @@ namespace gen {
 int check_shape(const DinerMlpShape &);
 int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
-int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t,
+                      int bicubic_pad = -1);
 }
 namespace genf16 {
 int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
-int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
+int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t,
+                      int bicubic_pad = -1);
 }
 
+int launch_train_point_inputs_gen_bc(const DinerScene &, int, const float *, const float *, const float *, int64_t, int, int, float *, int64_t,
+                                     float *, float *, hipStream_t);
+int launch_train_point_inputs_bwd_gen_bc(const DinerScene &, int, const float *, const float *, const float *, int64_t, int, int, const float *,
+                                         int64_t, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
+                                         hipStream_t);
+int launch_train_bicubic_scatter(const float *, const float *, int64_t, int, int, int, int, int, float *, hipStream_t);
 int launch_train_gemm_act(const float *, const float *, const float *, const float *, float *, int64_t, int, int, int64_t, int64_t, int64_t,
                           int64_t, int64_t, int64_t, int, int, int, float, int, int, int64_t, hipStream_t);
 int launch_train_point_inputs_gen(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, int,
@@ -167,6 +175,16 @@ static int check_index(const DinerLatentIndex *ix, const char *who)
     }
     if (ix->padding != DINER_INDEX_PAD_BORDER && ix->padding != DINER_INDEX_PAD_ZEROS && ix->padding != DINER_INDEX_PAD_REFLECTION) {
         set_error("%s: latent index padding=%d unknown (DINER_INDEX_PAD_BORDER 0, _ZEROS 1 or _REFLECTION 2)", who, ix->padding);
+        return DINER_E_INVALID;
+    }
+    return DINER_OK;
+}
+
+// the padding argument of the bicubic (_bc) entry points
+static int check_bicubic_padding(int32_t padding, const char *who)
+{
+    if (padding != DINER_INDEX_PAD_BORDER && padding != DINER_INDEX_PAD_ZEROS && padding != DINER_INDEX_PAD_REFLECTION) {
+        set_error("%s: bicubic padding=%d unknown (DINER_INDEX_PAD_BORDER 0, _ZEROS 1 or _REFLECTION 2)", who, padding);
         return DINER_E_INVALID;
     }
     return DINER_OK;
@@ -734,9 +752,10 @@ int diner_pack_mlp_gen_f16(const DinerMlpShape *shape, const DinerMlpGenRaw *raw
 }
 
 /* the three stages of a shape-general render, on the fp32 (f16 = false) or the f16x3 (f16 = true) point kernel */
+/* bicubic_pad >= 0: the bicubic lookup with that padding (the _bc entry points; index is then NULL) */
 static int render_points_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
                              const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out,
-                             void *stream)
+                             void *stream, int bicubic_pad = -1)
 {
     int rc;
     if (!shape) return bad("render_points_gen: shape is NULL");
@@ -748,13 +767,13 @@ static int render_points_gen(bool f16, const DinerScene *scene, const DinerLaten
     if (f16 && (uintptr_t)mlp_packed % 16) return bad("render_points_gen_f16: mlp_packed not 16-byte aligned");
     if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points_gen: NULL rays / z / out");
     return (f16 ? genf16::launch_points_mlp : gen::launch_points_mlp)(*scene, index ? *index : k_default_index, *shape, mlp_packed, rays, z,
-                                                                       NR, K, rgbsigma_out, (hipStream_t)stream);
+                                                                       NR, K, rgbsigma_out, (hipStream_t)stream, bicubic_pad);
 }
 
 static int render_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
                       const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
                       const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
-                      float *weights_out, uint32_t *status, void *stream)
+                      float *weights_out, uint32_t *status, void *stream, int bicubic_pad = -1)
 {
     int rc;
     if (!shape) return bad("render_gen: shape is NULL");
@@ -766,14 +785,14 @@ static int render_gen(bool f16, const DinerScene *scene, const DinerLatentIndex 
     const int64_t N = (int64_t)scene->SB * NR;
     float *z = workspace, *rgbsigma = workspace + N * cfg->n_samples;
     if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr, nullptr, stream))) return rc;
-    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
 static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
                             const float *mlp_packed, const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd,
                             uint64_t seed, float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
-                            uint32_t *status, void *stream)
+                            uint32_t *status, void *stream, int bicubic_pad = -1)
 {
     int rc;
     if (!shape) return bad("render_image_gen: shape is NULL");
@@ -789,7 +808,7 @@ static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatent
     if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
                              (hipStream_t)stream)))
         return rc;
-    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
@@ -842,5 +861,67 @@ static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatent
 DINER_GEN_ENTRY_POINTS(, false)
 DINER_GEN_ENTRY_POINTS(_f16, true)
 #undef DINER_GEN_ENTRY_POINTS
+
+/* ---- the bicubic latent lookup (points_mlp_gen_bc.hip, points_mlp_gen_f16_bc.hip, train_gen_bc.hip) ------------------------------ */
+#define DINER_GEN_BC_ENTRY_POINTS(SUFFIX, F16)                                                                                               \
+    int diner_render_points_gen##SUFFIX##_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,  \
+                                             const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)    \
+    {                                                                                                                                        \
+        if (check_bicubic_padding(padding, "render_points_gen" #SUFFIX "_bc")) return DINER_E_INVALID;                                       \
+        return render_points_gen(F16, scene, nullptr, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream, padding);                     \
+    }                                                                                                                                        \
+    int diner_render_gen##SUFFIX##_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,         \
+                                      const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,  \
+                                      const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out,            \
+                                      float *depth_out, float *weights_out, uint32_t *status, void *stream)                                  \
+    {                                                                                                                                        \
+        if (check_bicubic_padding(padding, "render_gen" #SUFFIX "_bc")) return DINER_E_INVALID;                                              \
+        return render_gen(F16, scene, nullptr, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss, u_fill, seed, workspace,     \
+                          rgb_out, depth_out, weights_out, status, stream, padding);                                                         \
+    }                                                                                                                                        \
+    int diner_render_image_gen##SUFFIX##_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,   \
+                                            const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed,        \
+                                            float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,         \
+                                            uint32_t *status, void *stream)                                                                  \
+    {                                                                                                                                        \
+        if (check_bicubic_padding(padding, "render_image_gen" #SUFFIX "_bc")) return DINER_E_INVALID;                                        \
+        return render_image_gen(F16, scene, nullptr, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace, rays_out, rgb_out, depth_out, \
+                                weights_out, status, stream, padding);                                                                       \
+    }
+
+DINER_GEN_BC_ENTRY_POINTS(, false)
+DINER_GEN_BC_ENTRY_POINTS(_f16, true)
+#undef DINER_GEN_BC_ENTRY_POINTS
+
+int diner_train_point_inputs_gen_bc(const DinerScene *scene, int32_t padding, const float *latent_nhwc, const float *rays, const float *z,
+                                    int64_t NR, int32_t K, int32_t sb, float *in_out, int64_t ld_in, float *zlat, float *taps, void *stream)
+{
+    int rc;
+    if ((rc = check_bicubic_padding(padding, "train_point_inputs_gen_bc"))) return rc;
+    if ((rc = check_train_gen_inputs(scene, nullptr, NR, K, sb, ld_in, "train_point_inputs_gen_bc"))) return rc;
+    if (!latent_nhwc || !rays || !z || !in_out || !zlat || !taps) return bad("train_point_inputs_gen_bc: NULL pointer");
+    return launch_train_point_inputs_gen_bc(*scene, padding, latent_nhwc, rays, z, NR, K, sb, in_out, ld_in, zlat, taps, (hipStream_t)stream);
+}
+
+int diner_train_point_inputs_backward_gen_bc(const DinerScene *scene, int32_t padding, const float *latent_nhwc, const float *rays,
+                                             const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in, int64_t ld_in,
+                                             const float *d_zlat, const float *d_far, float *workspace, float *d_rays, float *d_poses,
+                                             float *d_focal, float *d_c, float *d_image_shape, float *d_depths, void *stream)
+{
+    int rc;
+    if ((rc = check_bicubic_padding(padding, "train_point_inputs_backward_gen_bc"))) return rc;
+    if ((rc = check_train_gen_inputs(scene, nullptr, NR, K, sb, ld_in, "train_point_inputs_backward_gen_bc"))) return rc;
+    if (!latent_nhwc || !rays || !z || !d_in || !d_zlat || !workspace) return bad("train_point_inputs_backward_gen_bc: NULL pointer");
+    return launch_train_point_inputs_bwd_gen_bc(*scene, padding, latent_nhwc, rays, z, NR, K, sb, d_in, ld_in, d_zlat, d_far, workspace, d_rays,
+                                                d_poses, d_focal, d_c, d_image_shape, d_depths, (hipStream_t)stream);
+}
+
+int diner_train_bicubic_scatter(const float *dz, const float *taps, int64_t P, int32_t C, int32_t h, int32_t w, int32_t NV, int32_t sb,
+                                float *dlatent_nhwc, void *stream)
+{
+    if (!dz || !taps || !dlatent_nhwc) return bad("train_bicubic_scatter: NULL pointer");
+    if (P < 0 || C <= 0 || h <= 0 || w <= 0 || NV < 1 || sb < 0) return bad("train_bicubic_scatter: bad size");
+    return launch_train_bicubic_scatter(dz, taps, P, C, h, w, NV, sb, dlatent_nhwc, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -185,6 +185,55 @@ __device__ __forceinline__ LatentFoot latent_footprint(float u, float w, float s
 }
 
 // --------------------------------------------------------------------------------------------
+// bicubic latent lookup: grid_sample(mode="bicubic", align_corners=False) of SpatialEncoder.index (image_encoder.py:119-125) with
+// index_interp="bicubic".  The centre coordinate is NOT clipped or reflected; the 4 x 4 taps sit at (floor(ix) - 1 + i,
+// floor(iy) - 1 + j) and each integer tap position goes through the padding on its own (ATen's get_value_bounded): border clamps it,
+// reflection reflects it over [-0.5, size - 0.5] and clamps, zeros drops a tap outside the map.  The footprint is separable:
+// result = sum_j cy[j] * (sum_i cx[i] * texel(x[i], y[j])); with zeros padding the weight of a column / row outside the map is
+// folded to 0 per axis.  Indices are always inside the map (NaN / inf coordinates included), so every tap is readable.
+// --------------------------------------------------------------------------------------------
+struct BicubicFoot {
+    int x[4], y[4];        // texel columns / rows of the taps
+    float cx[4], cy[4];    // cubic-convolution weights (A = -0.75) at distances t + 1, t, 1 - t, 2 - t
+};
+
+// one axis: indices, weights and the weights' derivative in the fractional position t (d ic / d t = 1; the padding acts on the
+// integer tap positions and carries no gradient)
+__device__ __forceinline__ void bicubic_axis(float ic, int size, int padding, int (&idx)[4], float (&c)[4], float (&dc)[4])
+{
+    const float A = -0.75f;
+    const float c0f = floorf(ic), t = ic - c0f;
+    float d = t + 1.0f;                                     // ATen get_cubic_upsample_coefficients
+    c[0] = ((A * d - 5.0f * A) * d + 8.0f * A) * d - 4.0f * A;
+    dc[0] = (3.0f * A * d - 10.0f * A) * d + 8.0f * A;
+    c[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+    dc[1] = (3.0f * (A + 2.0f) * t - 2.0f * (A + 3.0f)) * t;
+    d = 1.0f - t;
+    c[2] = ((A + 2.0f) * d - (A + 3.0f)) * d * d + 1.0f;
+    dc[2] = -((3.0f * (A + 2.0f) * d - 2.0f * (A + 3.0f)) * d);
+    d = d + 1.0f;
+    c[3] = ((A * d - 5.0f * A) * d + 8.0f * A) * d - 4.0f * A;
+    dc[3] = -((3.0f * A * d - 10.0f * A) * d + 8.0f * A);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float p = c0f + (float)(i - 1);
+        const bool in = p >= 0.0f && p <= (float)(size - 1);   // NaN: outside
+        if (padding == DINER_INDEX_PAD_REFLECTION) p = reflect_coord(p, size);
+        idx[i] = safe_idx(clipf(p, (float)(size - 1)), size);
+        if (padding == DINER_INDEX_PAD_ZEROS && !in) { c[i] = 0.0f; dc[i] = 0.0f; }
+    }
+}
+
+__device__ __forceinline__ BicubicFoot bicubic_footprint(float u, float w, float sxl, float syl, int lw, int lh, int padding)
+{
+    BicubicFoot f;
+    float dcx[4], dcy[4];
+    bicubic_axis(unnorm(u * sxl, (float)lw / 2.0f), lw, padding, f.x, f.cx, dcx);
+    bicubic_axis(unnorm(w * syl, (float)lh / 2.0f), lh, padding, f.y, f.cy, dcy);
+    return f;
+}
+
+// --------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG (perf mode: statistically equivalent to torch.rand/randn, not
 // bit-matching any torch generator -- parity tests inject explicit noise instead)
 // --------------------------------------------------------------------------------------------

@@ -238,10 +238,25 @@ struct Tap {        // bilinear footprint of one (point, view) in the latent map
     float nw, ne, sw, se;    // weights; a tap outside the map has its weight forced to 0
 };
 
+struct TapBc {      // bicubic footprint of one (point, view) in the latent map (common.hpp BicubicFoot), 64 bytes
+    int xo[4], yo[4];        // float4 offsets of the 4 columns (x * c4) and the 4 rows (y * w * c4); texel (i, j) = xo[i] + yo[j]
+    float cx[4], cy[4];      // weights per axis; zeros padding: 0 for a column / row outside the map
+};
+
 // points_mlp_gen_ix.hip compiles this file a second time with DINER_GEN_IX defined: the kernel is then points_mlp_gen_ix_kernel, which
 // serves every other latent lookup mode (ix_interp / ix_padding, DINER_INDEX_*; common.hpp latent_footprint).  Its own translation
 // unit keeps this one's code object -- the three bilinear / border kernels -- exactly what it was.
-#ifndef DINER_GEN_IX
+// points_mlp_gen_bc.hip compiles it a third time with DINER_GEN_BC (and DINER_GEN_IX) defined: points_mlp_gen_bc_kernel, the 16-tap
+// bicubic lookup (common.hpp bicubic_footprint) with the padding ix_padding, again in a code object of its own.
+#ifdef DINER_GEN_BC
+constexpr int TAP_F4 = 4;   // float4 entries of one row's tap record in LDS
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                        const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                        int64_t NR, int K, float *__restrict__ rgbsigma, int ix_padding)
+{
+#elif !defined(DINER_GEN_IX)
+constexpr int TAP_F4 = 2;
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
                                                                      const float *__restrict__ rays, const float *__restrict__ zsamp,
@@ -250,6 +265,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
     constexpr bool GIX = false;
     const int ix_interp = 0, ix_padding = 0;
 #else
+constexpr int TAP_F4 = 2;
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
                                                                         const float *__restrict__ rays, const float *__restrict__ zsamp,
@@ -258,10 +274,14 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
 {
     constexpr bool GIX = true;
 #endif
-    __shared__ f32x4 lds[A_F4 + TILE_P * 2];  // A image + one Tap per row
+    __shared__ f32x4 lds[A_F4 + TILE_P * TAP_F4];  // A image + one Tap (bicubic: one TapBc) per row
     f32x4 *A4 = lds;
     float *A = (float *)lds;
+#ifdef DINER_GEN_BC
+    TapBc *taps = (TapBc *)(lds + A_F4);
+#else
     Tap *taps = (Tap *)(lds + A_F4);
+#endif
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rb0 = RB == 2 ? 0 : (wave & 1), ct0 = RB == 2 ? wave * CT : (wave >> 1) * CT;
@@ -322,6 +342,15 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
                 else val = 0.0f;
                 A[a_off(row, e)] = val;
             }
+#ifdef DINER_GEN_BC
+            if (wave == 0) {  // the 4 x 4 bicubic footprint in the latent map (image_encoder.py:97-127; common.hpp)
+                const BicubicFoot f = bicubic_footprint(u, w, sxl, syl, s.w, s.h, ix_padding);
+                TapBc t;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { t.xo[i] = f.x[i] * c4; t.yo[i] = f.y[i] * s.w * c4; t.cx[i] = f.cx[i]; t.cy[i] = f.cy[i]; }
+                taps[row] = t;
+            }
+#else
             if (wave == 0 && GIX) {  // footprint of any lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
                 const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
                 Tap t;
@@ -345,6 +374,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
                 t.sw = y1ok ? fy * ex : 0.0f; t.se = (x1ok && y1ok) ? fy * fx : 0.0f;
                 taps[row] = t;
             }
+#endif
         }
         __syncthreads();
         acc_bias(x, bias + L.bias_lin_in(), false, ct0, NT, lane);
@@ -357,6 +387,34 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
             for (int k0 = 0; k0 < L.dlat; k0 += KMAX) {
                 // ---- z[:, k0 : k0 + kc] = bilinear latent of the 64 points -> A (each wave gathers 8 rows) ---------
                 const int kc4 = (L.dlat - k0 < KMAX ? L.dlat - k0 : KMAX) / 4;
+#ifdef DINER_GEN_BC
+                // 16 texels per channel quad: sum_j cy[j] * (sum_i cx[i] * texel_ij), rows then columns, contracted FMAs.  The row
+                // loop is unrolled by BC_ROW_UNROLL only (4 x that many 16-byte loads in flight per lane): fully unrolled, the 16
+                // loads of a quad compete with the kernel's accumulators for registers.
+                for (int rr = 0; rr < TILE_P / NWAVES; ++rr) {
+                    const int r = wave * (TILE_P / NWAVES) + rr;
+                    const TapBc *tp = taps + r;
+                    const int x0 = tp->xo[0], x1 = tp->xo[1], x2 = tp->xo[2], x3 = tp->xo[3];
+                    const float w0 = tp->cx[0], w1 = tp->cx[1], w2 = tp->cx[2], w3 = tp->cx[3];
+                    for (int q = lane; q < kc4; q += 64) {
+                        const f32x4 *lq = lat + (k0 / 4 + q);
+                        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll BC_ROW_UNROLL
+                        for (int j = 0; j < 4; ++j) {
+                            const f32x4 *lr = lq + tp->yo[j];
+                            const float wy = tp->cy[j];
+                            const f32x4 a = lr[x0], bb = lr[x1], c = lr[x2], d = lr[x3];
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const float rowv = __builtin_fmaf(d[i], w3, __builtin_fmaf(c[i], w2, __builtin_fmaf(bb[i], w1, a[i] * w0)));
+                                acc[i] = j == 0 ? rowv * wy : __builtin_fmaf(rowv, wy, acc[i]);
+                            }
+                        }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) A[a_off(r, 4 * q + i)] = acc[i];
+                    }
+                }
+#else
                 for (int rr = 0; rr < TILE_P / NWAVES; ++rr) {
                     const int r = wave * (TILE_P / NWAVES) + rr;
                     const Tap t = taps[r];
@@ -369,6 +427,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
                                 __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
                     }
                 }
+#endif
                 __syncthreads();
                 gemm(x, A4, (const f32x4 *)(Wp + L.off_z + b * L.w_z), L.njb_lat, k0 / 8, kc4 / 2, rb0, ct0, NT, lane);
                 __syncthreads();
@@ -440,7 +499,20 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
     }
 }
 
-#ifdef DINER_GEN_IX
+#if defined(DINER_GEN_BC)
+int launch_points_mlp_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
+                         const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
+{
+    const dim3 grid((unsigned)((NR * (int64_t)K + TILE_P - 1) / TILE_P), (unsigned)s.SB), block(NWAVES * 64);
+    if (d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_bc_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    else if (d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_bc_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_bc_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    return check_launch("points_mlp_gen_bc_kernel");
+}
+#elif defined(DINER_GEN_IX)
 int launch_points_mlp_ix(const DinerScene &s, const Layout &L, int d_hidden, int ix_interp, int ix_padding, const float *mlp_packed,
                          const float *rays, const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {
@@ -456,6 +528,8 @@ int launch_points_mlp_ix(const DinerScene &s, const Layout &L, int d_hidden, int
 #else
 int launch_points_mlp_ix(const DinerScene &, const Layout &, int, int, int, const float *, const float *, const float *, int64_t, int,
                          float *, hipStream_t);   // points_mlp_gen_ix.hip
+int launch_points_mlp_bc(const DinerScene &, const Layout &, int, int, const float *, const float *, const float *, int64_t, int, float *,
+                         hipStream_t);            // points_mlp_gen_bc.hip
 
 // the instantiation a d_hidden runs on: <1,1> for up to 128 columns, <2,1> up to 256, <2,2> up to 512
 const char *kernel_name(int d_hidden)
@@ -463,8 +537,9 @@ const char *kernel_name(int d_hidden)
     return d_hidden <= 128 ? "points_mlp_gen_kernel<1,1>" : d_hidden <= 256 ? "points_mlp_gen_kernel<2,1>" : "points_mlp_gen_kernel<2,2>";
 }
 
+// bicubic_pad >= 0: the bicubic lookup with that DINER_INDEX_PAD_* (ix is then not read)
 int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const DinerMlpShape &m, const float *mlp_packed, const float *rays,
-                      const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
+                      const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st, int bicubic_pad)
 {
     int rc;
     if ((rc = check_shape(m))) return rc;
@@ -480,6 +555,7 @@ int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const Din
     const int64_t tiles = (P + TILE_P - 1) / TILE_P;
     if (tiles > 0x7fffffffLL) { set_error("render_points_gen: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
     const Layout L = layout_of(m);
+    if (bicubic_pad >= 0) return launch_points_mlp_bc(s, L, m.d_hidden, bicubic_pad, mlp_packed, rays, z, NR, K, rgbsigma, st);
     if (ix.interp != DINER_INDEX_BILINEAR || ix.padding != DINER_INDEX_PAD_BORDER)
         return launch_points_mlp_ix(s, L, m.d_hidden, ix.interp, ix.padding, mlp_packed, rays, z, NR, K, rgbsigma, st);
     const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);

@@ -284,10 +284,25 @@ struct Tap {        // footprint of one (point, view) in the latent map
     float nw, ne, sw, se;    // weights * 2^-4; a tap outside the map has its weight forced to 0
 };
 
+struct TapBc {      // bicubic footprint of one (point, view) in the latent map (common.hpp BicubicFoot), 64 bytes
+    int xo[4], yo[4];        // float4 offsets of the 4 columns (x * c4) and the 4 rows (y * w * c4); texel (i, j) = xo[i] + yo[j]
+    float cx[4], cy[4];      // weights per axis, cy * 2^-4; zeros padding: 0 for a column / row outside the map
+};
+
 // points_mlp_gen_f16_ix.hip compiles this file a second time with DINER_GENF16_IX defined: the kernel is then
 // points_mlp_gen_f16_ix_kernel, which serves every other latent lookup mode (ix_interp / ix_padding, DINER_INDEX_*; common.hpp
 // latent_footprint), in a code object of its own.
-#ifndef DINER_GENF16_IX
+// points_mlp_gen_f16_bc.hip compiles it a third time with DINER_GENF16_BC (and DINER_GENF16_IX) defined:
+// points_mlp_gen_f16_bc_kernel, the 16-tap bicubic lookup (common.hpp bicubic_footprint) with the padding ix_padding.
+#ifdef DINER_GENF16_BC
+constexpr int TAP_SLOTS = 4;   // 16-byte slots of one point's tap record in LDS
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                            const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                            int64_t NR, int K, float *__restrict__ rgbsigma, int ix_padding)
+{
+#elif !defined(DINER_GENF16_IX)
+constexpr int TAP_SLOTS = 2;
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
                                                                          const float *__restrict__ rays, const float *__restrict__ zsamp,
@@ -296,6 +311,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
     constexpr bool GIX = false;
     const int ix_interp = 0, ix_padding = 0;
 #else
+constexpr int TAP_SLOTS = 2;
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
                                                                             const float *__restrict__ rays, const float *__restrict__ zsamp,
@@ -304,10 +320,14 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
 {
     constexpr bool GIX = true;
 #endif
-    __shared__ u32x4 lds[A_H8 + TILE_P * 2];  // A image + one Tap per point
+    __shared__ u32x4 lds[A_H8 + TILE_P * TAP_SLOTS];  // A image + one Tap (bicubic: one TapBc) per point
     u32x4 *A = lds;
     const h8 *A8 = (const h8 *)lds;
+#ifdef DINER_GENF16_BC
+    TapBc *taps = (TapBc *)(lds + A_H8);
+#else
     Tap *taps = (Tap *)(lds + A_H8);
+#endif
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rb0 = RB == 2 ? 0 : (wave & 1), ct0 = RB == 2 ? wave * CT : (wave >> 1) * CT;
@@ -382,6 +402,18 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
                 A[a_slot(pl, 0, row)] = vh;
                 A[a_slot(pl, 1, row)] = vl;
             }
+#ifdef DINER_GENF16_BC
+            if (wave == 0) {  // the 4 x 4 bicubic footprint in the latent map (image_encoder.py:97-127; common.hpp); the scale rides on cy
+                const BicubicFoot f = bicubic_footprint(u, w, sxl, syl, s.w, s.h, ix_padding);
+                TapBc t;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    t.xo[i] = f.x[i] * c4; t.yo[i] = f.y[i] * s.w * c4;
+                    t.cx[i] = f.cx[i]; t.cy[i] = f.cy[i] * ACT_SCALE;
+                }
+                taps[row] = t;
+            }
+#else
             if (wave == 0) {  // footprint of the lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
                 const LatentFoot f = latent_footprint<GIX>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
                 Tap t;
@@ -390,6 +422,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
                 t.nw = f.nw * ACT_SCALE; t.ne = f.ne * ACT_SCALE; t.sw = f.sw * ACT_SCALE; t.se = f.se * ACT_SCALE;
                 taps[row] = t;
             }
+#endif
         }
         __syncthreads();
         acc_bias(x, bias + L.bias_lin_in(), false, ct0, NT, lane);
@@ -404,6 +437,44 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
                 const int kc = L.dlat - k0 < KMAX ? L.dlat - k0 : KMAX;
                 const int npl = (kc + 15) / 16 * 2;   // planes the GEMM reads (the last one zero when kc % 16 == 8)
                 const int r = wave * (TILE_P / NWAVES) + (lane & 7);
+#ifdef DINER_GENF16_BC
+                // 16 texels per channel quad: sum_j cy[j] * (sum_i cx[i] * texel_ij) in fp32, rows then columns, contracted FMAs; the
+                // hi / lo split takes the SUM (the outer weights are negative and sum |w| > 1: splitting taps would cancel halves).
+                // The row loop is unrolled by BC_ROW_UNROLL only, as in points_mlp_gen.hip.
+                const TapBc *tp = taps + r;
+                const int x0 = tp->xo[0], x1 = tp->xo[1], x2 = tp->xo[2], x3 = tp->xo[3];
+                const float w0 = tp->cx[0], w1 = tp->cx[1], w2 = tp->cx[2], w3 = tp->cx[3];
+                for (int pl = lane >> 3; pl < npl; pl += 8) {
+                    u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
+                    if (pl * 8 < kc) {
+                        unsigned ph[4], plo[4];
+#pragma unroll
+                        for (int half = 0; half < 2; ++half) {
+                            const f32x4 *lq = lat + (k0 / 4 + pl * 2 + half);
+                            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll BC_ROW_UNROLL
+                            for (int j = 0; j < 4; ++j) {
+                                const f32x4 *lr = lq + tp->yo[j];
+                                const float wy = tp->cy[j];
+                                const f32x4 a = lr[x0], bb = lr[x1], c = lr[x2], d = lr[x3];
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) {
+                                    const float rowv = __builtin_fmaf(d[i], w3, __builtin_fmaf(c[i], w2, __builtin_fmaf(bb[i], w1, a[i] * w0)));
+                                    acc[i] = j == 0 ? rowv * wy : __builtin_fmaf(rowv, wy, acc[i]);
+                                }
+                            }
+                            _Float16 hi[4], lo[4];
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) split(acc[i], hi[i], lo[i]);
+                            ph[2 * half] = pack2(hi[0], hi[1]); ph[2 * half + 1] = pack2(hi[2], hi[3]);
+                            plo[2 * half] = pack2(lo[0], lo[1]); plo[2 * half + 1] = pack2(lo[2], lo[3]);
+                        }
+                        vh = u32x4{ph[0], ph[1], ph[2], ph[3]}; vl = u32x4{plo[0], plo[1], plo[2], plo[3]};
+                    }
+                    A[a_slot(pl, 0, r)] = vh;
+                    A[a_slot(pl, 1, r)] = vl;
+                }
+#else
                 const Tap t = taps[r];
                 for (int pl = lane >> 3; pl < npl; pl += 8) {
                     u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
@@ -426,6 +497,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
                     A[a_slot(pl, 0, r)] = vh;
                     A[a_slot(pl, 1, r)] = vl;
                 }
+#endif
                 __syncthreads();
                 gemm(x, A8, Wh + (L.off_z + b * L.w_z) / 8, L.nkb_lat, k0 / 16, npl / 2, rb0, ct0, NT, lane);
                 __syncthreads();
@@ -510,7 +582,20 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
     }
 }
 
-#ifdef DINER_GENF16_IX
+#if defined(DINER_GENF16_BC)
+int launch_points_mlp_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
+                         const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
+{
+    const dim3 grid((unsigned)((NR * (int64_t)K + TILE_P - 1) / TILE_P), (unsigned)s.SB), block(NWAVES * 64);
+    if (d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_f16_bc_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    else if (d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_f16_bc_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_f16_bc_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding);
+    return check_launch("points_mlp_gen_f16_bc_kernel");
+}
+#elif defined(DINER_GENF16_IX)
 int launch_points_mlp_ix(const DinerScene &s, const Layout &L, int d_hidden, int ix_interp, int ix_padding, const float *mlp_packed,
                          const float *rays, const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {
@@ -526,6 +611,8 @@ int launch_points_mlp_ix(const DinerScene &s, const Layout &L, int d_hidden, int
 #else
 int launch_points_mlp_ix(const DinerScene &, const Layout &, int, int, int, const float *, const float *, const float *, int64_t, int,
                          float *, hipStream_t);   // points_mlp_gen_f16_ix.hip
+int launch_points_mlp_bc(const DinerScene &, const Layout &, int, int, const float *, const float *, const float *, int64_t, int, float *,
+                         hipStream_t);            // points_mlp_gen_f16_bc.hip
 
 // the instantiation a d_hidden runs on: <1,1> for up to 128 features, <2,1> up to 256, <2,2> up to 512
 static const char *kernel_name(int d_hidden)
@@ -533,8 +620,9 @@ static const char *kernel_name(int d_hidden)
     return d_hidden <= 128 ? "points_mlp_gen_f16_kernel<1,1>" : d_hidden <= 256 ? "points_mlp_gen_f16_kernel<2,1>" : "points_mlp_gen_f16_kernel<2,2>";
 }
 
+// bicubic_pad >= 0: the bicubic lookup with that DINER_INDEX_PAD_* (ix is then not read)
 int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const DinerMlpShape &m, const float *mlp_packed, const float *rays,
-                      const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
+                      const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st, int bicubic_pad)
 {
     int rc;
     if ((rc = gen::check_shape(m))) return rc;
@@ -550,6 +638,7 @@ int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const Din
     const int64_t tiles = (P + TILE_P - 1) / TILE_P;
     if (tiles > 0x7fffffffLL) { set_error("render_points_gen_f16: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
     const Layout L = layout_of(m);
+    if (bicubic_pad >= 0) return launch_points_mlp_bc(s, L, m.d_hidden, bicubic_pad, mlp_packed, rays, z, NR, K, rgbsigma, st);
     if (ix.interp != DINER_INDEX_BILINEAR || ix.padding != DINER_INDEX_PAD_BORDER)
         return launch_points_mlp_ix(s, L, m.d_hidden, ix.interp, ix.padding, mlp_packed, rays, z, NR, K, rgbsigma, st);
     const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);

@@ -198,7 +198,7 @@ class NeRFRendererDGS(torch.nn.Module):
     """
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000,
-                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False, train_f16x3_any_shape=False):
+                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False, train_f16x3_any_shape=False, bicubic_index=False):
         super().__init__()
         self.n_samples = n_samples
         self.n_depth_candidates = n_depth_candidates
@@ -258,6 +258,13 @@ class NeRFRendererDGS(torch.nn.Module):
         # effective_precision "f16x3", no warning) instead of exact fp32.  Opt-in: when False that path trains in fp32 behind the
         # precision warning, as before.  A plain attribute, so that a config can set it (renderer.kwargs.train_f16x3_any_shape).
         self.train_f16x3_any_shape = bool(train_f16x3_any_shape)
+        # An encoder with index_interp="bicubic" (grid_sample's 16-tap lookup, any index_padding): such a model of ANY shape, the standard
+        # one included, is routed like a non-standard shape -- inference on the shape-general kernels' bicubic compilations
+        # (points_mlp_gen_bc.hip / points_mlp_gen_f16_bc.hip: last_route "points_mlp_gen" / "points_mlp_gen_f16" under f16x3_any_shape),
+        # training on diner_amd/training_gen.py (needs train_any_shape; train_f16x3_any_shape for f16x3).  The 512-wide kernels and the
+        # lin_z maps do not serve bicubic.  Opt-in: when False a bicubic model raises, as before (the static _validate_model always
+        # does).  A plain attribute, so that a config can set it (renderer.kwargs.bicubic_index).
+        self.bicubic_index = bool(bicubic_index)
         from .training_gen import WeightSplitCache
         self._weight_split_cache = WeightSplitCache()   # that path's pre-split weights, per parameter version
         # render_image under autograd: rays per chunk of its backward, which re-runs the training path chunk by chunk (peak memory = one
@@ -290,8 +297,13 @@ class NeRFRendererDGS(torch.nn.Module):
     def _validate_model(model) -> MlpShape:
         """The shape of ``model``'s fusion MLP and encodings; raises ``NotImplementedError`` naming what lies outside what the kernels
         serve: the standard shape (the 512-wide kernels) and the envelope of the shape-general kernel (include/diner_hip.h)."""
-        enc, mlp = model.encoder, model.mlp_fine
         NeRFRendererDGS._latent_index(model)
+        return NeRFRendererDGS._validate_shape(model)
+
+    @staticmethod
+    def _validate_shape(model) -> MlpShape:
+        """_validate_model without the latent lookup's check"""
+        enc, mlp = model.encoder, model.mlp_fine
         if getattr(mlp, "combine_type", "average") != "average":
             raise NotImplementedError(f"only combine_type='average' (resnetfc.py:9-14), not {mlp.combine_type!r}")
         act = getattr(mlp, "activation", torch.nn.ReLU())
@@ -338,23 +350,48 @@ class NeRFRendererDGS(torch.nn.Module):
     def _latent_index(model) -> Optional[_lib.DinerLatentIndex]:
         """The encoder's latent lookup (SpatialEncoder index_interp / index_padding, image_encoder.py:24-25,119-125): None for the
         default bilinear / border (the entry points and torch ops without _ix), else the DinerLatentIndex of the _ix entry points.
-        Raises ``NotImplementedError`` for a mode no kernel serves (bicubic: 16 taps)."""
+        Raises ``NotImplementedError`` for a mode these entry points do not serve; bicubic is one: it has entry points of its own,
+        behind the renderer's ``bicubic_index`` switch (``_validate``)."""
         interp = getattr(model.encoder, "index_interp", "bilinear")
         padding = getattr(model.encoder, "index_padding", "border")
         if interp not in _lib.INDEX_INTERP or padding not in _lib.INDEX_PADDING:
             raise NotImplementedError(f"latent lookup index_interp={interp!r}, index_padding={padding!r} unsupported: index_interp in "
-                                      f"{sorted(_lib.INDEX_INTERP)}, index_padding in {sorted(_lib.INDEX_PADDING)} (image_encoder.py:24-25)")
+                                      f"{sorted(_lib.INDEX_INTERP)}, index_padding in {sorted(_lib.INDEX_PADDING)} (image_encoder.py:24-25); "
+                                      "index_interp='bicubic' is served by a renderer constructed with bicubic_index=True "
+                                      "(renderer.kwargs.bicubic_index: the shape-general kernels' 16-tap lookup)")
         if interp == "bilinear" and padding == "border":
             return None
         return _lib.DinerLatentIndex(_lib.INDEX_INTERP[interp], _lib.INDEX_PADDING[padding])
 
+    def _bicubic_pad(self, model) -> Optional[int]:
+        """the DINER_INDEX_PAD_* of ``model``'s lookup when it is bicubic and this renderer serves it (``bicubic_index``), else None.
+        Read from the model wherever the routing needs it: no call depends on which model another call saw."""
+        if model is None or not self.bicubic_index or getattr(model.encoder, "index_interp", "bilinear") != "bicubic":
+            return None
+        return _lib.INDEX_PADDING.get(getattr(model.encoder, "index_padding", "border"))
+
+    def _validate(self, model) -> MlpShape:
+        """_validate_model for this renderer's routing: with ``bicubic_index`` an encoder with index_interp="bicubic" and any of the
+        three paddings is accepted and takes the shape-general routes"""
+        if self._bicubic_pad(model) is not None:
+            return self._validate_shape(model)
+        return self._validate_model(model)
+
+    def _index(self, model) -> Optional[_lib.DinerLatentIndex]:
+        """_latent_index of ``model``; None for a bicubic one this renderer serves (``_bicubic_pad`` has its padding)"""
+        return None if self._bicubic_pad(model) is not None else self._latent_index(model)
+
+    def _needs_gen(self, shape: MlpShape, model=None) -> bool:
+        """``model`` has no 512-wide kernel: another shape than the standard one, or the bicubic lookup"""
+        return not shape.standard or self._bicubic_pad(model) is not None
+
     def _route(self, model, f16_ok=True) -> MlpShape:
         """validate ``model``; for a shape that takes a shape-general kernel, settle the precision (fp32 is what runs, unless
         f16x3_any_shape sends this inference call -- ``f16_ok`` -- to the split-fp16 kernel)"""
-        shape = self._validate_model(model)
-        if f16_ok and self._use_gen_f16(shape):
+        shape = self._validate(model)
+        if f16_ok and self._use_gen_f16(shape, model):
             self.effective_precision = "f16x3"
-        elif self._use_gen(shape):
+        elif self._use_gen(shape, model):
             self._settle_fp32(shape, stacklevel=4)
         else:
             self.effective_precision = self.precision
@@ -368,29 +405,40 @@ class NeRFRendererDGS(torch.nn.Module):
             self._warned_precision = True
         self.effective_precision = "fp32"
 
-    def _use_gen(self, shape: MlpShape) -> bool:
-        return self._force_gen or not shape.standard
+    def _use_gen(self, shape: MlpShape, model=None) -> bool:
+        return self._force_gen or self._needs_gen(shape, model)
 
-    def _use_gen_f16(self, shape: MlpShape) -> bool:
+    def _use_gen_f16(self, shape: MlpShape, model=None) -> bool:
         """inference of a non-standard model on the shape-general f16x3 kernel (f16x3_any_shape) instead of the fp32 one"""
-        return bool(self.f16x3_any_shape) and self.precision == "f16x3" and not shape.standard and not self._force_gen
+        return bool(self.f16x3_any_shape) and self.precision == "f16x3" and self._needs_gen(shape, model) and not self._force_gen
 
     def _gen_entry(self, name: str, f16: bool):
         """the C entry point ``diner_<name>`` of the shape-general path, its _f16 form for the split-fp16 kernel: -> (function, its name)"""
         full = "diner_" + (name.replace("_gen", "_gen_f16") if f16 else name)
         return getattr(_lib.lib(), full), full
 
-    def _use_gen_train(self, shape: MlpShape) -> bool:
-        return self._force_gen_train or (self.train_any_shape and not shape.standard)
+    def _gen_lookup(self, name: str, f16: bool, model):
+        """the entry point of ``_gen_entry`` for ``model``'s latent lookup and the arguments that follow the scene in its list:
+        ``diner_<name>`` (bilinear / border), ``.._ix`` + the DinerLatentIndex, or ``.._bc`` + the padding (bicubic)"""
+        pad = self._bicubic_pad(model)
+        if pad is not None:
+            return (*self._gen_entry(name + "_bc", f16), (int(pad),))
+        ix = self._latent_index(model)
+        if ix is not None:
+            return (*self._gen_entry(name + "_ix", f16), (C.byref(ix),))
+        return (*self._gen_entry(name, f16), ())
 
-    def _use_gen_train_f16(self, shape: MlpShape) -> bool:
+    def _use_gen_train(self, shape: MlpShape, model=None) -> bool:
+        return self._force_gen_train or (self.train_any_shape and self._needs_gen(shape, model))
+
+    def _use_gen_train_f16(self, shape: MlpShape, model=None) -> bool:
         """the shape-general training path in f16x3 (train_f16x3_any_shape) instead of exact fp32"""
-        return self._use_gen_train(shape) and bool(self.train_f16x3_any_shape) and self.precision == "f16x3"
+        return self._use_gen_train(shape, model) and bool(self.train_f16x3_any_shape) and self.precision == "f16x3"
 
-    @staticmethod
-    def _gen_training_unsupported(shape: MlpShape):
-        raise NotImplementedError(f"training (autograd through the renderer) supports the standard fusion MLP {tuple(STANDARD_SHAPE)[:6]} only "
-                                  f"unless train_any_shape is set; the shape {tuple(shape)} is supported for inference: call it under "
+    def _gen_training_unsupported(self, shape: MlpShape, model=None):
+        what = f"the shape {tuple(shape)}" + (" with index_interp='bicubic'" if self._bicubic_pad(model) is not None else "")
+        raise NotImplementedError(f"training (autograd through the renderer) supports the standard fusion MLP {tuple(STANDARD_SHAPE)[:6]} "
+                                  f"with a bilinear / nearest lookup only unless train_any_shape is set; {what} is supported for inference: call it under "
                                   "torch.no_grad() or with parameters that do not require grad, or construct the renderer with "
                                   "train_any_shape=True (renderer.train_any_shape: the shape-general fp32 training path)")
 
@@ -426,7 +474,7 @@ class NeRFRendererDGS(torch.nn.Module):
         maps, poses, focal, c, ishape = self._maps_pack
         latent = self._latent_pack if need_latent else None
         linz = None
-        ix = self._latent_index(model)
+        ix = self._index(model)      # (a bicubic model never comes with packed_mlp: no lin_z maps are built for it)
         ring = 2 if ix is not None and ix.padding == _lib.INDEX_PADDING["zeros"] else 0   # zeros padding: the ringed maps
         linz_bytes = 3 * latent.numel() // (latent.shape[2] * latent.shape[3]) * (latent.shape[2] + ring) * (latent.shape[3] + ring) * 4 \
             if latent is not None else 0
@@ -475,6 +523,8 @@ class NeRFRendererDGS(torch.nn.Module):
                          "mlp_gen_packed": nb(self._mlp_gen_pack), "mlp_gen_f16_packed": nb(self._mlp_gen_f16_pack)}}
         rep["cached"]["total"] = sum(rep["cached"].values())
         rep["linz_maps_max_bytes"] = self.linz_maps_max_bytes
+        bicubic = self._bicubic_pad(model) is not None
+        rep["bicubic_index"] = bicubic       # such a model builds no lin_z maps and keeps 16-float tap records per (view, point) row
         if rays_per_call is not None:
             NV = n_views if n_views is not None else (maps.shape[1] if maps is not None else 1)
             K, P = int(self.n_samples), int(rays_per_call) * int(self.n_samples)
@@ -483,7 +533,7 @@ class NeRFRendererDGS(torch.nn.Module):
             rows = NV * P
             # forward keeps: in56 + zlat + taps per (view, point); x, net of the 3 per-view blocks; the post-mean tensors per point
             rep["training_step"] = {"per_view_rows": rows,
-                                    "saved_activations": rows * 4 * (56 + 512 + 8 + 2 * 3 * 512) + P * 4 * (2 * 2 * 512 + 512 + 4),
+                                    "saved_activations": rows * 4 * (56 + 512 + (16 if bicubic else 8) + 2 * 3 * 512) + P * 4 * (2 * 2 * 512 + 512 + 4),
                                     "note": "peak = saved activations + ~8 row-matrices [rows,512] fp32 of forward/backward temporaries "
                                             "(measured: 24.5 GB at 4096 rays x 40 samples x 4 views, tools/bench_train.py)"}
         return rep
@@ -662,19 +712,15 @@ class NeRFRendererDGS(torch.nn.Module):
         z = _f32c(z_samp)
         SB, NR, K = z.shape
         shape = self._route(model)
-        if self._use_gen(shape):
-            f16 = self._use_gen_f16(shape)
+        if self._use_gen(shape, model):
+            f16 = self._use_gen_f16(shape, model)
             packed = self._mlp_shape_general(model, shape, f16)
             sc, _keep = self._scene(model, need_latent=True)
             assert SB == sc.SB
             out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
-            cs, ix = shape.c_struct(), self._latent_index(model)
-            if ix is None:
-                fn, name = self._gen_entry("render_points_gen", f16)
-                check(fn(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
-            else:
-                fn, name = self._gen_entry("render_points_gen_ix", f16)
-                check(fn(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
+            cs = shape.c_struct()
+            fn, name, look = self._gen_lookup("render_points_gen", f16, model)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
             self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
             return out
         packed = self._mlp(model)
@@ -701,12 +747,12 @@ class NeRFRendererDGS(torch.nn.Module):
         z = _f32c(z_samp)
         SB, NR, K = z.shape
         if rgbsigma is None and self._wants_grad(model, rays):
-            shape = self._validate_model(model)
-            if self._use_gen_train(shape):
+            shape = self._validate(model)
+            if self._use_gen_train(shape, model):
                 out = self._forward_train_gen(model, rays, True, shape, z_samples=z).fine
                 return out.weights, out.rgb, out.depth
-            if not shape.standard:
-                self._gen_training_unsupported(shape)
+            if self._needs_gen(shape, model):
+                self._gen_training_unsupported(shape, model)
             out = self._forward_train(model, rays, True, z_samples=z).fine   # differentiable like the reference's composite
             return out.weights, out.rgb, out.depth
         if rgbsigma is None:
@@ -751,14 +797,14 @@ class NeRFRendererDGS(torch.nn.Module):
         :return: ``out.fine.rgb`` [SB,B,3], ``out.fine.depth`` [SB,B], ``out.fine.weights`` iff requested
         """
         assert len(rays.shape) == 3
-        shape = self._validate_model(model)
+        shape = self._validate(model)
         if self._wants_grad(model, rays):
-            if self._use_gen_train(shape):
+            if self._use_gen_train(shape, model):
                 return self._forward_train_gen(model, rays, want_weights, shape, noise=noise, z_samples=z_samples)
-            if not shape.standard:
-                self._gen_training_unsupported(shape)
+            if self._needs_gen(shape, model):
+                self._gen_training_unsupported(shape, model)
             return self._forward_train(model, rays, want_weights, noise=noise, z_samples=z_samples)
-        if z_samples is None and self._use_gen(shape):
+        if z_samples is None and self._use_gen(shape, model):
             return self._forward_gen(model, rays, want_weights, shape, noise)
         with torch.no_grad():
             r = self._check_rays(rays)
@@ -835,13 +881,12 @@ class NeRFRendererDGS(torch.nn.Module):
         K = int(self.n_samples)
         dev = r.device
         big = want_weights or SB * NR > int(self.finite_sync_rays)
-        f16 = self._use_gen_f16(shape)
+        f16 = self._use_gen_f16(shape, model)
         packed = self._mlp_shape_general(model, shape, f16)
         sc, _keep = self._scene(model, need_latent=True)
         assert SB == sc.SB
         cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
-        cs, ix = shape.c_struct(), self._latent_index(model)
-        ixp = C.byref(ix) if ix is not None else None
+        cs = shape.c_struct()
         u_c = n_g = u_f = None
         if noise is not None:
             u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
@@ -853,14 +898,9 @@ class NeRFRendererDGS(torch.nn.Module):
         depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
         weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
         if self.stage_events is None:
-            if ix is None:
-                fn, name = self._gen_entry("render_gen", f16)
-                check(fn(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
-            else:
-                fn, name = self._gen_entry("render_gen_ix", f16)
-                check(fn(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                         _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
+            fn, name, look = self._gen_lookup("render_gen", f16, model)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
+                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
         else:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
@@ -868,8 +908,8 @@ class NeRFRendererDGS(torch.nn.Module):
             check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
                                              None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
             ev[1].record()
-            fn, name = self._gen_entry("render_points_gen_ix", f16)
-            check(fn(C.byref(sc), ixp, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st), name)
+            fn, name, look = self._gen_lookup("render_points_gen", f16, model)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st), name)
             ev[2].record()
             check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
                                     _ptr(depth), _ptr(weights), status, st), "diner_composite")
@@ -896,9 +936,9 @@ class NeRFRendererDGS(torch.nn.Module):
         return self._render_image(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth)
 
     def _render_image_grad(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth):
-        shape = self._validate_model(model)
-        if not shape.standard and not self._use_gen_train(shape):
-            self._gen_training_unsupported(shape)          # before any device work, as forward() raises it
+        shape = self._validate(model)
+        if self._needs_gen(shape, model) and not self._use_gen_train(shape, model):
+            self._gen_training_unsupported(shape, model)          # before any device work, as forward() raises it
         from .training import camera_leaves
         leaves = [model.encoder.latent, *camera_leaves(model, None)[1:], *model.mlp_fine.parameters()]
         H, W = int(H), int(W)
@@ -915,8 +955,8 @@ class NeRFRendererDGS(torch.nn.Module):
         and hand out the generated rays [SB,H*W,8], the samples the compositing used [SB,H*W,K] (workspace layout rays | z | ..., here
         z only: the rays go to rays_out) and the flat rgb [SB,H*W,3] / depth [SB,H*W]."""
         shape = self._route(model, f16_ok=saved is None)   # under autograd (``saved``) the frame is the training path's: exact fp32
-        gen = self._use_gen(shape)
-        f16 = saved is None and self._use_gen_f16(shape)
+        gen = self._use_gen(shape, model)
+        f16 = saved is None and self._use_gen_f16(shape, model)
         dev = target_extrinsics.device
         SB = target_extrinsics.shape[0]
         E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
@@ -938,26 +978,16 @@ class NeRFRendererDGS(torch.nn.Module):
         L = _lib.lib()
         self._poll_status()
         seed = self._next_seed()
-        ix = self._latent_index(model)   # another lookup mode than bilinear / border: the _ix entry points, through ctypes
+        ix = self._index(model)   # another lookup mode than bilinear / border: the _ix (bicubic: _bc) entry points, through ctypes
         rays_out = None if saved is None else torch.empty((SB, H * W, 8), dtype=torch.float32, device=dev)
-        if gen and ix is not None:
+        if gen:
             cs = shape.c_struct()
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
                              dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            fn, name = self._gen_entry("render_image_gen_ix", f16)
-            check(fn(C.byref(sc), C.byref(ix), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed,
-                     _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), name)
-            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
-        elif gen:
-            cs = shape.c_struct()
-            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
-                             dtype=torch.float32, device=dev)
-            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
-            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            fn, name = self._gen_entry("render_image_gen", f16)
-            check(fn(C.byref(sc), C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed, _ptr(ws),
+            fn, name, look = self._gen_lookup("render_image_gen", f16, model)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed, _ptr(ws),
                      _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), name)
             self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
         elif ix is not None:
@@ -1018,7 +1048,7 @@ class NeRFRendererDGS(torch.nn.Module):
         """_forward_train for a model of any shape of the envelope (train_any_shape): the path of diner_amd/training_gen.py, in exact fp32
         or (train_f16x3_any_shape) in f16x3"""
         from . import training_gen
-        f16 = self._use_gen_train_f16(shape)
+        f16 = self._use_gen_train_f16(shape, model)
         if f16:
             self.effective_precision = "f16x3"
         else:
@@ -1094,7 +1124,7 @@ class _RenderImageFn(torch.autograd.Function):
         acc = [None] * len(idx)
         d_rays = torch.zeros_like(rays) if want_t else None
         step = max(1, int(r.grad_chunk_rays))
-        gen = r._use_gen_train(shape)
+        gen = r._use_gen_train(shape, model)
         prec, r.precision = r.precision, ctx.precision
         try:
             with torch.enable_grad():

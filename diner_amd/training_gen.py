@@ -180,7 +180,9 @@ class _Layout:
 
 class _RenderGenFn(torch.autograd.Function):
     """(rays, latent, poses, focal, c, image_shape, depths, *mlp_params) -> (rgb, depth, weights) for fixed samples, any shape of the
-    envelope.  Same contract as ``training._RenderFn`` (``cams``: the caller's leaves, whose versions backward() checks)."""
+    envelope.  Same contract as ``training._RenderFn`` (``cams``: the caller's leaves, whose versions backward() checks).
+    ``ix``: the latent lookup -- None (bilinear / border), a DinerLatentIndex, or an int: the bicubic lookup with that DINER_INDEX_PAD_*
+    (16-float tap records and the _bc entry points of csrc/train_gen_bc.hip)."""
 
     @staticmethod
     def forward(ctx, renderer, scene, ix, keep, cams, shape, f16, z, rays, latent, poses, focal, c_, image_shape, depths, *params):
@@ -210,12 +212,17 @@ class _RenderGenFn(torch.autograd.Function):
             return renderer._weight_split_cache.get(params[i], w_in if i == 0 else prm[i], False) if f16 else None
 
         rgbsigma = f(SB, NR, K, 4)
-        ixp = C.byref(ix) if ix is not None else None
+        bicubic = isinstance(ix, int)
+        ixp = C.byref(ix) if ix is not None and not bicubic else None
         saved = []
         for sb in range(SB):
-            inp, zl, taps = f(R, ld_in), f(R, scene.C), f(R, 8)
-            check(L.diner_train_point_inputs_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
-                                                 _p(taps), st), "diner_train_point_inputs_gen")
+            inp, zl, taps = f(R, ld_in), f(R, scene.C), f(R, 16 if bicubic else 8)
+            if bicubic:
+                check(L.diner_train_point_inputs_gen_bc(C.byref(scene), ix, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
+                                                        _p(taps), st), "diner_train_point_inputs_gen_bc")
+            else:
+                check(L.diner_train_point_inputs_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
+                                                     _p(taps), st), "diner_train_point_inputs_gen")
             x = f(R, H)
             linear_fwd(inp, w_in, prm[1], x, sw=sw(0))                                                # resnetfc.py:139
             blocks = []
@@ -293,7 +300,8 @@ class _RenderGenFn(torch.autograd.Function):
             g_ishape = z0(2) if want["image_shape"] else None
             g_depths = z0((SB, NV, scene.H, scene.W)) if want["depths"] else None
             ws = f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
-        ixp = C.byref(ctx.ix) if ctx.ix is not None else None
+        bicubic = isinstance(ctx.ix, int)
+        ixp = C.byref(ctx.ix) if ctx.ix is not None and not bicubic else None
         lat_nhwc = ctx.keep[1]
         g = [torch.zeros_like(p) for p in prm]          # parameter gradients (fp32, accumulated atomically)
         g_in = torch.zeros_like(ctx.w_in)
@@ -345,10 +353,14 @@ class _RenderGenFn(torch.autograd.Function):
             if cam_any:   # lin_in's input gradient, then the transpose of the point inputs to the geometric leaves
                 d_in = f(R, ld_in)
                 linear_bwd_x(d_x, ctx.w_in, None, d_in, sw=swt(0), amax=a_x)
-                check(L.diner_train_point_inputs_backward_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in), ld_in,
-                                                              _p(d_zl), _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c),
-                                                              _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward_gen")
-            if lay.nlz:
+                bwd, name = ((L.diner_train_point_inputs_backward_gen_bc, "diner_train_point_inputs_backward_gen_bc") if bicubic else
+                             (L.diner_train_point_inputs_backward_gen, "diner_train_point_inputs_backward_gen"))
+                check(bwd(C.byref(scene), ctx.ix if bicubic else ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in), ld_in, _p(d_zl),
+                          _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c), _p(g_ishape), _p(g_depths), st), name)
+            if lay.nlz and bicubic:
+                check(L.diner_train_bicubic_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
+                      "diner_train_bicubic_scatter")
+            elif lay.nlz:
                 check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                       "diner_train_bilinear_scatter")
         d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
@@ -372,7 +384,9 @@ def render_with_grad(renderer, model, rays, z, scene, shape, keep=None, f16=Fals
         raise NotImplementedError(f"combine_layer={shape.combine_layer} >= n_blocks={shape.n_blocks} (no mean over views) with NV={scene.NV}: "
                                   "the reference supports it for one view only (pixelnerf.py:137)")
     params = mlp_params(model.mlp_fine)
-    ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
+    # the encoder's lookup mode (None: bilinear / border; an int: bicubic with that padding, renderer.bicubic_index)
+    pad = renderer._bicubic_pad(model)
+    ix = int(pad) if pad is not None else renderer._latent_index(model)
     cams = camera_leaves(model, rays)
     f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
     return _RenderGenFn.apply(renderer, scene, ix, keep, cams, shape, bool(f16), z, *f32[:1], model.encoder.latent, *f32[1:], *params)

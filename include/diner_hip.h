@@ -359,6 +359,40 @@ int diner_render_image_gen_f16_ix(const DinerScene *scene, const DinerLatentInde
                                   uint64_t seed, float *workspace, float *rays_out, float *rgb_out, float *depth_out,
                                   float *weights_out, uint32_t *status, void *stream);
 
+/* ---- the bicubic latent lookup: SpatialEncoder.index with index_interp="bicubic" (src/models/image_encoder.py:119-125:
+ * F.grid_sample(mode="bicubic", align_corners=False, padding_mode=index_padding) at the feature_padding-rescaled uv of :113-114) on the
+ * shape-general kernels (points_mlp_gen_bc.hip, points_mlp_gen_f16_bc.hip).  ATen's semantics: the centre coordinate
+ * ix = ((u sxl + 1) w - 1) / 2 is neither clipped nor reflected; x0 = floor(ix), tx = ix - x0; four cubic-convolution weights per axis
+ * (A = -0.75) at distances tx + 1, tx, 1 - tx, 2 - tx; the 16 taps sit at (x0 - 1 + i, y0 - 1 + j) and every integer tap position goes
+ * through the padding on its own (border: clamped; reflection: reflected over [-0.5, size - 0.5], then clamped; zeros: a tap outside
+ * the map contributes 0); result = sum_j cy_j (sum_i cx_i texel_ij).  Every index is clamped into the map, whatever the coordinate.
+ * Bicubic does not travel in DinerLatentIndex (the _ix entry points keep rejecting interp = 2): these entry points take the argument
+ * lists of their _gen_ix forms with `padding` (DINER_INDEX_PAD_*) in place of the DinerLatentIndex pointer; any other padding value:
+ * DINER_E_INVALID.  New symbols only: DINER_ABI_VERSION stays 3.  The 512-wide kernels and the lin_z maps do not serve bicubic. */
+/* Replaces PixelNeRF.forward + ResnetFC.forward per point (src/models/pixelnerf.py:55-145, src/models/resnetfc.py:129-159) with the
+ * encoder's index() of src/models/image_encoder.py:97-127 in bicubic mode; mlp_packed from diner_pack_mlp_gen / _gen_f16 */
+int diner_render_points_gen_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,
+                               const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream);
+int diner_render_points_gen_f16_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,
+                                   const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream);
+/* Replace NeRFRendererDGS.forward (src/models/nerf_renderer.py:399-424) for such a model, as diner_render_gen_ix does */
+int diner_render_gen_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,
+                        int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse, const float *n_gauss,
+                        const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out, float *weights_out,
+                        uint32_t *status, void *stream);
+int diner_render_gen_f16_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,
+                            const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                            const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                            float *weights_out, uint32_t *status, void *stream);
+/* Replace the render half of DINER.predict_imgs_from_batch (src/models/diner.py:75-97), as diner_render_image_gen_ix does */
+int diner_render_image_gen_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,
+                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
+                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream);
+int diner_render_image_gen_f16_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,
+                                  const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed,
+                                  float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
+                                  uint32_t *status, void *stream);
+
 /* ---- training path: building blocks of the forward-with-saved-activations and
  * the backward of composite (src/models/nerf_renderer.py:286-365) + PixelNeRF.forward
  * (src/models/pixelnerf.py:55-145) + ResnetFC.forward (src/models/resnetfc.py:129-159), orchestrated by
@@ -492,6 +526,26 @@ int diner_train_point_inputs_backward_gen(const DinerScene *scene, const DinerLa
                                           int64_t ld_in, const float *d_zlat, const float *d_far, float *workspace, float *d_rays,
                                           float *d_poses, float *d_focal, float *d_c, float *d_image_shape, float *d_depths,
                                           void *stream);
+
+/* The same three steps for the bicubic lookup (train_gen_bc.hip; see "the bicubic latent lookup" above; padding: DINER_INDEX_PAD_*).
+ * diner_train_point_inputs_gen_bc replaces SpatialEncoder.index (src/models/image_encoder.py:97-127) next to the inputs of
+ * pixelnerf.py:128, as diner_train_point_inputs_gen does: in_out [R, ld_in], zlat [R, C], and taps [R, 16] = the footprint's 4 columns
+ * and 4 rows (int bits), then the weights cx[4], cy[4] (zeros padding: 0 for a column / row outside the map). */
+int diner_train_point_inputs_gen_bc(const DinerScene *scene, int32_t padding, const float *latent_nhwc, const float *rays, const float *z,
+                                    int64_t NR, int32_t K, int32_t sb, float *in_out, int64_t ld_in, float *zlat, float *taps,
+                                    void *stream);
+/* diner_train_point_inputs_backward_gen for the bicubic lookup: grid_sample's gradient with respect to the grid (autograd of
+ * image_encoder.py:119-125) is sum_ij dcx_i cy_j texel_ij (and cx_i dcy_j) with the cubic weights' derivatives in tx, ty, times
+ * w/2 sxl and h/2 syl; the padding puts no factor on it.  Same 24-column row records, reductions, outputs and workspace. */
+int diner_train_point_inputs_backward_gen_bc(const DinerScene *scene, int32_t padding, const float *latent_nhwc, const float *rays,
+                                             const float *z, int64_t NR, int32_t K, int32_t sb, const float *d_in, int64_t ld_in,
+                                             const float *d_zlat, const float *d_far, float *workspace, float *d_rays, float *d_poses,
+                                             float *d_focal, float *d_c, float *d_image_shape, float *d_depths, void *stream);
+/* diner_train_bilinear_scatter for the 16-tap records of diner_train_point_inputs_gen_bc (grid_sample's input gradient, autograd of
+ * image_encoder.py:119-125): dlatent_nhwc[sb][v][y_j][x_i][ch] += dz[row][ch] * cx_i * cy_j, float atomics, consecutive rows with the
+ * same footprint summed in registers first; the caller zeroes the [SB,NV,h,w,C] buffer. */
+int diner_train_bicubic_scatter(const float *dz, const float *taps, int64_t P, int32_t C, int32_t h, int32_t w, int32_t NV, int32_t sb,
+                                float *dlatent_nhwc, void *stream);
 
 /* ---- shape-general training path in f16x3 (train_gen_f16.hip; renderer.train_f16x3_any_shape) ------------------------------- */
 /* diner_train_gemm_act in the arithmetic of diner_train_gemm's DINER_PRECISION_F16X3 mode: the activation is applied in fp32, then each
