@@ -67,6 +67,17 @@ class DinerLatentIndex(C.Structure):
     _fields_ = [("interp", C.c_int32), ("padding", C.c_int32)]
 
 
+class DinerLatentLevel(C.Structure):
+    _fields_ = [("data", _FP), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+LATENT_MAX_LEVELS = 5   # DINER_LATENT_MAX_LEVELS
+
+
+class DinerLatentLevels(C.Structure):
+    _fields_ = [("level", DinerLatentLevel * LATENT_MAX_LEVELS)]
+
+
 # SpatialEncoder's index_interp / index_padding (reference src/models/image_encoder.py:24-25) -> DINER_INDEX_* of include/diner_hip.h
 INDEX_INTERP = {"bilinear": 0, "nearest": 1}
 INDEX_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
@@ -190,6 +201,10 @@ SYMBOLS = {
     "diner_train_point_inputs_backward_gen_bc": (C.c_int, [C.POINTER(DinerScene), _I32, _P, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P,
                                                            _P, _P, _P, _P, _P, _P]),
     "diner_train_bicubic_scatter": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    # the latent assembled from the encoder's feature pyramid in diner_pack_latent's layout, and its adjoint (csrc/latent_assemble.hip;
+    # the ABI version stays 3: new entry points only)
+    "diner_assemble_latent": (C.c_int, [C.POINTER(DinerLatentLevels), _I32, _I64, _I32, _I32, _P, _P]),
+    "diner_assemble_latent_backward": (C.c_int, [_P, _I32, _I64, _I32, _I32, C.POINTER(DinerLatentLevels), _P]),
 }
 
 _lib = None

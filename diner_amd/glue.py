@@ -4,6 +4,9 @@ with the reference's own function signatures so they can replace them in place:
 * :func:`gen_rays`      -- reference ``src/util/cam_geometry.py:36-79`` (differentiable in the cameras, near and far, like the
   reference's plain-torch version: the backward is ``diner_gen_rays_backward``)
 * :func:`depth2normal`  -- reference ``src/util/depth2normal.py:7-87``
+
+and the tail of the encoder: :func:`assemble_latent` -- reference ``src/models/image_encoder.py:262-272`` (the feature levels upsampled to
+the first one's size and concatenated), written once in the NHWC layout the render and training kernels read.
 """
 from __future__ import annotations
 
@@ -135,3 +138,90 @@ def pack_maps_from_depth(depths, depths_std, intrinsics):
     check(_lib.lib().diner_pack_maps_from_depth(d.data_ptr(), s.data_ptr(), k.data_ptr(), SB * NV, H, W, out.data_ptr(),
                                                 _st(d.device)), "diner_pack_maps_from_depth")
     return out
+
+
+def _levels_struct(ts):
+    lv = _lib.DinerLatentLevels()
+    for i, t in enumerate(ts):
+        lv.level[i].data, lv.level[i].C, lv.level[i].h, lv.level[i].w = t.data_ptr(), t.shape[1], t.shape[2], t.shape[3]
+    return lv
+
+
+def _assemble_check(levels, SB, NV, mode):
+    if mode != "bilinear":   # (the reference's nearest branch is unreachable: it compares with "nearest ", image_encoder.py:262)
+        raise NotImplementedError(f"assemble_latent: upsample mode {mode!r} is not implemented (the encoder's tail is bilinear, "
+                                  "align_corners=True)")
+    levels = list(levels)
+    if not 1 <= len(levels) <= _lib.LATENT_MAX_LEVELS:
+        raise ValueError(f"assemble_latent: {len(levels)} levels, expected 1..{_lib.LATENT_MAX_LEVELS}")
+    N = int(SB) * int(NV)
+    for t in levels:
+        if not t.is_cuda:
+            raise RuntimeError("diner_amd.glue.assemble_latent runs on the GPU only")
+        if t.dim() != 4 or t.shape[0] != N:
+            raise ValueError(f"assemble_latent: a level must be [SB*NV = {N}, C_l, h_l, w_l], not {tuple(t.shape)}")
+    return levels
+
+
+def _assemble(lv, SB, NV):
+    """fp32 contiguous levels [SB*NV, C_l, h_l, w_l] -> the NHWC buffer [SB, NV, h, w, C]"""
+    h, w = lv[0].shape[2:]
+    out = torch.empty((SB, NV, h, w, sum(t.shape[1] for t in lv)), dtype=torch.float32, device=lv[0].device)
+    check(_lib.lib().diner_assemble_latent(C.byref(_levels_struct(lv)), len(lv), SB * NV, h, w, out.data_ptr(), _st(out.device)),
+          "diner_assemble_latent")
+    return out
+
+
+def assemble_latent_backward(d_latent, level_shapes):
+    """Adjoint of :func:`assemble_latent`: d_latent of logical shape [SB, NV, C, h, w] (made NHWC-strided fp32 once if it is not) ->
+    the levels' gradients [SB*NV, C_l, h_l, w_l] in fp32 (``diner_assemble_latent_backward``: gather form, bitwise reproducible)."""
+    SB, NV, _, h, w = d_latent.shape
+    g = d_latent.detach().permute(0, 1, 3, 4, 2)
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        g = g.to(torch.float32).contiguous()
+    grads = [torch.empty(tuple(s), dtype=torch.float32, device=g.device) for s in level_shapes]
+    check(_lib.lib().diner_assemble_latent_backward(g.data_ptr(), len(grads), SB * NV, h, w, C.byref(_levels_struct(grads)), _st(g.device)),
+          "diner_assemble_latent_backward")
+    return grads
+
+
+class _AssembleLatentFn(torch.autograd.Function):
+    """assemble_latent with a backward: forward = diner_assemble_latent (the no-grad call's values), backward = its adjoint kernel"""
+
+    @staticmethod
+    def forward(ctx, SB, NV, *levels):
+        lv = [_f(t) for t in levels]
+        ctx.shapes, ctx.dtypes = [tuple(t.shape) for t in lv], [t.dtype for t in levels]
+        return _assemble(lv, SB, NV).permute(0, 1, 4, 2, 3)
+
+    @staticmethod
+    def backward(ctx, d_latent):
+        grads = assemble_latent_backward(d_latent, ctx.shapes)
+        return (None, None, *[g.to(dt) if need else None for g, dt, need in zip(grads, ctx.dtypes, ctx.needs_input_grad[2:])])
+
+
+def assemble_latent(levels, SB, NV, mode="bilinear"):
+    """The tail of ``SpatialEncoder.forward`` (reference src/models/image_encoder.py:262-272) in one kernel: ``levels`` = the feature
+    pyramid, a list of 1..5 tensors [SB*NV, C_l, h_l, w_l]; every level is upsampled to ``levels[0]``'s (h, w) like
+    ``F.interpolate(mode="bilinear", align_corners=True)`` and the results are concatenated along the channels.
+    Returns the latent in its logical shape [SB, NV, C, h, w] with NHWC storage: ``buf.permute(0, 1, 4, 2, 3)`` of a contiguous
+    [SB, NV, h, w, C] buffer, the layout the render and training kernels read -- :func:`latent_is_packed` is true for it and the renderer
+    then takes the buffer as it is (no copy, no re-pack).  ``.shape``, ``grid_sample`` and indexing see an ordinary tensor.
+    Differentiable with respect to every level (``diner_assemble_latent_backward``, deterministic)."""
+    levels = _assemble_check(levels, SB, NV, mode)
+    SB, NV = int(SB), int(NV)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in levels):
+        return _AssembleLatentFn.apply(SB, NV, *levels)
+    with torch.no_grad():
+        return _assemble([_f(t) for t in levels], SB, NV).permute(0, 1, 4, 2, 3)
+
+
+def nhwc_strided(t) -> bool:
+    """a 5-d fp32 tensor of logical shape [SB, NV, C, h, w] whose storage is a contiguous [SB, NV, h, w, C] buffer"""
+    return isinstance(t, torch.Tensor) and t.dim() == 5 and t.dtype == torch.float32 and t.permute(0, 1, 3, 4, 2).is_contiguous()
+
+
+def latent_is_packed(t) -> bool:
+    """True when ``t`` [SB, NV, C, h, w] already has the layout the kernels read (what :func:`assemble_latent` returns):
+    ``t.permute(0, 1, 3, 4, 2)`` is a contiguous fp32 CUDA tensor."""
+    return nhwc_strided(t) and t.is_cuda

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import DinerMlpRaw, DinerSamplerCfg, DinerScene, check
+from .glue import latent_is_packed
 
 
 class MlpShape(NamedTuple):
@@ -216,6 +217,7 @@ class NeRFRendererDGS(torch.nn.Module):
         self._calls = 0
         self._maps_key = self._maps_pack = None      # packed depth/sigma/normal maps + cameras
         self._latent_key = self._latent_pack = None  # packed NHWC latent
+        self._latent_shared = False                  # the pack IS encoder.latent's storage (glue.assemble_latent's layout)
         self._linz_key = self._linz_pack = None      # lin_z[b](latent) feature maps (f16x3 mode)
         # f16x3 mode: hoist lin_z from per point to per latent texel (linear map and bilinear interpolation
         # commute; diner_pack_linz_maps).  Costs 3x the latent's memory per encode(); set False to keep
@@ -463,13 +465,17 @@ class NeRFRendererDGS(torch.nn.Module):
             self._maps_pack, self._maps_key = (maps, poses, _f32c(model.focal), _f32c(model.c), ishape), _Sources(msrc)
         if need_latent:
             if self._latent_key is None or not self._latent_key.valid_for([enc.latent]):
-                lat = _f32c(enc.latent)
-                SB, NV, Cc, h, w = lat.shape
-                latent = torch.empty((SB, NV, h, w, Cc), dtype=torch.float32, device=dev)
-                check(_lib.lib().diner_pack_latent(_ptr(lat), SB * NV, Cc, h, w, _ptr(latent), _stream(dev)),
-                      "diner_pack_latent")
-                torch.cuda.current_stream(dev).synchronize()
+                if latent_is_packed(enc.latent):   # glue.assemble_latent's layout: the latent's own buffer is the pack (no copy)
+                    latent = enc.latent.detach().permute(0, 1, 3, 4, 2)
+                else:
+                    lat = _f32c(enc.latent)
+                    SB, NV, Cc, h, w = lat.shape
+                    latent = torch.empty((SB, NV, h, w, Cc), dtype=torch.float32, device=dev)
+                    check(_lib.lib().diner_pack_latent(_ptr(lat), SB * NV, Cc, h, w, _ptr(latent), _stream(dev)),
+                          "diner_pack_latent")
+                    torch.cuda.current_stream(dev).synchronize()
                 self._latent_pack, self._latent_key = latent, _Sources([enc.latent])
+                self._latent_shared = latent.data_ptr() == enc.latent.data_ptr()   # (memory_report: one buffer, not two)
                 self._latent_gen += 1
         maps, poses, focal, c, ishape = self._maps_pack
         latent = self._latent_pack if need_latent else None
@@ -513,7 +519,8 @@ class NeRFRendererDGS(torch.nn.Module):
 
     def memory_report(self, model=None, rays_per_call=None, n_views=None):
         """Bytes of device memory this renderer holds / will take, so that the appetite is a number and not a surprise:
-        ``cached`` = what the pack caches hold right now (packed maps, NHWC latent, lin_z maps, packed MLP); with ``rays_per_call``
+        ``cached`` = what the pack caches hold right now (packed maps, NHWC latent, lin_z maps, packed MLP; ``latent_zero_copy``: the NHWC
+        latent is the model's own buffer, glue.assemble_latent's, and no second copy exists); with ``rays_per_call``
         (and ``n_views``, default: the cached scene's) also ``per_call`` = workspace + outputs of one inference ``forward`` and
         ``training_step`` = the activations the differentiable path keeps alive between forward and backward
         (diner_amd/training.py: every layer's input in fp32, 24 GB for 4096 rays x 40 samples x 4 views)."""
@@ -522,6 +529,8 @@ class NeRFRendererDGS(torch.nn.Module):
         rep = {"cached": {"maps": nb(maps), "latent_nhwc": nb(self._latent_pack), "linz_maps": nb(self._linz_pack), "mlp_packed": nb(self._mlp_pack),
                          "mlp_gen_packed": nb(self._mlp_gen_pack), "mlp_gen_f16_packed": nb(self._mlp_gen_f16_pack)}}
         rep["cached"]["total"] = sum(rep["cached"].values())
+        # a latent in glue.assemble_latent's layout is counted once: "latent_nhwc" is then encoder.latent's own storage, not a second copy
+        rep["latent_zero_copy"] = bool(self._latent_shared and self._latent_pack is not None)
         rep["linz_maps_max_bytes"] = self.linz_maps_max_bytes
         bicubic = self._bicubic_pad(model) is not None
         rep["bicubic_index"] = bicubic       # such a model builds no lin_z maps and keeps 16-float tap records per (view, point) row

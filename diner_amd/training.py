@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .glue import latent_is_packed
 
 HID = 512
 K_CHUNK = 4096  # rows per split of the weight-gradient GEMMs (multiple of 16)
@@ -202,10 +203,14 @@ class _RenderFn(torch.autograd.Function):
         NV, P = scene.NV, NR * K
         R = NV * P
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        lat = latent.detach().to(torch.float32).contiguous()
-        SBl, NVl, Cl, hl, wl = lat.shape
-        lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)   # coalesced texel reads for the gather
-        check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+        ctx.lat_packed = latent_is_packed(latent)
+        if ctx.lat_packed:   # glue.assemble_latent's layout: the gathers read the latent's own buffer
+            lat, lat_nhwc = None, latent.detach().permute(0, 1, 3, 4, 2)
+        else:
+            lat = latent.detach().to(torch.float32).contiguous()
+            SBl, NVl, Cl, hl, wl = lat.shape
+            lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)   # coalesced texel reads for the gather
+            check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
         prm = [p.detach().to(torch.float32).contiguous() for p in params]
         # backward() re-reads these tensors (they alias the live parameters): remember their versions, as
         # ctx.save_for_backward would, so that an in-place update between forward and backward is an error instead of a
@@ -365,8 +370,11 @@ class _RenderFn(torch.autograd.Function):
                                                           _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward")
             check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, HID, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                   "diner_train_bilinear_scatter")
-        d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
-        check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+        if ctx.lat_packed:   # the gradient in the latent's own (NHWC) strides: glue.assemble_latent's backward reads it as it is
+            d_lat = d_lat_nhwc.permute(0, 1, 4, 2, 3)
+        else:
+            d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
+            check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
         g[0] = g_in56[:, :55].contiguous()
         g[1] = g[3].clone()  # lin_in's bias sees the same dY as lin_z[0]'s: x = lin_in(..) + lin_z[0](z)
         cam = (None,) * 6

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .glue import latent_is_packed
 from .training import CAMERA_INPUTS, EXP_ACT, EXP_W, camera_leaves
 
 K_CHUNK = 4096  # rows per split of the weight-gradient GEMMs (multiple of 32)
@@ -197,10 +198,14 @@ class _RenderGenFn(torch.autograd.Function):
         H, F = shape.d_hidden, shape.num_freqs
         ld_in = 8 * (F + 1)
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        lat = latent.detach().to(torch.float32).contiguous()
-        SBl, NVl, Cl, hl, wl = lat.shape
-        lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
-        check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+        ctx.lat_packed = latent_is_packed(latent)
+        if ctx.lat_packed:   # glue.assemble_latent's layout: the gathers read the latent's own buffer
+            lat, lat_nhwc = None, latent.detach().permute(0, 1, 3, 4, 2)
+        else:
+            lat = latent.detach().to(torch.float32).contiguous()
+            SBl, NVl, Cl, hl, wl = lat.shape
+            lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
+            check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
         prm = [p.detach().to(torch.float32).contiguous() for p in params]
         # backward() re-reads these tensors: an in-place update between forward and backward must be an error (training._RenderFn)
         ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
@@ -363,8 +368,11 @@ class _RenderGenFn(torch.autograd.Function):
             elif lay.nlz:
                 check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                       "diner_train_bilinear_scatter")
-        d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
-        check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+        if ctx.lat_packed:   # the gradient in the latent's own (NHWC) strides: glue.assemble_latent's backward reads it as it is
+            d_lat = d_lat_nhwc.permute(0, 1, 4, 2, 3)
+        else:
+            d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
+            check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
         g[0] = g_in[:, :shape.d_in].contiguous()
         cam = (None,) * 6
         if cam_any:

@@ -162,6 +162,32 @@ int diner_decode_depth_u16(const uint16_t *depth, const uint16_t *conf, const ui
  * the MLP kernel stages into LDS (C = 512; any other multiple of 8 up to 1024 for the shape-general path) */
 int diner_pack_latent(const float *latent_nchw, int64_t N, int32_t C, int32_t h, int32_t w,
                       float *latent_out, void *stream);
+/* ---- the latent assembled from the encoder's feature pyramid, directly in diner_pack_latent's layout ----
+ * Replaces the tail of SpatialEncoder.forward (src/models/image_encoder.py:262-272): every level upsampled to the first level's size
+ * with F.interpolate(mode="bilinear", align_corners=True), then torch.cat along the channels -- and the diner_pack_latent that followed.
+ * A level: NCHW [N, C, h, w], contiguous; C a multiple of 8; a level may be larger or smaller than the output.  The output has
+ * C = sum of the levels' C (at most 1024, diner_pack_latent's limit), N = SB * NV images; element offsets are 64-bit.
+ *   out[n, y, x, off_l + c] = bilinear(level_l[n, c])(y, x) with ATen's align_corners=True taps: scale = (in - 1) / (out - 1) in fp32
+ *   (0 when out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1,
+ *   value = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d): a level of the output's size comes out bit-identical.
+ * diner_assemble_latent_backward is the exact adjoint in gather form: every coarse texel sums weight * d_out over the fine pixels whose
+ * i0 or i1 is that texel, in a fixed order (no atomics: run-to-run deterministic), with the taps of the same device function as the
+ * forward.  levels_grad: the levels' shapes with `data` = the gradient buffers, NCHW, every element of which is WRITTEN (no pre-zeroing;
+ * the descriptor is shared by both directions, hence the const of the field).
+ * Before any launch: DINER_E_INVALID for a NULL pointer, n_levels outside 1..DINER_LATENT_MAX_LEVELS or a non-positive size;
+ * DINER_E_UNSUPPORTED for a channel count outside the envelope (or N > 65535 images). */
+#define DINER_LATENT_MAX_LEVELS 5
+typedef struct DinerLatentLevel {
+    const float *data;       /* [N, C, h, w] */
+    int32_t C, h, w;
+} DinerLatentLevel;
+typedef struct DinerLatentLevels {
+    DinerLatentLevel level[DINER_LATENT_MAX_LEVELS];   /* the first n_levels are read */
+} DinerLatentLevels;
+int diner_assemble_latent(const DinerLatentLevels *levels, int32_t n_levels, int64_t N, int32_t h, int32_t w, float *out_nhwc,
+                          void *stream);
+int diner_assemble_latent_backward(const float *d_out_nhwc, int32_t n_levels, int64_t N, int32_t h, int32_t w,
+                                   const DinerLatentLevels *levels_grad, void *stream);
 /* ---- once per weight version: MFMA-fragment-ordered copies of the fusion MLP (one image per
  * precision mode, both in the same buffer) ------------------------------------------------ */
 int64_t diner_mlp_packed_floats(void);
