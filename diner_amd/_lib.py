@@ -205,6 +205,17 @@ SYMBOLS = {
     # the ABI version stays 3: new entry points only)
     "diner_assemble_latent": (C.c_int, [C.POINTER(DinerLatentLevels), _I32, _I64, _I32, _I32, _P, _P]),
     "diner_assemble_latent_backward": (C.c_int, [_P, _I32, _I64, _I32, _I32, C.POINTER(DinerLatentLevels), _P]),
+    # lin_z hoisted into per-texel maps on the shape-general kernels: the *_gen_ix argument lists, then precision (PRECISIONS), the bicubic
+    # padding (-1: not bicubic, else INDEX_PADDING) and the maps of diner_pack_linz_maps_gen (the ABI version stays 3: new entry points only)
+    "diner_linz_maps_gen_floats": (_I64, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape)]),
+    "diner_pack_linz_maps_gen": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape), _P, _P, _P]),
+    "diner_render_points_gen_lz": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _P,
+                                             _I64, _I32, _P, _P, _I32, _I32, _P]),
+    "diner_render_gen_lz": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P, _P, _I64,
+                                      C.POINTER(DinerSamplerCfg), _I32, _P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _I32, _I32, _P]),
+    "diner_render_image_gen_lz": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P,
+                                            C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P,
+                                            _I32, _I32, _P]),
 }
 
 _lib = None

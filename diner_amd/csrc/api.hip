@@ -122,12 +122,18 @@ int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
 int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t,
                       int bicubic_pad = -1);
+int launch_points_mlp_lz(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *,
+                         hipStream_t, int bicubic_pad, const float *lzmaps);
+int64_t linz_maps_floats(const DinerMlpShape &, int64_t texels);
+int launch_linz_maps(const DinerMlpShape &, const float *, int64_t, const float *, float *, hipStream_t);
 }
 namespace genf16 {
 int64_t packed_floats(const DinerMlpShape &);
 int launch_pack_mlp(const DinerMlpShape &, const DinerMlpGenRaw &, float *, hipStream_t);
 int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t,
                       int bicubic_pad = -1);
+int launch_points_mlp_lz(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *,
+                         hipStream_t, int bicubic_pad, const float *lzmaps);
 }
 
 int launch_train_point_inputs_gen_bc(const DinerScene &, int, const float *, const float *, const float *, int64_t, int, int, float *, int64_t,
@@ -755,7 +761,7 @@ int diner_pack_mlp_gen_f16(const DinerMlpShape *shape, const DinerMlpGenRaw *raw
 /* bicubic_pad >= 0: the bicubic lookup with that padding (the _bc entry points; index is then NULL) */
 static int render_points_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
                              const float *mlp_packed, const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out,
-                             void *stream, int bicubic_pad = -1)
+                             void *stream, int bicubic_pad = -1, const float *lz = nullptr)
 {
     int rc;
     if (!shape) return bad("render_points_gen: shape is NULL");
@@ -766,6 +772,10 @@ static int render_points_gen(bool f16, const DinerScene *scene, const DinerLaten
     if (!mlp_packed) return bad("render_points_gen: mlp_packed is NULL");
     if (f16 && (uintptr_t)mlp_packed % 16) return bad("render_points_gen_f16: mlp_packed not 16-byte aligned");
     if (NR > 0 && scene->SB > 0 && (!rays || !z || !rgbsigma_out)) return bad("render_points_gen: NULL rays / z / out");
+    if (lz)   /* the lin_z-map forms (the _lz entry points, nlz > 0) */
+        return (f16 ? genf16::launch_points_mlp_lz : gen::launch_points_mlp_lz)(*scene, index ? *index : k_default_index, *shape, mlp_packed,
+                                                                                 rays, z, NR, K, rgbsigma_out, (hipStream_t)stream,
+                                                                                 bicubic_pad, lz);
     return (f16 ? genf16::launch_points_mlp : gen::launch_points_mlp)(*scene, index ? *index : k_default_index, *shape, mlp_packed, rays, z,
                                                                        NR, K, rgbsigma_out, (hipStream_t)stream, bicubic_pad);
 }
@@ -773,7 +783,7 @@ static int render_points_gen(bool f16, const DinerScene *scene, const DinerLaten
 static int render_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
                       const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
                       const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
-                      float *weights_out, uint32_t *status, void *stream, int bicubic_pad = -1)
+                      float *weights_out, uint32_t *status, void *stream, int bicubic_pad = -1, const float *lz = nullptr)
 {
     int rc;
     if (!shape) return bad("render_gen: shape is NULL");
@@ -785,14 +795,14 @@ static int render_gen(bool f16, const DinerScene *scene, const DinerLatentIndex 
     const int64_t N = (int64_t)scene->SB * NR;
     float *z = workspace, *rgbsigma = workspace + N * cfg->n_samples;
     if ((rc = diner_sample_depthguided(scene, rays, NR, cfg, u_coarse, n_gauss, u_fill, nullptr, seed, z, nullptr, nullptr, stream))) return rc;
-    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad, lz))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
 static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape,
                             const float *mlp_packed, const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd,
                             uint64_t seed, float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
-                            uint32_t *status, void *stream, int bicubic_pad = -1)
+                            uint32_t *status, void *stream, int bicubic_pad = -1, const float *lz = nullptr)
 {
     int rc;
     if (!shape) return bad("render_image_gen: shape is NULL");
@@ -808,7 +818,7 @@ static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatent
     if ((rc = launch_sampler(*scene, nullptr, cam, rays, NR, *cfg, nullptr, nullptr, nullptr, nullptr, seed, z, nullptr, nullptr,
                              (hipStream_t)stream)))
         return rc;
-    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad))) return rc;
+    if ((rc = render_points_gen(f16, scene, index, shape, mlp_packed, rays, z, NR, cfg->n_samples, rgbsigma, stream, bicubic_pad, lz))) return rc;
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
@@ -892,6 +902,89 @@ DINER_GEN_ENTRY_POINTS(_f16, true)
 DINER_GEN_BC_ENTRY_POINTS(, false)
 DINER_GEN_BC_ENTRY_POINTS(_f16, true)
 #undef DINER_GEN_BC_ENTRY_POINTS
+
+/* ---- lin_z hoisted into per-texel maps (linz_maps_gen.hip, points_mlp_gen_lz.hip, points_mlp_gen_f16_lz.hip and their _bc twins) -- */
+int64_t diner_linz_maps_gen_floats(const DinerScene *scene, const DinerMlpShape *shape)
+{
+    if (!scene || !shape) return bad("linz_maps_gen_floats: NULL pointer");
+    const int rc = gen::check_shape(*shape);
+    if (rc) return rc;
+    if (scene->SB < 0 || scene->NV <= 0 || scene->h <= 0 || scene->w <= 0) return bad("linz_maps_gen_floats: bad SB / NV / h / w");
+    return gen::linz_maps_floats(*shape, (int64_t)scene->SB * scene->NV * scene->h * scene->w);
+}
+
+int diner_pack_linz_maps_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, float *maps_out, void *stream)
+{
+    if (!scene || !shape || !mlp_packed || !maps_out) return bad("pack_linz_maps_gen: NULL pointer");
+    const int rc = gen::check_shape(*shape);
+    if (rc) return rc;
+    if (scene->SB < 0 || scene->NV <= 0 || scene->h <= 0 || scene->w <= 0) return bad("pack_linz_maps_gen: bad SB / NV / h / w");
+    if (!scene->latent) return bad("pack_linz_maps_gen: scene latent is NULL");
+    if (scene->C != shape->d_latent) {
+        set_error("pack_linz_maps_gen: latent channels C=%d != d_latent=%d", scene->C, shape->d_latent);
+        return DINER_E_INVALID;
+    }
+    return gen::launch_linz_maps(*shape, scene->latent, (int64_t)scene->SB * scene->NV * scene->h * scene->w, mlp_packed, maps_out,
+                                 (hipStream_t)stream);
+}
+
+/* precision, bicubic_padding and the maps of the _lz entry points -> f16, the maps to hand on (NULL when nlz = 0: the parent's route) */
+static int check_lz(const DinerMlpShape *shape, int32_t precision, int32_t bicubic_padding, const float *maps, const char *who, bool &f16,
+                    const float *&lz)
+{
+    if (precision != DINER_PRECISION_FP32 && precision != DINER_PRECISION_F16X3) {
+        set_error("%s: precision=%d unknown (DINER_PRECISION_FP32 0 or DINER_PRECISION_F16X3 1)", who, precision);
+        return DINER_E_INVALID;
+    }
+    if (bicubic_padding != -1 && check_bicubic_padding(bicubic_padding, who)) return DINER_E_INVALID;
+    if (!shape) { set_error("%s: shape is NULL", who); return DINER_E_INVALID; }
+    const int rc = gen::check_shape(*shape);
+    if (rc) return rc;
+    const bool has_lz = shape->combine_layer > 0;   /* nlz = min(combine_layer, n_blocks) > 0 */
+    if (has_lz && !maps) { set_error("%s: linz_maps_gen is NULL (the shape has lin_z layers: diner_pack_linz_maps_gen)", who); return DINER_E_INVALID; }
+    f16 = precision == DINER_PRECISION_F16X3;
+    lz = has_lz ? maps : nullptr;
+    return DINER_OK;
+}
+
+int diner_render_points_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                               const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream,
+                               int32_t precision, int32_t bicubic_padding, const float *linz_maps_gen)
+{
+    bool f16;
+    const float *lz;
+    int rc;
+    if ((rc = check_lz(shape, precision, bicubic_padding, linz_maps_gen, "render_points_gen_lz", f16, lz))) return rc;
+    return render_points_gen(f16, scene, bicubic_padding >= 0 ? nullptr : index, shape, mlp_packed, rays, z, NR, K, rgbsigma_out, stream,
+                             bicubic_padding, lz);
+}
+
+int diner_render_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                        const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                        const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                        float *weights_out, uint32_t *status, void *stream, int32_t precision, int32_t bicubic_padding,
+                        const float *linz_maps_gen)
+{
+    bool f16;
+    const float *lz;
+    int rc;
+    if ((rc = check_lz(shape, precision, bicubic_padding, linz_maps_gen, "render_gen_lz", f16, lz))) return rc;
+    return render_gen(f16, scene, bicubic_padding >= 0 ? nullptr : index, shape, mlp_packed, rays, NR, cfg, white_bkgd, u_coarse, n_gauss,
+                      u_fill, seed, workspace, rgb_out, depth_out, weights_out, status, stream, bicubic_padding, lz);
+}
+
+int diner_render_image_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
+                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream,
+                              int32_t precision, int32_t bicubic_padding, const float *linz_maps_gen)
+{
+    bool f16;
+    const float *lz;
+    int rc;
+    if ((rc = check_lz(shape, precision, bicubic_padding, linz_maps_gen, "render_image_gen_lz", f16, lz))) return rc;
+    return render_image_gen(f16, scene, bicubic_padding >= 0 ? nullptr : index, shape, mlp_packed, cam, cfg, white_bkgd, seed, workspace,
+                            rays_out, rgb_out, depth_out, weights_out, status, stream, bicubic_padding, lz);
+}
 
 int diner_train_point_inputs_gen_bc(const DinerScene *scene, int32_t padding, const float *latent_nhwc, const float *rays, const float *z,
                                     int64_t NR, int32_t K, int32_t sb, float *in_out, int64_t ld_in, float *zlat, float *taps, void *stream)

@@ -233,6 +233,7 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[RB][CT], float *A,
     }
 }
 
+#ifndef DINER_GEN_MAPS   // linz_maps_gen.hip takes the layout and gemm() above only
 struct Tap {        // bilinear footprint of one (point, view) in the latent map
     int o00, o01, o10, o11;  // float4 offsets of the 4 texels (clamped, always readable)
     float nw, ne, sw, se;    // weights; a tap outside the map has its weight forced to 0
@@ -248,7 +249,29 @@ struct TapBc {      // bicubic footprint of one (point, view) in the latent map 
 // unit keeps this one's code object -- the three bilinear / border kernels -- exactly what it was.
 // points_mlp_gen_bc.hip compiles it a third time with DINER_GEN_BC (and DINER_GEN_IX) defined: points_mlp_gen_bc_kernel, the 16-tap
 // bicubic lookup (common.hpp bicubic_footprint) with the padding ix_padding, again in a code object of its own.
-#ifdef DINER_GEN_BC
+// points_mlp_gen_lz.hip and points_mlp_gen_lz_bc.hip compile it with DINER_GEN_LZ on top of DINER_GEN_IX (and DINER_GEN_BC): the lin_z-map
+// forms points_mlp_gen_lz_kernel / points_mlp_gen_lz_bc_kernel.  lin_z[b] is linear and the lookup a weighted sum of texels, so
+// lin_z[b](lookup(F)) = sum_i w_i (W_b F_i) + bias_b: instead of gathering d_latent channels and multiplying per point, view and block they
+// gather d_hidden channels of the map M_b = W_b F (linz_maps_gen.hip; no bias in it, so it is exactly linear in the taps and every
+// lookup mode, bicubic's negative weights and zeros padding's missing taps included, reads the same maps) and add them to x.
+#if defined(DINER_GEN_LZ) && defined(DINER_GEN_BC)
+constexpr int TAP_F4 = 4;
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_lz_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                           const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                           int64_t NR, int K, float *__restrict__ rgbsigma, int ix_padding,
+                                                                           const float *__restrict__ lzmaps)
+{
+#elif defined(DINER_GEN_LZ)
+constexpr int TAP_F4 = 2;
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_lz_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                        const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                        int64_t NR, int K, float *__restrict__ rgbsigma, int ix_interp,
+                                                                        int ix_padding, const float *__restrict__ lzmaps)
+{
+    constexpr bool GIX = true;
+#elif defined(DINER_GEN_BC)
 constexpr int TAP_F4 = 4;   // float4 entries of one row's tap record in LDS
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
@@ -315,7 +338,11 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
     const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
     const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
     const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1, din_pad = 8 * L.njb_in;
+#ifdef DINER_GEN_LZ
+    const int c4 = H / 4;        // float4 per texel of a lin_z map: the taps address the maps, the latent itself is never read
+#else
     const int c4 = L.dlat / 4;   // float4 per latent texel
+#endif
 
     for (int v = 0; v < s.NV; ++v) {
         // ---- geometry + positional encodings -> A[:, 0:din_pad]; bilinear footprint -> taps ----------
@@ -381,9 +408,65 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
         gemm(x, A4, (const f32x4 *)(Wp + L.off_in), L.njb_in, 0, L.njb_in, rb0, ct0, NT, lane);   // resnetfc.py:139
         __syncthreads();
 
+#ifndef DINER_GEN_LZ
         const f32x4 *lat = (const f32x4 *)s.latent + ((int64_t)sb * s.NV + v) * s.h * s.w * c4;
+#endif
         for (int b = 0; b < L.nvb; ++b) {
             acc_bias(x, bias + L.bias_lin_z(b), true, ct0, NT, lane);                               // :152-153 x = x + lin_z(z)
+#ifdef DINER_GEN_LZ
+            {
+                // ---- (W_b z)[:, 0 : H] = the lookup of the 64 points in map M_b -> LDS as fp32 [row][LD], column ^ 32 for the rows of lane
+                // half 1 (the two halves of a wave read rows 4 apart: 64 banks, no conflict); then every lane adds the elements of its
+                // accumulators (the C/D layout of the 32x32 MFMA, store_act's index map read backwards).  While H <= 256 the staging area
+                // lies behind the columns store_act writes next, and no barrier is needed between the adds and that store.
+                const int LD = (H + 63) & ~63;
+                const bool apart = (H + LD) * TILE_P <= A_F4 * 4;
+                float *S = A + (apart ? H * TILE_P : 0);
+                const f32x4 *mp = (const f32x4 *)lzmaps + (((int64_t)b * s.SB + sb) * s.NV + v) * s.h * s.w * c4;
+                for (int idx = lane; idx < (TILE_P / NWAVES) * c4; idx += 64) {   // a wave gathers 8 rows, c4 quads each
+                    const int rr = idx / c4, q = idx - rr * c4, r = wave * (TILE_P / NWAVES) + rr;
+                    f32x4 val;
+#ifdef DINER_GEN_BC
+                    const TapBc *tp = taps + r;   // rows then columns, contracted FMAs: the gather of the bicubic kernel
+                    const f32x4 *lq = mp + q;
+                    const int x0 = tp->xo[0], x1 = tp->xo[1], x2 = tp->xo[2], x3 = tp->xo[3];
+                    const float w0 = tp->cx[0], w1 = tp->cx[1], w2 = tp->cx[2], w3 = tp->cx[3];
+#pragma unroll BC_ROW_UNROLL
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x4 *lr = lq + tp->yo[j];
+                        const float wy = tp->cy[j];
+                        const f32x4 a = lr[x0], bb = lr[x1], c = lr[x2], d = lr[x3];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float rowv = __builtin_fmaf(d[i], w3, __builtin_fmaf(c[i], w2, __builtin_fmaf(bb[i], w1, a[i] * w0)));
+                            val[i] = j == 0 ? rowv * wy : __builtin_fmaf(rowv, wy, val[i]);
+                        }
+                    }
+#else
+                    const Tap t = taps[r];
+                    const f32x4 a = mp[t.o00 + q], bb = mp[t.o01 + q], c = mp[t.o10 + q], d = mp[t.o11 + q];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
+                        val[i] = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+#endif
+                    *(f32x4 *)(S + r * LD + ((4 * q) ^ (((r >> 2) & 1) << 5))) = val;
+                }
+                __syncthreads();
+                const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+                for (int tn = 0; tn < CT; ++tn) {
+                    const int t = ct0 + tn < NT ? ct0 + tn : NT - 1;
+                    const float *col = S + ((t * 32 + c) ^ (h << 5));
+#pragma unroll
+                    for (int tm = 0; tm < RB; ++tm) {
+                        const int r0 = (rb0 + tm) * 32 + 4 * h;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) x[tm][tn][i] += col[(r0 + 8 * (i >> 2) + (i & 3)) * LD];
+                    }
+                }
+                if (!apart) __syncthreads();
+            }
+#else
             for (int k0 = 0; k0 < L.dlat; k0 += KMAX) {
                 // ---- z[:, k0 : k0 + kc] = bilinear latent of the 64 points -> A (each wave gathers 8 rows) ---------
                 const int kc4 = (L.dlat - k0 < KMAX ? L.dlat - k0 : KMAX) / 4;
@@ -432,6 +515,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
                 gemm(x, A4, (const f32x4 *)(Wp + L.off_z + b * L.w_z), L.njb_lat, k0 / 8, kc4 / 2, rb0, ct0, NT, lane);
                 __syncthreads();
             }
+#endif  // DINER_GEN_LZ
             store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
             __syncthreads();
             acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
@@ -499,7 +583,53 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_ix_kernel(DinerSce
     }
 }
 
-#if defined(DINER_GEN_BC)
+#if defined(DINER_GEN_LZ) && defined(DINER_GEN_BC)
+int launch_points_mlp_lz_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
+                            const float *z, int64_t NR, int K, float *rgbsigma, const float *lzmaps, hipStream_t st)
+{
+    const dim3 grid((unsigned)((NR * (int64_t)K + TILE_P - 1) / TILE_P), (unsigned)s.SB), block(NWAVES * 64);
+    if (d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_lz_bc_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    else if (d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_lz_bc_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_lz_bc_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    return check_launch("points_mlp_gen_lz_bc_kernel");
+}
+#elif defined(DINER_GEN_LZ)
+int check_shape(const DinerMlpShape &);   // points_mlp_gen.hip
+int launch_points_mlp_lz_bc(const DinerScene &, const Layout &, int, int, const float *, const float *, const float *, int64_t, int, float *,
+                            const float *, hipStream_t);   // points_mlp_gen_lz_bc.hip
+
+// launch_points_mlp with the lin_z maps of linz_maps_gen.hip (lzmaps; the shape has nlz > 0): every lookup mode runs on one kernel
+int launch_points_mlp_lz(const DinerScene &s, const DinerLatentIndex &ix, const DinerMlpShape &m, const float *mlp_packed, const float *rays,
+                         const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st, int bicubic_pad, const float *lzmaps)
+{
+    int rc;
+    if ((rc = check_shape(m))) return rc;
+    if (m.combine_layer >= m.n_blocks && s.NV != 1) {
+        set_error("render_points_gen_lz: combine_layer=%d >= n_blocks=%d never averages over views, which the reference supports for NV = 1 "
+                  "only (src/models/pixelnerf.py:137 reshapes (SB, NV, B, 4) to (SB, B, 4)); NV=%d", m.combine_layer, m.n_blocks, s.NV);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (s.C != m.d_latent) { set_error("render_points_gen_lz: latent channels C=%d != d_latent=%d", s.C, m.d_latent); return DINER_E_INVALID; }
+    if (s.num_freqs != m.num_freqs) { set_error("render_points_gen_lz: scene num_freqs=%d != shape num_freqs=%d", s.num_freqs, m.num_freqs); return DINER_E_INVALID; }
+    const int64_t P = NR * (int64_t)K;
+    if (P == 0 || s.SB == 0) return DINER_OK;
+    const int64_t tiles = (P + TILE_P - 1) / TILE_P;
+    if (tiles > 0x7fffffffLL) { set_error("render_points_gen_lz: too many points (%lld)", (long long)P); return DINER_E_INVALID; }
+    const Layout L = layout_of(m);
+    if (bicubic_pad >= 0) return launch_points_mlp_lz_bc(s, L, m.d_hidden, bicubic_pad, mlp_packed, rays, z, NR, K, rgbsigma, lzmaps, st);
+    const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);
+    if (m.d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_lz_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    else if (m.d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_lz_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_lz_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    return check_launch("points_mlp_gen_lz_kernel");
+}
+#elif defined(DINER_GEN_BC)
 int launch_points_mlp_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
                          const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {
@@ -568,6 +698,7 @@ int launch_points_mlp(const DinerScene &s, const DinerLatentIndex &ix, const Din
     return check_launch(kernel_name(m.d_hidden));
 }
 #endif  // DINER_GEN_IX
+#endif  // DINER_GEN_MAPS
 
 }  // namespace gen
 }  // namespace diner

@@ -294,7 +294,28 @@ struct TapBc {      // bicubic footprint of one (point, view) in the latent map 
 // latent_footprint), in a code object of its own.
 // points_mlp_gen_f16_bc.hip compiles it a third time with DINER_GENF16_BC (and DINER_GENF16_IX) defined:
 // points_mlp_gen_f16_bc_kernel, the 16-tap bicubic lookup (common.hpp bicubic_footprint) with the padding ix_padding.
-#ifdef DINER_GENF16_BC
+// points_mlp_gen_f16_lz.hip and points_mlp_gen_f16_lz_bc.hip compile it with DINER_GENF16_LZ on top of DINER_GENF16_IX (and
+// DINER_GENF16_BC): the lin_z-map forms points_mlp_gen_f16_lz_kernel / points_mlp_gen_f16_lz_bc_kernel, which gather d_hidden channels of
+// the fp32 maps M_b = W_b F of linz_maps_gen.hip (see points_mlp_gen.hip) through the same tap records and add them, as they are, to the
+// fp32 accumulators: no operand is split, and the maps are more exact than the split GEMM they replace.
+#if defined(DINER_GENF16_LZ) && defined(DINER_GENF16_BC)
+constexpr int TAP_SLOTS = 4;
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_lz_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                               const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                               int64_t NR, int K, float *__restrict__ rgbsigma, int ix_padding,
+                                                                               const float *__restrict__ lzmaps)
+{
+#elif defined(DINER_GENF16_LZ)
+constexpr int TAP_SLOTS = 2;
+template <int RB, int CT>
+__global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_lz_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
+                                                                            const float *__restrict__ rays, const float *__restrict__ zsamp,
+                                                                            int64_t NR, int K, float *__restrict__ rgbsigma, int ix_interp,
+                                                                            int ix_padding, const float *__restrict__ lzmaps)
+{
+    constexpr bool GIX = true;
+#elif defined(DINER_GENF16_BC)
 constexpr int TAP_SLOTS = 4;   // 16-byte slots of one point's tap record in LDS
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_bc_kernel(DinerScene s, Layout L, const float *__restrict__ Wp,
@@ -362,7 +383,11 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
     const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
     const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
     const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
+#ifdef DINER_GENF16_LZ
+    const int c4 = H / 4;        // float4 per texel of a lin_z map: the taps address the maps, the latent itself is never read
+#else
     const int c4 = L.dlat / 4;   // float4 per latent texel
+#endif
 
     for (int v = 0; v < s.NV; ++v) {
         // ---- geometry + positional encodings -> planes 0 .. 2 nkb_in of A (a wave writes whole planes); footprint -> taps ----------
@@ -429,9 +454,70 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
         gemm(x, A8, Wh + L.off_in / 8, L.nkb_in, 0, L.nkb_in, rb0, ct0, NT, lane);                  // resnetfc.py:139
         __syncthreads();
 
+#ifndef DINER_GENF16_LZ
         const f32x4 *lat = (const f32x4 *)s.latent + ((int64_t)sb * s.NV + v) * s.h * s.w * c4;
+#endif
         for (int b = 0; b < L.nvb; ++b) {
             acc_bias(x, bias + L.bias_lin_z(b), true, ct0, NT, lane);                               // :152-153 x = x + lin_z(z)
+#ifdef DINER_GENF16_LZ
+            {
+                // ---- (W_b z)[:, 0 : H] / 16 = the lookup of the 64 points in map M_b (the scale rides on the tap weights) -> LDS as fp32
+                // [point][c4 quads], quad ^ (point & msk) so that the 16-byte reads of neighbouring points fall into different banks;
+                // then every lane adds the 4 runs of 4 features per tile that its accumulators hold.  No operand image lives in the
+                // 128 KiB meanwhile; while H <= 256 the staging area lies behind the planes store_act writes next, and no barrier is
+                // needed between the adds and that store.
+                const int msk = (c4 & 15) ? 7 : 15;
+                const bool apart = 2 * H * TILE_P <= A_H8 * 4;
+                f32x4 *S4 = (f32x4 *)lds + (apart ? H * TILE_P / 4 : 0);
+                const f32x4 *mp = (const f32x4 *)lzmaps + (((int64_t)b * s.SB + sb) * s.NV + v) * s.h * s.w * c4;
+                for (int idx = lane; idx < (TILE_P / NWAVES) * c4; idx += 64) {   // a wave gathers 8 points, c4 quads each
+                    const int rr = idx / c4, q = idx - rr * c4, r = wave * (TILE_P / NWAVES) + rr;
+                    f32x4 val;
+#ifdef DINER_GENF16_BC
+                    const TapBc *tp = taps + r;   // rows then columns, contracted FMAs: the gather of the bicubic kernel
+                    const f32x4 *lq = mp + q;
+                    const int x0 = tp->xo[0], x1 = tp->xo[1], x2 = tp->xo[2], x3 = tp->xo[3];
+                    const float w0 = tp->cx[0], w1 = tp->cx[1], w2 = tp->cx[2], w3 = tp->cx[3];
+#pragma unroll BC_ROW_UNROLL
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x4 *lr = lq + tp->yo[j];
+                        const float wy = tp->cy[j];
+                        const f32x4 a = lr[x0], bb = lr[x1], c = lr[x2], d = lr[x3];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float rowv = __builtin_fmaf(d[i], w3, __builtin_fmaf(c[i], w2, __builtin_fmaf(bb[i], w1, a[i] * w0)));
+                            val[i] = j == 0 ? rowv * wy : __builtin_fmaf(rowv, wy, val[i]);
+                        }
+                    }
+#else
+                    const Tap t = taps[r];
+                    const f32x4 a = mp[t.o00 + q], bb = mp[t.o01 + q], c = mp[t.o10 + q], d = mp[t.o11 + q];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
+                        val[i] = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+#endif
+                    S4[r * c4 + (q ^ (r & msk))] = val;
+                }
+                __syncthreads();
+                const int h = lane >> 5;
+#pragma unroll
+                for (int tn = 0; tn < CT; ++tn) {
+                    const int t = ct0 + tn < NT ? ct0 + tn : NT - 1;
+#pragma unroll
+                    for (int tm = 0; tm < RB; ++tm) {
+                        const int point = (rb0 + tm) * 32 + (lane & 31);
+                        const f32x4 *sp = S4 + point * c4;
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const f32x4 mv = sp[(8 * t + 2 * g + h) ^ (point & msk)];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) x[tm][tn][4 * g + j] += mv[j];
+                        }
+                    }
+                }
+                if (!apart) __syncthreads();
+            }
+#else
             for (int k0 = 0; k0 < L.dlat; k0 += KMAX) {
                 // ---- z[:, k0 : k0 + kc] / 16 = the latent of the 64 points -> A: a wave gathers 8 points, a lane 8 columns of one ----
                 const int kc = L.dlat - k0 < KMAX ? L.dlat - k0 : KMAX;
@@ -502,6 +588,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
                 gemm(x, A8, Wh + (L.off_z + b * L.w_z) / 8, L.nkb_lat, k0 / 16, npl / 2, rb0, ct0, NT, lane);
                 __syncthreads();
             }
+#endif  // DINER_GENF16_LZ
             store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
             __syncthreads();
             acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
@@ -582,7 +669,52 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_ix_kernel(Dine
     }
 }
 
-#if defined(DINER_GENF16_BC)
+#if defined(DINER_GENF16_LZ) && defined(DINER_GENF16_BC)
+int launch_points_mlp_lz_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
+                            const float *z, int64_t NR, int K, float *rgbsigma, const float *lzmaps, hipStream_t st)
+{
+    const dim3 grid((unsigned)((NR * (int64_t)K + TILE_P - 1) / TILE_P), (unsigned)s.SB), block(NWAVES * 64);
+    if (d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_bc_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    else if (d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_bc_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_bc_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix_padding, lzmaps);
+    return check_launch("points_mlp_gen_f16_lz_bc_kernel");
+}
+#elif defined(DINER_GENF16_LZ)
+int launch_points_mlp_lz_bc(const DinerScene &, const Layout &, int, int, const float *, const float *, const float *, int64_t, int, float *,
+                            const float *, hipStream_t);   // points_mlp_gen_f16_lz_bc.hip
+
+// launch_points_mlp with the lin_z maps of linz_maps_gen.hip (lzmaps; the shape has nlz > 0): every lookup mode runs on one kernel
+int launch_points_mlp_lz(const DinerScene &s, const DinerLatentIndex &ix, const DinerMlpShape &m, const float *mlp_packed, const float *rays,
+                         const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st, int bicubic_pad, const float *lzmaps)
+{
+    int rc;
+    if ((rc = gen::check_shape(m))) return rc;
+    if (m.combine_layer >= m.n_blocks && s.NV != 1) {
+        set_error("render_points_gen_lz (f16x3): combine_layer=%d >= n_blocks=%d never averages over views, which the reference supports for "
+                  "NV = 1 only (src/models/pixelnerf.py:137 reshapes (SB, NV, B, 4) to (SB, B, 4)); NV=%d", m.combine_layer, m.n_blocks, s.NV);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (s.C != m.d_latent) { set_error("render_points_gen_lz (f16x3): latent channels C=%d != d_latent=%d", s.C, m.d_latent); return DINER_E_INVALID; }
+    if (s.num_freqs != m.num_freqs) { set_error("render_points_gen_lz (f16x3): scene num_freqs=%d != shape num_freqs=%d", s.num_freqs, m.num_freqs); return DINER_E_INVALID; }
+    const int64_t P = NR * (int64_t)K;
+    if (P == 0 || s.SB == 0) return DINER_OK;
+    const int64_t tiles = (P + TILE_P - 1) / TILE_P;
+    if (tiles > 0x7fffffffLL) { set_error("render_points_gen_lz (f16x3): too many points (%lld)", (long long)P); return DINER_E_INVALID; }
+    const Layout L = layout_of(m);
+    if (bicubic_pad >= 0) return launch_points_mlp_lz_bc(s, L, m.d_hidden, bicubic_pad, mlp_packed, rays, z, NR, K, rgbsigma, lzmaps, st);
+    const dim3 grid((unsigned)tiles, (unsigned)s.SB), block(NWAVES * 64);
+    if (m.d_hidden <= 128)
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_kernel<1, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    else if (m.d_hidden <= 256)
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_kernel<2, 1>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    else
+        hipLaunchKernelGGL((points_mlp_gen_f16_lz_kernel<2, 2>), grid, block, 0, st, s, L, mlp_packed, rays, z, NR, K, rgbsigma, ix.interp, ix.padding, lzmaps);
+    return check_launch("points_mlp_gen_f16_lz_kernel");
+}
+#elif defined(DINER_GENF16_BC)
 int launch_points_mlp_bc(const DinerScene &s, const Layout &L, int d_hidden, int ix_padding, const float *mlp_packed, const float *rays,
                          const float *z, int64_t NR, int K, float *rgbsigma, hipStream_t st)
 {

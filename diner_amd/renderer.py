@@ -199,7 +199,8 @@ class NeRFRendererDGS(torch.nn.Module):
     """
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000,
-                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False, train_f16x3_any_shape=False, bicubic_index=False):
+                 white_bkgd=True, train_any_shape=False, f16x3_any_shape=False, train_f16x3_any_shape=False, bicubic_index=False,
+                 linz_maps_any_shape=False):
         super().__init__()
         self.n_samples = n_samples
         self.n_depth_candidates = n_depth_candidates
@@ -238,7 +239,7 @@ class NeRFRendererDGS(torch.nn.Module):
         self._mlp_pack = None
         # Models of any other shape (MlpShape) run on the shape-general fp32 kernel (points_mlp_gen.hip) through the *_gen entry
         # points, always through ctypes.  After every inference call: `last_route` = the point kernel that ran ("points_mlp_f16",
-        # "points_mlp", "points_mlp_gen" or "points_mlp_gen_f16"), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
+        # "points_mlp", "points_mlp_gen" or "points_mlp_gen_f16", with "_lz" appended when linz_maps_any_shape's maps were read), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
         self._mlp_gen_key = self._mlp_gen_pack = None
         self.last_route = self.last_binding = self.effective_precision = None
         self._warned_precision = False
@@ -267,6 +268,16 @@ class NeRFRendererDGS(torch.nn.Module):
         # lin_z maps do not serve bicubic.  Opt-in: when False a bicubic model raises, as before (the static _validate_model always
         # does).  A plain attribute, so that a config can set it (renderer.kwargs.bicubic_index).
         self.bicubic_index = bool(bicubic_index)
+        # lin_z hoisted into per-texel maps for the models of the shape-general inference routes (any shape, any lookup mode, bicubic
+        # included; both precisions): outside autograd such a model's maps M_b = lin_z[b].weight . latent (no bias; csrc/linz_maps_gen.hip)
+        # are built once per encode() and weight version, and the point kernels' lin_z-map forms (last_route "points_mlp_gen_lz" /
+        # "points_mlp_gen_f16_lz") gather d_hidden channels of them instead of gathering d_latent channels and multiplying per point,
+        # view and block.  Costs min(combine_layer, n_blocks) * d_hidden / d_latent times the latent's memory, within
+        # linz_maps_max_bytes (above it: no maps, the route without them, silently); see memory_report().  Opt-in: when False nothing
+        # changes.  The standard model keeps its own kernels and maps; training builds none.  A plain attribute, so that a config can
+        # set it (renderer.kwargs.linz_maps_any_shape).
+        self.linz_maps_any_shape = bool(linz_maps_any_shape)
+        self._linz_gen_key = self._linz_gen_pack = None
         from .training_gen import WeightSplitCache
         self._weight_split_cache = WeightSplitCache()   # that path's pre-split weights, per parameter version
         # render_image under autograd: rays per chunk of its backward, which re-runs the training path chunk by chunk (peak memory = one
@@ -430,6 +441,43 @@ class NeRFRendererDGS(torch.nn.Module):
             return (*self._gen_entry(name + "_ix", f16), (C.byref(ix),))
         return (*self._gen_entry(name, f16), ())
 
+    def _gen_call(self, name: str, f16: bool, model, lz):
+        """``_gen_lookup`` and the arguments that end the list: with the lin_z maps ``lz`` the one entry point ``diner_<name>_lz`` of both
+        precisions and every lookup (DinerLatentIndex pointer or NULL after the scene; precision, bicubic padding or -1, maps at the end)"""
+        if lz is None:
+            return (*self._gen_lookup(name, f16, model), ())
+        pad = self._bicubic_pad(model)
+        ix = None if pad is not None else self._latent_index(model)
+        full = "diner_" + name + "_lz"
+        return (getattr(_lib.lib(), full), full, (C.byref(ix) if ix is not None else None,),
+                (_lib.PRECISIONS["f16x3" if f16 else "fp32"], -1 if pad is None else int(pad), _ptr(lz)))
+
+    @staticmethod
+    def _gen_route(f16: bool, lz) -> str:
+        return ("points_mlp_gen_f16" if f16 else "points_mlp_gen") + ("_lz" if lz is not None else "")
+
+    def _linz_maps_gen(self, shape: MlpShape, sc: DinerScene, latent: torch.Tensor) -> Optional[torch.Tensor]:
+        """the lin_z maps of a shape-general inference route (``linz_maps_any_shape``): a single cached entry, rebuilt when the latent
+        pack or an MLP pack was rebuilt; None (the route without maps) when the switch is off, grad mode is involved, the shape has no
+        lin_z layer or the maps exceed ``linz_maps_max_bytes``"""
+        if not self.linz_maps_any_shape or torch.is_grad_enabled() or min(shape.combine_layer, shape.n_blocks) == 0:
+            return None
+        cs = shape.c_struct()
+        n = int(_lib.lib().diner_linz_maps_gen_floats(C.byref(sc), C.byref(cs)))
+        if n < 0:
+            check(n, "diner_linz_maps_gen_floats")
+        if n == 0 or (self.linz_maps_max_bytes is not None and 4 * n > self.linz_maps_max_bytes):
+            return None
+        packed = self._mlp_gen_pack       # the fp32 image: one exact fp32 builder serves both precisions
+        key = (self._latent_gen, self._mlp_gen, shape)
+        if key != self._linz_gen_key:
+            dev = latent.device
+            self._linz_gen_pack = self._linz_gen_key = None    # (never both generations at once)
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+            check(_lib.lib().diner_pack_linz_maps_gen(C.byref(sc), C.byref(cs), _ptr(packed), _ptr(out), _stream(dev)), "diner_pack_linz_maps_gen")
+            self._linz_gen_pack, self._linz_gen_key = out, key
+        return self._linz_gen_pack
+
     def _use_gen_train(self, shape: MlpShape, model=None) -> bool:
         return self._force_gen_train or (self.train_any_shape and self._needs_gen(shape, model))
 
@@ -444,7 +492,9 @@ class NeRFRendererDGS(torch.nn.Module):
                                   "torch.no_grad() or with parameters that do not require grad, or construct the renderer with "
                                   "train_any_shape=True (renderer.train_any_shape: the shape-general fp32 training path)")
 
-    def _scene(self, model, need_latent=True, packed_mlp=None) -> Tuple[DinerScene, tuple]:
+    def _scene(self, model, need_latent=True, packed_mlp=None, gen_shape: Optional[MlpShape] = None) -> Tuple[DinerScene, tuple]:
+        """``gen_shape``: the call is a shape-general inference route's (its fp32 MLP image is packed): the tuple then ends with that
+        route's lin_z maps, or None (``_linz_maps_gen``)"""
         enc = model.encoder
         dev = enc.depths.device
         msrc = [model.poses, model.focal, model.c, model.image_shape, enc.depths, enc.depths_std, enc.normals]
@@ -515,6 +565,8 @@ class NeRFRendererDGS(torch.nn.Module):
         sc.maps = maps.data_ptr()
         sc.latent = latent.data_ptr() if latent is not None else None
         sc.linz_maps = linz.data_ptr() if linz is not None else None
+        if gen_shape is not None:
+            return sc, (maps, poses, focal, c, latent, linz, self._linz_maps_gen(gen_shape, sc, latent))
         return sc, (maps, poses, focal, c, latent, linz)
 
     def memory_report(self, model=None, rays_per_call=None, n_views=None):
@@ -527,7 +579,9 @@ class NeRFRendererDGS(torch.nn.Module):
         nb = lambda t: 0 if t is None else t.numel() * t.element_size()
         maps = self._maps_pack[0] if self._maps_pack is not None else None
         rep = {"cached": {"maps": nb(maps), "latent_nhwc": nb(self._latent_pack), "linz_maps": nb(self._linz_pack), "mlp_packed": nb(self._mlp_pack),
-                         "mlp_gen_packed": nb(self._mlp_gen_pack), "mlp_gen_f16_packed": nb(self._mlp_gen_f16_pack)}}
+                         "mlp_gen_packed": nb(self._mlp_gen_pack), "mlp_gen_f16_packed": nb(self._mlp_gen_f16_pack),
+                         # the lin_z maps of a shape-general route (linz_maps_any_shape): nlz * d_hidden / d_latent times the latent
+                         "linz_maps_gen": nb(self._linz_gen_pack)}}
         rep["cached"]["total"] = sum(rep["cached"].values())
         # a latent in glue.assemble_latent's layout is counted once: "latent_nhwc" is then encoder.latent's own storage, not a second copy
         rep["latent_zero_copy"] = bool(self._latent_shared and self._latent_pack is not None)
@@ -572,6 +626,14 @@ class NeRFRendererDGS(torch.nn.Module):
             self._mlp_gen += 1
         return self._mlp_pack
 
+    def _gen_packs(self, model, shape: MlpShape, f16: bool) -> Tuple[torch.Tensor, Optional[MlpShape]]:
+        """the packed MLP image of a shape-general inference call and the ``gen_shape`` argument of its ``_scene``: with
+        ``linz_maps_any_shape`` (outside grad mode, a shape with lin_z layers) the fp32 image is packed as well, for the map builder"""
+        lz = self.linz_maps_any_shape and not torch.is_grad_enabled() and min(shape.combine_layer, shape.n_blocks) > 0
+        if lz and f16:
+            self._mlp_shape_general(model, shape, False)
+        return self._mlp_shape_general(model, shape, f16), (shape if lz else None)
+
     def _mlp_shape_general(self, model, shape: MlpShape, f16=False) -> torch.Tensor:
         """the packed image of diner_pack_mlp_gen (``f16``: of diner_pack_mlp_gen_f16, in a cache of its own), cached like _mlp() (and
         on the shape)"""
@@ -605,6 +667,7 @@ class NeRFRendererDGS(torch.nn.Module):
                 self._mlp_gen_f16_pack, self._mlp_gen_f16_key = packed, (shape, _Sources(params))
             else:
                 self._mlp_gen_pack, self._mlp_gen_key = packed, (shape, _Sources(params))
+            self._mlp_gen += 1
         return self._mlp_gen_f16_pack if f16 else self._mlp_gen_pack
 
     # ------------------------------------------------------------------------------------------
@@ -723,14 +786,15 @@ class NeRFRendererDGS(torch.nn.Module):
         shape = self._route(model)
         if self._use_gen(shape, model):
             f16 = self._use_gen_f16(shape, model)
-            packed = self._mlp_shape_general(model, shape, f16)
-            sc, _keep = self._scene(model, need_latent=True)
+            packed, gshape = self._gen_packs(model, shape, f16)
+            sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
+            lz = _keep[6] if gshape is not None else None
             assert SB == sc.SB
             out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
             cs = shape.c_struct()
-            fn, name, look = self._gen_lookup("render_points_gen", f16, model)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device)), name)
-            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
+            fn, name, look, tail = self._gen_call("render_points_gen", f16, model, lz)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device), *tail), name)
+            self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
             return out
         packed = self._mlp(model)
         sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
@@ -891,8 +955,9 @@ class NeRFRendererDGS(torch.nn.Module):
         dev = r.device
         big = want_weights or SB * NR > int(self.finite_sync_rays)
         f16 = self._use_gen_f16(shape, model)
-        packed = self._mlp_shape_general(model, shape, f16)
-        sc, _keep = self._scene(model, need_latent=True)
+        packed, gshape = self._gen_packs(model, shape, f16)
+        sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
+        lz = _keep[6] if gshape is not None else None
         assert SB == sc.SB
         cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
         cs = shape.c_struct()
@@ -907,9 +972,9 @@ class NeRFRendererDGS(torch.nn.Module):
         depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
         weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
         if self.stage_events is None:
-            fn, name, look = self._gen_lookup("render_gen", f16, model)
+            fn, name, look, tail = self._gen_call("render_gen", f16, model, lz)
             check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st), name)
+                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st, *tail), name)
         else:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
@@ -917,15 +982,15 @@ class NeRFRendererDGS(torch.nn.Module):
             check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
                                              None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
             ev[1].record()
-            fn, name, look = self._gen_lookup("render_points_gen", f16, model)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st), name)
+            fn, name, look, tail = self._gen_call("render_points_gen", f16, model, lz)
+            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st, *tail), name)
             ev[2].record()
             check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
                                     _ptr(depth), _ptr(weights), status, st), "diner_composite")
             ev[3].record()
             self.stage_events.append(ev)
         self._after_launch(dev, sync=big)
-        self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
+        self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False):
@@ -971,7 +1036,12 @@ class NeRFRendererDGS(torch.nn.Module):
         E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
         zn = torch.as_tensor(z_near, dtype=torch.float32, device=dev).expand(SB).contiguous()
         zf = torch.as_tensor(z_far, dtype=torch.float32, device=dev).expand(SB).contiguous()
-        if gen:
+        lz = None
+        if gen and saved is None:
+            packed, gshape = self._gen_packs(model, shape, f16)
+            sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
+            lz = _keep[6] if gshape is not None else None
+        elif gen:    # the forward of render_image under autograd: the frame without maps, as before
             packed = self._mlp_shape_general(model, shape, f16)
             sc, _keep = self._scene(model, need_latent=True)
         else:
@@ -995,10 +1065,10 @@ class NeRFRendererDGS(torch.nn.Module):
                              dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
             depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            fn, name, look = self._gen_lookup("render_image_gen", f16, model)
+            fn, name, look, tail = self._gen_call("render_image_gen", f16, model, lz)
             check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed, _ptr(ws),
-                     _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), name)
-            self.last_route, self.last_binding = ("points_mlp_gen_f16" if f16 else "points_mlp_gen"), "ctypes"
+                     _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev), *tail), name)
+            self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
         elif ix is not None:
             ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, prec)), dtype=torch.float32, device=dev)
             rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)

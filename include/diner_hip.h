@@ -419,6 +419,43 @@ int diner_render_image_gen_f16_bc(const DinerScene *scene, int32_t padding, cons
                                   float *workspace, float *rays_out, float *rgb_out, float *depth_out, float *weights_out,
                                   uint32_t *status, void *stream);
 
+/* ---- lin_z hoisted into per-texel maps on the shape-general kernels (linz_maps_gen.hip, points_mlp_gen_lz.hip,
+ * points_mlp_gen_f16_lz.hip and their _bc twins).  ResnetFC.forward's `x = x + self.lin_z[blkid](z)` (src/models/resnetfc.py:152-153) is
+ * linear and z = SpatialEncoder.index (src/models/image_encoder.py:97-127) a weighted sum of texels, so
+ * lin_z[b](z) = sum_i w_i (W_b F_i) + bias_b.  A map is M_b[sb, v, y, x, :] = W_z[b] . F[sb, v, y, x, :]: d_hidden floats per latent
+ * texel, NHWC fp32, layout [nlz][SB, NV, h, w, d_hidden], nlz = min(combine_layer, n_blocks), WITHOUT lin_z[b].bias (unlike
+ * diner_pack_linz_maps): exactly linear in the taps, so the same maps serve every lookup mode -- bilinear / nearest, border / zeros /
+ * reflection, and bicubic -- with no ring of extra texels.  Memory: nlz * d_hidden / d_latent times the latent.  The point kernels
+ * gather d_hidden channels of M_b through the lookup's taps and add them to the fp32 accumulator in place of the per-point lin_z GEMM;
+ * everything else is the arithmetic of the *_gen / *_gen_f16 entry points.  New symbols only: DINER_ABI_VERSION stays 3; the other
+ * *_gen* entry points keep ignoring scene->linz_maps. */
+/* floats of the maps of a scene (SB, NV, h, w are read): 0 when nlz = 0; < 0: DINER_E_INVALID, or the DINER_E_* code of an unsupported
+ * shape (that of diner_mlp_gen_packed_floats) */
+int64_t diner_linz_maps_gen_floats(const DinerScene *scene, const DinerMlpShape *shape);
+/* Replaces the lin_z[b](z) Linear layers of ResnetFC.forward (src/models/resnetfc.py:152-153), per texel instead of per point: an exact
+ * fp32 MFMA GEMM of scene->latent (NHWC, diner_pack_latent) with each lin_z[b] of mlp_packed = the image of diner_pack_mlp_gen (the fp32
+ * one, for both precisions).  Writes diner_linz_maps_gen_floats floats; nlz = 0: nothing. */
+int diner_pack_linz_maps_gen(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, float *maps_out, void *stream);
+/* Replace PixelNeRF.forward + ResnetFC.forward per point (src/models/pixelnerf.py:55-145, src/models/resnetfc.py:129-159),
+ * NeRFRendererDGS.forward (src/models/nerf_renderer.py:399-424) and the render half of DINER.predict_imgs_from_batch
+ * (src/models/diner.py:75-97), as their _gen_ix forms do.  One family for both precisions and every lookup: the argument lists of the
+ * _gen_ix forms, then precision (DINER_PRECISION_FP32: mlp_packed from diner_pack_mlp_gen; DINER_PRECISION_F16X3: from
+ * diner_pack_mlp_gen_f16), bicubic_padding (-1: the lookup of `index`, NULL = bilinear / border; otherwise DINER_INDEX_PAD_* of the
+ * bicubic lookup, `index` is then ignored) and linz_maps_gen (diner_pack_linz_maps_gen's output; with nlz = 0 it is not read and the
+ * call is that of the _gen_ix / _gen_bc form).  DINER_E_INVALID: NULL maps with nlz > 0, precision or bicubic_padding out of range. */
+int diner_render_points_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                               const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream,
+                               int32_t precision, int32_t bicubic_padding, const float *linz_maps_gen);
+int diner_render_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                        const float *rays, int64_t NR, const DinerSamplerCfg *cfg, int32_t white_bkgd, const float *u_coarse,
+                        const float *n_gauss, const float *u_fill, uint64_t seed, float *workspace, float *rgb_out, float *depth_out,
+                        float *weights_out, uint32_t *status, void *stream, int32_t precision, int32_t bicubic_padding,
+                        const float *linz_maps_gen);
+int diner_render_image_gen_lz(const DinerScene *scene, const DinerLatentIndex *index, const DinerMlpShape *shape, const float *mlp_packed,
+                              const DinerTargetCam *cam, const DinerSamplerCfg *cfg, int32_t white_bkgd, uint64_t seed, float *workspace,
+                              float *rays_out, float *rgb_out, float *depth_out, float *weights_out, uint32_t *status, void *stream,
+                              int32_t precision, int32_t bicubic_padding, const float *linz_maps_gen);
+
 /* ---- training path: building blocks of the forward-with-saved-activations and
  * the backward of composite (src/models/nerf_renderer.py:286-365) + PixelNeRF.forward
  * (src/models/pixelnerf.py:55-145) + ResnetFC.forward (src/models/resnetfc.py:129-159), orchestrated by
