@@ -84,7 +84,7 @@ INDEX_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
 
 
 # every symbol include/diner_hip.h declares: name -> (restype, argtypes)
-_I64, _I32, _U64, _P = C.c_int64, C.c_int32, C.c_uint64, C.c_void_p
+_I64, _I32, _U64, _P, _F32 = C.c_int64, C.c_int32, C.c_uint64, C.c_void_p, C.c_float
 SYMBOLS = {
     "diner_last_error": (C.c_char_p, []),
     "diner_version": (C.c_int, []),
@@ -205,6 +205,10 @@ SYMBOLS = {
     # the ABI version stays 3: new entry points only)
     "diner_assemble_latent": (C.c_int, [C.POINTER(DinerLatentLevels), _I32, _I64, _I32, _I32, _P, _P]),
     "diner_assemble_latent_backward": (C.c_int, [_P, _I32, _I64, _I32, _I32, C.POINTER(DinerLatentLevels), _P]),
+    # conv1's input (the head of the encoder: normalise, replicate pad, the padding's positional encoding) and its adjoint to the images
+    # (csrc/encoder_input.hip; the ABI version stays 3: new entry points only)
+    "diner_encoder_input": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F32, _F32, _F32, _F32, _F32, _F32, _P, _P]),
+    "diner_encoder_input_backward": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _F32, _F32, _F32, _P, _P]),
     # lin_z hoisted into per-texel maps on the shape-general kernels: the *_gen_ix argument lists, then precision (PRECISIONS), the bicubic
     # padding (-1: not bicubic, else INDEX_PADDING) and the maps of diner_pack_linz_maps_gen (the ABI version stays 3: new entry points only)
     "diner_linz_maps_gen_floats": (_I64, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape)]),

@@ -6,7 +6,11 @@ with the reference's own function signatures so they can replace them in place:
 * :func:`depth2normal`  -- reference ``src/util/depth2normal.py:7-87``
 
 and the tail of the encoder: :func:`assemble_latent` -- reference ``src/models/image_encoder.py:262-272`` (the feature levels upsampled to
-the first one's size and concatenated), written once in the NHWC layout the render and training kernels read.
+the first one's size and concatenated), written once in the NHWC layout the render and training kernels read;
+its head: :func:`encoder_input` -- reference ``src/models/pixelnerf.py:44`` + ``src/models/image_encoder.py:222-232`` (conv1's input: the
+images normalised and replicate-padded, plus the positional encoding of the padding);
+and both around the model's own CNN trunk: :func:`encode`, with ``PixelNeRF.encode``'s signature (reference
+``src/models/pixelnerf.py:35-53`` + ``SpatialEncoder.forward``, ``src/models/image_encoder.py:206-272``).
 """
 from __future__ import annotations
 
@@ -225,3 +229,146 @@ def latent_is_packed(t) -> bool:
     """True when ``t`` [SB, NV, C, h, w] already has the layout the kernels read (what :func:`assemble_latent` returns):
     ``t.permute(0, 1, 3, 4, 2)`` is a contiguous fp32 CUDA tensor."""
     return nhwc_strided(t) and t.is_cuda
+
+
+# ---- the head of the encoder: conv1's input -----------------------------------------------------------------------------------------
+IMAGENET_MEAN = (0.485, 0.456, 0.406)    # PixelNeRF.normalize_rgb (reference src/models/pixelnerf.py:32-33)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+_pixel_coords = {}    # (Hp, Wp, device) -> (xs [Wp], ys [Hp]): they depend on nothing but the sizes
+_PIXEL_COORDS_MAX = 8  # sizes kept (oldest dropped first): a training run has one or two, and an entry is two short vectors
+
+
+def _coords(Hp, Wp, dev):
+    """The pixel coordinates of a padded size, made once.  They are written on the stream that is current at the first call and read by
+    launches on whatever stream is current later; torch's caching allocator does not reuse their memory while the cache holds them, and
+    the first launch that reads them is queued on their own stream, behind the fill: a later launch on another stream is ordered after it
+    only if the caller has ordered its streams, as for any tensor shared between streams."""
+    key = (Hp, Wp, str(dev))
+    if key not in _pixel_coords:
+        while len(_pixel_coords) >= _PIXEL_COORDS_MAX:
+            _pixel_coords.pop(next(iter(_pixel_coords)))
+        with torch.no_grad():
+            _pixel_coords[key] = (torch.linspace(-1, 1, Wp, device=dev), torch.linspace(-1, 1, Hp, device=dev))   # image_encoder.py:228-229
+    return _pixel_coords[key]
+
+
+def _three(v, what):
+    v = [float(x) for x in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v)]
+    if len(v) != 3:
+        raise ValueError(f"encoder_input: {what} must hold 3 values, not {len(v)}")
+    return v
+
+
+def _pe_channels(pad, F):
+    return 2 * (1 + 2 * F) if F >= 0 and pad > 0 else 0
+
+
+def _encoder_input(x, pad, F, mean, std):
+    """fp32 contiguous x [N,3,H,W] -> [N, 3 + Cpe, H + 2 pad, W + 2 pad]"""
+    N, _, H, W = x.shape
+    Cpe = _pe_channels(pad, F)
+    Hp, Wp = H + 2 * pad, W + 2 * pad
+    if pad < 0 or Hp < 2 or Wp < 2 or N < 1:
+        raise ValueError(f"encoder_input: bad sizes N={N}, H={H}, W={W}, image_padding={pad}")
+    xs, ys = _coords(Hp, Wp, x.device) if Cpe else (None, None)
+    out = torch.empty((N, 3 + Cpe, Hp, Wp), dtype=torch.float32, device=x.device)
+    check(_lib.lib().diner_encoder_input(x.data_ptr(), N, H, W, pad, F, xs.data_ptr() if Cpe else None, ys.data_ptr() if Cpe else None,
+                                         *mean, *std, out.data_ptr(), _st(x.device)), "diner_encoder_input")
+    return out
+
+
+def encoder_input_backward(d_out, image_padding, padding_pe, std=IMAGENET_STD):
+    """Adjoint of :func:`encoder_input` to the images: d_out [N, 3 + Cpe, Hp, Wp] -> d_images [N,3,H,W] in fp32: every image pixel sums
+    the gradient of the padded pixels copied from it, divided by std (``diner_encoder_input_backward``: gather form, bitwise
+    reproducible); the encoding's channels carry no gradient."""
+    pad, F = int(image_padding), max(int(padding_pe), -1)
+    g = _f(d_out)
+    if not g.is_cuda:
+        raise RuntimeError("diner_amd.glue.encoder_input_backward runs on the GPU only")
+    N, Ct, Hp, Wp = g.shape
+    H, W = Hp - 2 * pad, Wp - 2 * pad
+    if Ct != 3 + _pe_channels(pad, F) or H < 1 or W < 1:
+        raise ValueError(f"encoder_input_backward: d_out {tuple(g.shape)} does not belong to image_padding={pad}, padding_pe={F}")
+    d_img = torch.empty((N, 3, H, W), dtype=torch.float32, device=g.device)
+    check(_lib.lib().diner_encoder_input_backward(g.data_ptr(), N, H, W, pad, F, *_three(std, "std"), d_img.data_ptr(), _st(g.device)),
+          "diner_encoder_input_backward")
+    return d_img
+
+
+class _EncoderInputFn(torch.autograd.Function):
+    """encoder_input with a backward: forward = diner_encoder_input (the no-grad call's values, bit for bit), backward = its adjoint"""
+
+    @staticmethod
+    def forward(ctx, images, pad, F, mean, std):
+        ctx.pad, ctx.F, ctx.std, ctx.shape, ctx.dtype = pad, F, std, images.shape, images.dtype
+        return _encoder_input(_f(images).reshape(-1, *images.shape[-3:]), pad, F, mean, std)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        return encoder_input_backward(d_out, ctx.pad, ctx.F, ctx.std).reshape(ctx.shape).to(ctx.dtype), None, None, None, None
+
+
+def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """conv1's input in one kernel (reference src/models/pixelnerf.py:44 + src/models/image_encoder.py:222-232): ``images``
+    [..., 3, H, W] -> [N, 3 + Cpe, H + 2 image_padding, W + 2 image_padding] in fp32, N = the product of the leading dimensions.
+    Channels 0..2: ``(images - mean) / std`` replicate-padded by ``image_padding``, bit-equal to ``Normalize`` + ``ReplicationPad2d``;
+    with ``padding_pe >= 0`` and ``image_padding > 0`` the Cpe = 2 (1 + 2 padding_pe) channels of ``PositionalEncoding(padding_pe,
+    freq_factor=pi, d_in=2)`` of the pixel coordinates follow, zero over the image's own pixels.
+    Differentiable with respect to the images (``diner_encoder_input_backward``, deterministic)."""
+    if not isinstance(images, torch.Tensor) or images.dim() < 3 or images.shape[-3] != 3:
+        raise ValueError("encoder_input: images must be [..., 3, H, W]")
+    if not images.is_cuda:
+        raise RuntimeError("diner_amd.glue.encoder_input runs on the GPU only")
+    pad, F = int(image_padding), max(int(padding_pe), -1)
+    mean, std = _three(mean, "mean"), _three(std, "std")
+    if torch.is_grad_enabled() and images.requires_grad:
+        return _EncoderInputFn.apply(images, pad, F, mean, std)
+    with torch.no_grad():
+        return _encoder_input(_f(images).reshape(-1, *images.shape[-3:]), pad, F, mean, std)
+
+
+def encode(model, images, depths, depths_std, extrinsics, intrinsics):
+    """Drop-in for ``PixelNeRF.encode`` (reference src/models/pixelnerf.py:35-53) with ``SpatialEncoder.forward``
+    (src/models/image_encoder.py:206-272) inside: images [SB,NV,3,H,W], depths, depths_std [SB,NV,1,H,W], extrinsics [SB,NV,4,4],
+    intrinsics [SB,NV,3,3].  The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`)
+    run on the HIP kernels; the model's own trunk modules (``model.encoder.model``: conv1, bn1, relu, maxpool, layer1..) run unchanged on
+    PyTorch in between.  Leaves the model in the state the reference's encode leaves it in, with ``encoder.latent`` in the layout the
+    render and training kernels read (:func:`latent_is_packed`).  ``model.encode = functools.partial(glue.encode, model)``."""
+    enc = model.encoder
+    if enc.upsample_interp != "bilinear":   # before any device work; there is no eager fallback
+        raise NotImplementedError(f"encode: upsample_interp {enc.upsample_interp!r} is not implemented (assemble_latent is bilinear, "
+                                  "align_corners=True)")
+    SB, NV, _, H, W = images.shape
+    norm = getattr(model, "normalize_rgb", None)
+    mean, std = getattr(norm, "mean", None), getattr(norm, "std", None)
+    enc.depths, enc.depths_std = depths, depths_std
+    enc.normals = depth2normal(depths.flatten(0, 1), intrinsics.flatten(0, 1)).reshape(SB, NV, 3, H, W)
+    enc.nviews, enc.nobjects = NV, SB
+    x = encoder_input(images, enc.image_padding, enc.padding_pe, IMAGENET_MEAN if mean is None else mean,
+                      IMAGENET_STD if std is None else std)
+    trunk = enc.model
+    x = trunk.relu(trunk.bn1(trunk.conv1(x)))
+    levels = [x]
+    if enc.num_layers > 1:
+        if enc.use_first_pool:
+            x = trunk.maxpool(x)
+        x = trunk.layer1(x)
+        levels.append(x)
+    for i in (2, 3, 4):
+        if enc.num_layers > i:
+            x = getattr(trunk, f"layer{i}")(x)
+            levels.append(x)
+    enc.latent = assemble_latent(levels, SB, NV, mode=enc.upsample_interp)
+    model.poses = extrinsics
+    model.c = intrinsics[:, :, :2, -1]
+    model.focal = torch.stack((intrinsics[:, :, 0, 0], intrinsics[:, :, 1, 1]), dim=-1)
+    shape = getattr(model, "image_shape", None)
+    if not (isinstance(shape, torch.Tensor) and shape.numel() >= 2 and shape.device == images.device):
+        model.image_shape = shape = torch.empty(2, dtype=torch.float32, device=images.device)
+    with torch.no_grad():
+        shape[0] = W
+        shape[1] = H
+    return None

@@ -188,6 +188,29 @@ int diner_assemble_latent(const DinerLatentLevels *levels, int32_t n_levels, int
                           void *stream);
 int diner_assemble_latent_backward(const float *d_out_nhwc, int32_t n_levels, int64_t N, int32_t h, int32_t w,
                                    const DinerLatentLevels *levels_grad, void *stream);
+/* ---- once per encode(): conv1's input, the head of the encoder ----------------------------- */
+/* Replaces PixelNeRF.encode's Normalize (src/models/pixelnerf.py:44) and the head of SpatialEncoder.forward (pad_layer, linspace /
+ * meshgrid / PositionalEncoding / interior zeroing / expand / cat, src/models/image_encoder.py:222-232) in one launch (New symbols only:
+ * DINER_ABI_VERSION stays 3).  images [N,3,H,W] -> out [N, 3 + Cpe, Hp, Wp], Hp = H + 2 pad, Wp = W + 2 pad (pad = image_padding):
+ *   channels 0..2:  (images[n, c, clamp(y - pad, 0, H - 1), clamp(x - pad, 0, W - 1)] - mean[c]) / std[c] -- an fp32 subtract and a true
+ *                   fp32 divide, bit-equal to Normalize + ReplicationPad2d; pad may exceed H or W;
+ *   channels 3..:   present iff pe_freqs >= 0 && pad > 0 (the reference's padding_pe >= 0 and feature_padding > 0), Cpe = 2 (1 + 2F),
+ *                   F = pe_freqs (-1: none; 0: the two raw coordinates only).  0 where pad <= y < Hp - pad && pad <= x < Wp - pad;
+ *                   elsewhere, with v = (xs[x], ys[y]): [v_0, v_1, e_0, ...], e[2 j + i] = sin(phi_j + v_i f_(j / 2)), j = 0..2F-1,
+ *                   f_k = fp32(pi) 2^k, phi_j = 0 (j even) / fp32(pi / 2) (j odd): PositionalEncoding(F, freq_factor = pi, d_in = 2)
+ *                   (src/models/positional_encoding.py:14-53).  The same values for every n: computed once per pixel.
+ * xs [Wp], ys [Hp]: the pixel coordinates, torch.linspace(-1, 1, Wp) / (.., Hp) made by the caller (read only with the encoding on, may be
+ * NULL otherwise).  mean / std: the three channel constants by value.  `out` 16-byte aligned with Wp % 4 == 0 takes 16-byte stores.
+ * diner_encoder_input_backward is the adjoint to the images: d_images[n,c,y,x] = (sum of d_out[n,c,y',x'] over every (y',x') whose clamp
+ * lands on (y,x)) / std[c], a gather with a fixed summation order (no atomics: two runs agree bit for bit); the encoding's channels of
+ * d_out [N, 3 + Cpe, Hp, Wp] carry no gradient and are not read.  Every element of d_images [N,3,H,W] is written.
+ * Before any launch: DINER_E_INVALID for a NULL pointer, N / H / W <= 0, pad < 0, pe_freqs < -1, Hp or Wp below 2, or a std of 0;
+ * DINER_E_UNSUPPORTED for pe_freqs > 30, a padded size of 2^30 or more, N > 65535 images (forward) or pad > 4095 (backward only). */
+int diner_encoder_input(const float *images, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t pe_freqs, const float *xs,
+                        const float *ys, float mean0, float mean1, float mean2, float std0, float std1, float std2, float *out,
+                        void *stream);
+int diner_encoder_input_backward(const float *d_out, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t pe_freqs, float std0, float std1,
+                                 float std2, float *d_images, void *stream);
 /* ---- once per weight version: MFMA-fragment-ordered copies of the fusion MLP (one image per
  * precision mode, both in the same buffer) ------------------------------------------------ */
 int64_t diner_mlp_packed_floats(void);
