@@ -209,6 +209,13 @@ SYMBOLS = {
     # (csrc/encoder_input.hip; the ABI version stays 3: new entry points only)
     "diner_encoder_input": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F32, _F32, _F32, _F32, _F32, _F32, _P, _P]),
     "diner_encoder_input_backward": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _F32, _F32, _F32, _P, _P]),
+    # a training step's ray selection and photometric losses (csrc/train_glue.hip; the ABI version stays 3: new entry points only)
+    "diner_gen_rays_at": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "diner_gen_rays_at_backward_workspace_floats": (_I64, [_I32, _I32]),
+    "diner_gen_rays_at_backward": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "diner_photo_loss_workspace_floats": (_I64, [_I32, _I32, _I32, _I32]),
+    "diner_photo_loss": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "diner_photo_loss_backward": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     # lin_z hoisted into per-texel maps on the shape-general kernels: the *_gen_ix argument lists, then precision (PRECISIONS), the bicubic
     # padding (-1: not bicubic, else INDEX_PADDING) and the maps of diner_pack_linz_maps_gen (the ABI version stays 3: new entry points only)
     "diner_linz_maps_gen_floats": (_I64, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape)]),

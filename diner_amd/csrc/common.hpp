@@ -72,6 +72,26 @@ __device__ __forceinline__ void project(const View &v, float iw, float ih, float
     w = w / ih * 2.0f - 1.0f;
 }
 
+// One ray of gen_rays (reference src/util/cam_geometry.py:36-79) at pixel (x, y): E [4,4] world->cam, Kk [3,3] -> o[8] = origin(3), unit
+// direction(3), near, far; pixel centres, OpenCV convention.  The only place that computes a ray: gen_rays_kernel (encode_glue.hip, every
+// pixel) and gen_rays_at_kernel (train_glue.hip, selected pixels) both call it, so a selected ray is the full image's ray bit for bit.
+__device__ __forceinline__ void gen_ray(const float *__restrict__ E, const float *__restrict__ Kk, int x, int y, float near, float far,
+                                        float *__restrict__ o)
+{
+    const float fx = Kk[0], fy = Kk[4], cx = Kk[2], cy = Kk[5];
+    float dx = (((float)x + 0.5f) - cx) / fx, dy = (((float)y + 0.5f) - cy) / fy, dz = 1.0f;  // :62-63
+    const float n = sqrtf(dx * dx + dy * dy + dz * dz);                                        // :64 pow(2).sum().sqrt()
+    dx = dx / n; dy = dy / n; dz = dz / n;
+    // world direction = R^T d (bmm: k-ordered FMA chain), origin = -R^T t (:67-72)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        o[3 + r] = __builtin_fmaf(E[2 * 4 + r], dz, __builtin_fmaf(E[1 * 4 + r], dy, E[0 * 4 + r] * dx));
+        o[r] = __builtin_fmaf(-1.0f * E[2 * 4 + r], E[2 * 4 + 3], __builtin_fmaf(-1.0f * E[1 * 4 + r], E[1 * 4 + 3], (-1.0f * E[0 * 4 + r]) * E[0 * 4 + 3]));
+    }
+    o[6] = near;
+    o[7] = far;
+}
+
 // sin() of the positional encodings.  The argument is the reference's fp32 value (one fma, positional_encoding.py:45-49); its sine comes
 // from the hardware's v_sin_f32 (sin(2 pi x) of an argument in revolutions) behind a compensated reduction: r1 = RN(a * C_HI),
 // r2 = the part of a / 2pi that r1 lost (exact by fma) + a * C_LO, sin(2 pi (fract(r1) + r2)) -- accurate for every finite a.  Measured

@@ -18,20 +18,7 @@ __global__ void gen_rays_kernel(const float *__restrict__ extr, const float *__r
     if (i >= (int64_t)B * H * W) return;
     const int b = (int)(i / ((int64_t)H * W));
     const int p = (int)(i - (int64_t)b * H * W), y = p / W, x = p - y * W;
-    const float *E = extr + b * 16, *Kk = intr + b * 9;
-    const float fx = Kk[0], fy = Kk[4], cx = Kk[2], cy = Kk[5];
-    float dx = (((float)x + 0.5f) - cx) / fx, dy = (((float)y + 0.5f) - cy) / fy, dz = 1.0f;  // :62-63
-    const float n = sqrtf(dx * dx + dy * dy + dz * dz);                                        // :64 pow(2).sum().sqrt()
-    dx = dx / n; dy = dy / n; dz = dz / n;
-    // world direction = R^T d (bmm: k-ordered FMA chain), origin = -R^T t (:67-72)
-    float *o = rays + i * 8;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        o[3 + r] = __builtin_fmaf(E[2 * 4 + r], dz, __builtin_fmaf(E[1 * 4 + r], dy, E[0 * 4 + r] * dx));
-        o[r] = __builtin_fmaf(-1.0f * E[2 * 4 + r], E[2 * 4 + 3], __builtin_fmaf(-1.0f * E[1 * 4 + r], E[1 * 4 + 3], (-1.0f * E[0 * 4 + r]) * E[0 * 4 + 3]));
-    }
-    o[6] = z_near[b];
-    o[7] = z_far[b];
+    gen_ray(extr + b * 16, intr + b * 9, x, y, z_near[b], z_far[b], rays + i * 8);   // common.hpp: the per-pixel arithmetic
 }
 
 // ---- backward of gen_rays: d_rays [B,H,W,8] -> d_extr [B,4,4], d_intr [B,3,3], d_near [B], d_far [B] ----------------------

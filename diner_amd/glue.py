@@ -10,7 +10,9 @@ the first one's size and concatenated), written once in the NHWC layout the rend
 its head: :func:`encoder_input` -- reference ``src/models/pixelnerf.py:44`` + ``src/models/image_encoder.py:222-232`` (conv1's input: the
 images normalised and replicate-padded, plus the positional encoding of the padding);
 and both around the model's own CNN trunk: :func:`encode`, with ``PixelNeRF.encode``'s signature (reference
-``src/models/pixelnerf.py:35-53`` + ``SpatialEncoder.forward``, ``src/models/image_encoder.py:206-272``).
+``src/models/pixelnerf.py:35-53`` + ``SpatialEncoder.forward``, ``src/models/image_encoder.py:206-272``);
+and a training step around the renderer: :func:`gen_rays_at` (gen_rays at the selected pixels only), :func:`photo_loss` (ground-truth
+gather, MSE and antibias loss) and :func:`calc_losses`, which assembles ``DINER.calc_losses`` (reference ``src/models/diner.py:217-290``).
 """
 from __future__ import annotations
 
@@ -372,3 +374,240 @@ def encode(model, images, depths, depths_std, extrinsics, intrinsics):
         shape[0] = W
         shape[1] = H
     return None
+
+
+# ---- a training step around renderer.forward: ray selection and the photometric losses --------------------------------------------------
+def _indices(pix_idcs, SB, who):
+    """pix_idcs as the kernels read it: [SB, B], int64 or int32, contiguous -> (tensor, is_int64)"""
+    if not isinstance(pix_idcs, torch.Tensor) or pix_idcs.dim() != 2 or pix_idcs.shape[0] != SB:
+        raise ValueError(f"{who}: pix_idcs must be a tensor [SB = {SB}, B]")
+    if pix_idcs.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"{who}: pix_idcs must be int64 or int32, not {pix_idcs.dtype}")
+    return pix_idcs.contiguous(), int(pix_idcs.dtype == torch.int64)
+
+
+def _check_indices(pix_idcs, npix, who):
+    if pix_idcs.numel():
+        lo, hi = (int(v) for v in torch.aminmax(pix_idcs))
+        if lo < 0 or hi >= npix:
+            raise IndexError(f"{who}: pix_idcs spans [{lo}, {hi}], outside [0, H*W = {npix})")
+
+
+def _gen_rays_at(e, k, zn, zf, idx, is64, W, H):
+    SB, B = idx.shape
+    out = torch.empty((SB, B, 8), dtype=torch.float32, device=e.device)
+    check(_lib.lib().diner_gen_rays_at(e.data_ptr(), k.data_ptr(), zn.data_ptr(), zf.data_ptr(), idx.data_ptr(), is64, SB, B, int(H), int(W),
+                                       out.data_ptr(), _st(e.device)), "diner_gen_rays_at")
+    return out
+
+
+def gen_rays_at_backward(e, k, d_rays, pix_idcs, H, W):
+    """Backward of :func:`gen_rays_at` on fp32 contiguous cameras e [SB,4,4], k [SB,3,3], d_rays [SB,B,8] and pix_idcs [SB,B]:
+    -> d_extrinsics [SB,4,4], d_intrinsics [SB,3,3], d_near [SB], d_far [SB] in fp32 (diner_gen_rays_at_backward: it reads d_rays and the
+    indices only; fixed-order fp64 sums, bitwise reproducible)."""
+    SB, dev = e.shape[0], e.device
+    idx, is64 = _indices(pix_idcs, SB, "gen_rays_at_backward")
+    B = idx.shape[1]
+    g = _f(d_rays)
+    assert g.numel() == SB * B * 8, "gen_rays_at_backward: d_rays must be [SB, B, 8]"
+    L = _lib.lib()
+    n = int(L.diner_gen_rays_at_backward_workspace_floats(SB, B))
+    if n < 0:
+        raise ValueError(f"gen_rays_at_backward: bad sizes SB={SB}, B={B}")
+    ws = torch.empty(max(n, 2), dtype=torch.float32, device=dev)
+    d_e = torch.empty((SB, 4, 4), dtype=torch.float32, device=dev)
+    d_k = torch.empty((SB, 3, 3), dtype=torch.float32, device=dev)
+    d_n = torch.empty(SB, dtype=torch.float32, device=dev)
+    d_f = torch.empty(SB, dtype=torch.float32, device=dev)
+    check(L.diner_gen_rays_at_backward(e.data_ptr(), k.data_ptr(), g.data_ptr(), idx.data_ptr(), is64, SB, B, int(H), int(W), d_e.data_ptr(),
+                                       d_k.data_ptr(), d_n.data_ptr(), d_f.data_ptr(), ws.data_ptr(), _st(dev)), "diner_gen_rays_at_backward")
+    return d_e, d_k, d_n, d_f
+
+
+class _GenRaysAtFn(torch.autograd.Function):
+    """gen_rays_at with a backward: forward = diner_gen_rays_at (the no-grad call's values, bit for bit), backward = diner_gen_rays_at_backward"""
+
+    @staticmethod
+    def forward(ctx, extrinsics, intrinsics, z_near, z_far, W, H, idx, is64):
+        e, k = _f(extrinsics), _f(intrinsics)
+        SB = e.shape[0]
+        out = _gen_rays_at(e, k, _per_camera(z_near, SB, e.device), _per_camera(z_far, SB, e.device), idx, is64, W, H)
+        ctx.save_for_backward(extrinsics, intrinsics, idx)    # (version-checked by autograd: an in-place edit before backward raises)
+        ctx.e, ctx.k, ctx.HW = e, k, (int(H), int(W))
+        ctx.zs = (z_near, z_far)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rays):
+        extrinsics, intrinsics, idx = ctx.saved_tensors
+        H, W = ctx.HW
+        d_e, d_k, d_n, d_f = gen_rays_at_backward(ctx.e, ctx.k, d_rays, idx, H, W)
+        z_near, z_far = ctx.zs
+        return (_like(d_e, extrinsics) if ctx.needs_input_grad[0] else None,
+                _like(d_k, intrinsics) if ctx.needs_input_grad[1] else None,
+                _like(d_n, z_near) if ctx.needs_input_grad[2] else None,
+                _like(d_f, z_far) if ctx.needs_input_grad[3] else None, None, None, None, None)
+
+
+def gen_rays_at(extrinsics, intrinsics, W, H, z_near, z_far, pix_idcs, check_indices=False):
+    """:func:`gen_rays` at selected pixels only, in one kernel (reference src/models/diner.py:224-227 + :257-258): extrinsics [SB,4,4],
+    intrinsics [SB,3,3], z_near / z_far [SB] (or one value for all), pix_idcs [SB,B] (int64 or int32, on the device, ``idx = x + y * W`` as in
+    diner.py:246) -> rays [SB,B,8], bit-equal to ``gen_rays(...).view(SB, H*W, 8)[b, pix_idcs[b]]``.  Differentiable with respect to the same
+    inputs as gen_rays (``diner_gen_rays_at_backward``: it reads d_rays [SB,B,8] and the indices, not a full-image gradient; deterministic;
+    duplicate indices are separate terms).
+    ``check_indices=True``: one host-side ``aminmax`` (a device synchronisation) raises ``IndexError`` for an index outside [0, H*W) before
+    anything is launched.  With ``False`` the kernel clamps an index into [0, H*W): it never reads or writes out of bounds, and the result for
+    such an index is unspecified."""
+    SB = extrinsics.shape[0]
+    idx, is64 = _indices(pix_idcs, SB, "gen_rays_at")
+    if check_indices:
+        _check_indices(idx, int(H) * int(W), "gen_rays_at")
+    if not extrinsics.is_cuda or not idx.is_cuda:
+        raise RuntimeError("diner_amd.glue.gen_rays_at runs on the GPU only")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                       for t in (extrinsics, intrinsics, z_near, z_far)):
+        return _GenRaysAtFn.apply(extrinsics, intrinsics, z_near, z_far, W, H, idx, is64)
+    with torch.no_grad():
+        e, k = _f(extrinsics), _f(intrinsics)
+        return _gen_rays_at(e, k, _per_camera(z_near, SB, e.device), _per_camera(z_far, SB, e.device), idx, is64, W, H)
+
+
+def _photo_loss(p, t, idx, is64, patch, pool):
+    """fp32 contiguous pred [SB,B,3], target [SB,3,H,W] -> (losses [2], gt_colors [SB,B,3], cell_sign [SB,3,nc,nc] or None)"""
+    SB, B, _ = p.shape
+    H, W = t.shape[2:]
+    L = _lib.lib()
+    n = int(L.diner_photo_loss_workspace_floats(SB, B, patch, pool))
+    if n < 0:
+        raise ValueError(f"photo_loss: bad sizes SB={SB}, B={B}, patch={patch}, pool={pool}")
+    ws = torch.empty(max(n, 2), dtype=torch.float32, device=p.device)
+    gt = torch.empty((SB, B, 3), dtype=torch.float32, device=p.device)
+    losses = torch.empty(2, dtype=torch.float32, device=p.device)
+    nc = patch // pool if patch else 0
+    sign = torch.empty((SB, 3, nc, nc), dtype=torch.float32, device=p.device) if patch else None
+    check(L.diner_photo_loss(p.data_ptr(), t.data_ptr(), idx.data_ptr(), is64, SB, B, H, W, patch, pool, gt.data_ptr(), losses.data_ptr(),
+                             sign.data_ptr() if patch else None, ws.data_ptr(), _st(p.device)), "diner_photo_loss")
+    return losses, gt, sign
+
+
+def photo_loss_backward(pred, gt_colors, cell_sign, g_mse, g_ab, patch, pool):
+    """d_pred [SB,B,3] in fp32 from fp32 contiguous pred, gt_colors and the cell signs :func:`photo_loss` kept; g_mse / g_ab: the two losses'
+    gradients as fp32 device scalars, or None for 0 (``diner_photo_loss_backward``: one elementwise kernel)."""
+    SB, B, _ = pred.shape
+    d = torch.empty((SB, B, 3), dtype=torch.float32, device=pred.device)
+    check(_lib.lib().diner_photo_loss_backward(pred.data_ptr(), gt_colors.data_ptr(), cell_sign.data_ptr() if patch else None,
+                                               None if g_mse is None else g_mse.data_ptr(), None if g_ab is None else g_ab.data_ptr(),
+                                               SB, B, patch, pool, d.data_ptr(), _st(pred.device)), "diner_photo_loss_backward")
+    return d
+
+
+class _PhotoLossFn(torch.autograd.Function):
+    """photo_loss with a backward to pred: forward = diner_photo_loss (the no-grad call's values), backward = diner_photo_loss_backward"""
+
+    @staticmethod
+    def forward(ctx, pred, t, idx, is64, patch, pool):
+        p = _f(pred)
+        losses, gt, sign = _photo_loss(p, t, idx, is64, patch, pool)
+        ctx.save_for_backward(pred)      # (version-checked by autograd: an in-place edit before backward raises)
+        ctx.p, ctx.gt, ctx.sign, ctx.patch, ctx.pool = p, gt, sign, patch, pool
+        ctx.mark_non_differentiable(gt)
+        ctx.set_materialize_grads(False)
+        return losses[0], losses[1], gt
+
+    @staticmethod
+    def backward(ctx, g_mse, g_ab, _g_gt):
+        pred, = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        g_mse, g_ab = (None if g is None else _f(g) for g in (g_mse, g_ab))
+        d = photo_loss_backward(ctx.p, ctx.gt, ctx.sign, g_mse, g_ab, ctx.patch, ctx.pool)
+        return d.reshape(pred.shape).to(pred.dtype), None, None, None, None, None
+
+
+def photo_loss(pred, target_rgb, pix_idcs, patch=None, antibias_downsampling=3):
+    """The photometric losses of ``DINER.calc_losses`` after the renderer (reference src/models/diner.py:265-267, :280-282 and
+    src/losses/antibiasloss.py) in one kernel and a one-block sum: pred [SB,B,3] (the renderer's ``fine.rgb``), target_rgb [SB,3,H,W],
+    pix_idcs [SB,B] (as for :func:`gen_rays_at`; an index outside [0, H*W) is clamped, the result is then unspecified)
+    -> ``(mse, antibias, gt_colors)``:
+
+    * ``gt_colors`` [SB,B,3] = ``target_rgb.view(SB, 3, -1).permute(0, 2, 1)[b, pix_idcs[b]]`` (what the caller's VGG loss needs too);
+    * ``mse`` = ``MSELoss(reduction="mean")(pred, gt_colors)``;
+    * ``antibias`` = ``AntibiasLoss(antibias_downsampling)`` on the two patches ``x.view(SB, s, s, 3).permute(0, 3, 1, 2)`` with
+      ``patch = s`` (``B == s * s``, rays row-major): ``AvgPool2d(p)``, ``p = 2 ** antibias_downsampling``, of both (floor semantics:
+      ``s // p`` cells per side, trailing rows and columns that fill no cell are ignored), then the L1 mean over the
+      ``SB * 3 * (s // p) ** 2`` cells.  With ``patch=None`` it is a zero scalar and no pooling runs.  ``s < p`` raises ``ValueError``
+      (the reference's pool fails there).
+
+    Sums are fp64 per workgroup, added in block order (no atomics: two runs agree bit for bit).  Differentiable with respect to ``pred``
+    (``diner_photo_loss_backward``); ``target_rgb`` and ``pix_idcs`` get no gradient."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or pred.shape[-1] != 3:
+        raise ValueError("photo_loss: pred must be [SB, B, 3]")
+    SB, B, _ = pred.shape
+    if not isinstance(target_rgb, torch.Tensor) or target_rgb.dim() != 4 or target_rgb.shape[:2] != (SB, 3):
+        raise ValueError(f"photo_loss: target_rgb must be [SB = {SB}, 3, H, W]")
+    idx, is64 = _indices(pix_idcs, SB, "photo_loss")
+    if idx.shape[1] != B or SB < 1 or B < 1:
+        raise ValueError(f"photo_loss: pix_idcs {tuple(idx.shape)} does not belong to pred {tuple(pred.shape)} (at least one ray)")
+    pool = 1
+    if patch is not None:
+        patch, n = int(patch), int(antibias_downsampling)
+        if n < 0 or patch < 1 or patch * patch != B:
+            raise ValueError(f"photo_loss: patch={patch} needs B == patch * patch (B = {B}) and antibias_downsampling >= 0")
+        pool = 2 ** n
+        if patch < pool:
+            raise ValueError(f"photo_loss: a {patch} x {patch} patch is smaller than the {pool} x {pool} pooling cell "
+                             f"(antibias_downsampling={n})")
+    patch = patch or 0
+    if not (pred.is_cuda and target_rgb.is_cuda and idx.is_cuda):
+        raise RuntimeError("diner_amd.glue.photo_loss runs on the GPU only")
+    t = _f(target_rgb)
+    if torch.is_grad_enabled() and pred.requires_grad:
+        return _PhotoLossFn.apply(pred, t, idx, is64, patch, pool)
+    with torch.no_grad():
+        losses, gt, _ = _photo_loss(_f(pred), t, idx, is64, patch, pool)
+        return losses[0], losses[1], gt
+
+
+def calc_losses(nerf, renderer, batch, znear, zfar, pix_idcs, patch=None, w_vgg=0., vggloss=None, w_antibias=0., antibias_downsampling=3):
+    """``DINER.calc_losses`` (reference src/models/diner.py:217-290) assembled from the HIP pieces: ``nerf.encode`` (whatever the model has
+    bound, e.g. ``functools.partial(glue.encode, nerf)``) on the batch's source views, :func:`gen_rays_at` for the selected target pixels,
+    ``renderer.forward(model=nerf, rays=rays)``, :func:`photo_loss`, and -- with ``w_vgg > 0`` -- the caller's ``vggloss`` on the NCHW
+    patches.  ``batch``: the reference's keys (``src_rgbs, src_depths, src_depth_stds, src_extrinsics, src_intrinsics, target_rgb,
+    target_extrinsics, target_intrinsics``); ``znear`` / ``zfar``: one value or [SB].  Returns the reference's dict ``rgb_fine, vgg_fine,
+    antibias, total`` with ``total = rgb_fine + w_vgg * vgg_fine + w_antibias * antibias`` (terms with a zero weight are the float 0. and
+    are left out).  ``total`` is a new tensor: the reference adds in place into ``rgb_fine``, which therefore aliases its ``total``.
+
+    ``pix_idcs`` [SB,B] is an argument, the random draw stays the caller's.  The reference's two draws (diner.py:229-247), on the device:
+
+        pix_idcs = torch.randint(0, H * W, (SB, ray_batch_size), device=dev)                       # w_vgg == 0
+
+        s, pad = vgg_spatch, (vgg_spatch + 1) // 2                                                   # w_vgg > 0: an s x s patch
+        fg = batch["target_alpha"][:, 0].clone()
+        fg[..., :pad] = 0; fg[..., :pad, :] = 0; fg[..., -pad:] = 0; fg[..., -pad:, :] = 0
+        centre = torch.multinomial(fg.view(SB, H * W), 1)                                            # [SB,1]
+        ys, xs = torch.meshgrid(torch.arange(s, device=dev), torch.arange(s, device=dev), indexing="ij")
+        pix_idcs = ((centre % W).view(SB, 1, 1) + xs - pad + ((centre // W).view(SB, 1, 1) + ys - pad) * W).flatten(1)   # patch=s
+
+    ``patch`` is required when ``w_vgg > 0`` or ``w_antibias > 0``."""
+    SB, _, H, W = batch["target_rgb"].shape
+    if (w_vgg > 0 or w_antibias > 0) and patch is None:
+        raise ValueError("calc_losses: w_vgg > 0 and w_antibias > 0 need the patch side (patch=s, B == s * s)")
+    if w_vgg > 0 and vggloss is None:
+        raise ValueError("calc_losses: w_vgg > 0 needs vggloss")
+    nerf.encode(images=batch["src_rgbs"], depths=batch["src_depths"], depths_std=batch["src_depth_stds"],
+                extrinsics=batch["src_extrinsics"], intrinsics=batch["src_intrinsics"])
+    rays = gen_rays_at(batch["target_extrinsics"], batch["target_intrinsics"], W, H, znear, zfar, pix_idcs)
+    pred = renderer.forward(model=nerf, rays=rays).fine.rgb
+    loss_fine, loss_antibias, gt_colors = photo_loss(pred, batch["target_rgb"], pix_idcs, patch=patch if w_antibias > 0 else None,
+                                                     antibias_downsampling=antibias_downsampling)
+    total = loss_fine
+    loss_vgg = 0.
+    if w_vgg > 0:
+        s = int(patch)
+        loss_vgg = vggloss(pred.view(SB, s, s, 3).permute(0, 3, 1, 2), gt_colors.view(SB, s, s, 3).permute(0, 3, 1, 2))
+        total = total + w_vgg * loss_vgg
+    if w_antibias > 0:
+        total = total + w_antibias * loss_antibias
+    else:
+        loss_antibias = 0.
+    return dict(rgb_fine=loss_fine, vgg_fine=loss_vgg, antibias=loss_antibias, total=total)

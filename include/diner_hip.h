@@ -211,6 +211,49 @@ int diner_encoder_input(const float *images, int64_t N, int32_t H, int32_t W, in
                         void *stream);
 int diner_encoder_input_backward(const float *d_out, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t pe_freqs, float std0, float std1,
                                  float std2, float *d_images, void *stream);
+/* ---- once per training step: ray selection and the photometric losses (csrc/train_glue.hip) ---- */
+/* The two stretches of DINER.calc_losses (src/models/diner.py:217-290) around renderer.forward (New symbols only: DINER_ABI_VERSION stays
+ * 3).  pix_idcs [SB,B]: the selected pixels, idx = x + y W (diner.py:246), int64 (idx_is_int64 != 0) or int32; an index outside
+ * [0, H W) is clamped into it -- nothing is read or written out of bounds, the result for such an index is unspecified.
+ *
+ * diner_gen_rays_at replaces gen_rays + the selection rays.view(SB, H*W, -1)[batch_idx_helper, pix_idcs] (diner.py:224-227, :257-258):
+ * rays_out [SB,B,8], ray (b, j) = diner_gen_rays' ray of camera b at pixel pix_idcs[b, j], bit for bit (one device function computes
+ * both).  diner_gen_rays_at_backward: d_rays [SB,B,8] -> the outputs of diner_gen_rays_backward (every one written, not accumulated);
+ * reads d_rays and the indices only, a pixel selected twice is two terms.  The same 18 per-camera sums in fp64: per-block partials in the
+ * workspace (diner_gen_rays_at_backward_workspace_floats(SB, B) floats, 8-byte aligned; -1 for bad sizes), a block count that depends on
+ * B only, added in block order -- no atomics, bitwise reproducible.
+ * Before any launch: DINER_E_INVALID for a NULL pointer, SB or B < 0, H or W <= 0, H W >= 2^31; DINER_E_UNSUPPORTED for SB > 65535 or
+ * SB B >= 2^31. */
+int diner_gen_rays_at(const float *extrinsics, const float *intrinsics, const float *z_near, const float *z_far, const void *pix_idcs,
+                      int32_t idx_is_int64, int32_t SB, int32_t B, int32_t H, int32_t W, float *rays_out, void *stream);
+int64_t diner_gen_rays_at_backward_workspace_floats(int32_t SB, int32_t B);
+int diner_gen_rays_at_backward(const float *extrinsics, const float *intrinsics, const float *d_rays, const void *pix_idcs,
+                               int32_t idx_is_int64, int32_t SB, int32_t B, int32_t H, int32_t W, float *d_extrinsics, float *d_intrinsics,
+                               float *d_near, float *d_far, float *workspace, void *stream);
+/* diner_photo_loss replaces the ground-truth gather target_rgb.view(SB, 3, -1).permute(0, 2, 1)[batch_idx_helper, pix_idcs]
+ * (diner.py:265), MSELoss (:267) and AntibiasLoss on the two patches (:280-282, src/losses/antibiasloss.py: AvgPool2d(pool) of both, then
+ * L1Loss).  pred [SB,B,3] (the renderer's fine.rgb), target_rgb [SB,3,H,W] ->
+ *   gt_colors_out [SB,B,3]   = target_rgb[b, :, y, x] at pixel pix_idcs[b, j], bit for bit;
+ *   losses_out[0]            = sum (pred - gt)^2 / (SB B 3);
+ *   losses_out[1]            = with patch = s > 0 (B == s s, ray j = row j / s, column j % s, as view(SB, s, s, 3)) and pool = p = 2^n:
+ *                              sum |avg_cell(pred) - avg_cell(gt)| / (SB 3 nc^2) over the nc = s / p (floor) cells per side and channel
+ *                              (AvgPool2d's floor semantics: trailing rows / columns that fill no cell are ignored); 0 with patch = 0;
+ *   cell_sign_out [SB,3,nc,nc] = sign of that pooled difference (-1, 0, 1), kept for the backward (not read with patch = 0, may be NULL).
+ * Prediction and ground truth of a cell are pooled separately, in the same order, then subtracted: equal cells give an exact 0.  One
+ * workgroup per (scene, cell row, chunk of cells) -- or 1024 rays without a patch -- writes an fp64 partial pair to the workspace
+ * (diner_photo_loss_workspace_floats floats, 8-byte aligned; -1 for bad sizes), a one-block pass adds them in block order: no atomics,
+ * bitwise reproducible.
+ * diner_photo_loss_backward: d_pred_out [SB,B,3] = g_mse 2 (pred - gt) / (SB B 3) + g_ab cell_sign / (p^2 SB 3 nc^2), formed in fp64 and
+ * rounded once; a pixel outside every cell gets the first term only.  g_mse, g_ab: device scalars (NULL: 0).  target_rgb and the indices
+ * get no gradient.
+ * Before any launch: DINER_E_INVALID for a NULL pointer, SB or B <= 0, B != s s, pool not a power of two, s < pool;
+ * DINER_E_UNSUPPORTED for pool > 32 (a cell row is pooled from LDS) and the limits of diner_gen_rays_at. */
+int64_t diner_photo_loss_workspace_floats(int32_t SB, int32_t B, int32_t patch, int32_t pool);
+int diner_photo_loss(const float *pred, const float *target_rgb, const void *pix_idcs, int32_t idx_is_int64, int32_t SB, int32_t B, int32_t H,
+                     int32_t W, int32_t patch, int32_t pool, float *gt_colors_out, float *losses_out, float *cell_sign_out, float *workspace,
+                     void *stream);
+int diner_photo_loss_backward(const float *pred, const float *gt_colors, const float *cell_sign, const float *g_mse, const float *g_ab,
+                              int32_t SB, int32_t B, int32_t patch, int32_t pool, float *d_pred_out, void *stream);
 /* ---- once per weight version: MFMA-fragment-ordered copies of the fusion MLP (one image per
  * precision mode, both in the same buffer) ------------------------------------------------ */
 int64_t diner_mlp_packed_floats(void);
