@@ -205,6 +205,8 @@ SYMBOLS = {
     # the ABI version stays 3: new entry points only)
     "diner_assemble_latent": (C.c_int, [C.POINTER(DinerLatentLevels), _I32, _I64, _I32, _I32, _P, _P]),
     "diner_assemble_latent_backward": (C.c_int, [_P, _I32, _I64, _I32, _I32, C.POINTER(DinerLatentLevels), _P]),
+    "diner_assemble_latent_bicubic": (C.c_int, [C.POINTER(DinerLatentLevels), _I32, _I64, _I32, _I32, _P, _P]),
+    "diner_assemble_latent_bicubic_backward": (C.c_int, [_P, _I32, _I64, _I32, _I32, C.POINTER(DinerLatentLevels), _P]),
     # conv1's input (the head of the encoder: normalise, replicate pad, the padding's positional encoding) and its adjoint to the images
     # (csrc/encoder_input.hip; the ABI version stays 3: new entry points only)
     "diner_encoder_input": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F32, _F32, _F32, _F32, _F32, _F32, _P, _P]),

@@ -6,7 +6,8 @@ with the reference's own function signatures so they can replace them in place:
 * :func:`depth2normal`  -- reference ``src/util/depth2normal.py:7-87``
 
 and the tail of the encoder: :func:`assemble_latent` -- reference ``src/models/image_encoder.py:262-272`` (the feature levels upsampled to
-the first one's size and concatenated), written once in the NHWC layout the render and training kernels read;
+the first one's size and concatenated), written once in the NHWC layout the render and training kernels read
+(:func:`assemble_latent_bicubic` for ``upsample_interp="bicubic"``);
 its head: :func:`encoder_input` -- reference ``src/models/pixelnerf.py:44`` + ``src/models/image_encoder.py:222-232`` (conv1's input: the
 images normalised and replicate-padded, plus the positional encoding of the padding);
 and both around the model's own CNN trunk: :func:`encode`, with ``PixelNeRF.encode``'s signature (reference
@@ -153,42 +154,47 @@ def _levels_struct(ts):
     return lv
 
 
-def _assemble_check(levels, SB, NV, mode):
-    if mode != "bilinear":   # (the reference's nearest branch is unreachable: it compares with "nearest ", image_encoder.py:262)
-        raise NotImplementedError(f"assemble_latent: upsample mode {mode!r} is not implemented (the encoder's tail is bilinear, "
-                                  "align_corners=True)")
+def _assemble_check(levels, SB, NV, who):
     levels = list(levels)
     if not 1 <= len(levels) <= _lib.LATENT_MAX_LEVELS:
-        raise ValueError(f"assemble_latent: {len(levels)} levels, expected 1..{_lib.LATENT_MAX_LEVELS}")
+        raise ValueError(f"{who}: {len(levels)} levels, expected 1..{_lib.LATENT_MAX_LEVELS}")
     N = int(SB) * int(NV)
     for t in levels:
         if not t.is_cuda:
-            raise RuntimeError("diner_amd.glue.assemble_latent runs on the GPU only")
+            raise RuntimeError(f"diner_amd.glue.{who} runs on the GPU only")
         if t.dim() != 4 or t.shape[0] != N:
-            raise ValueError(f"assemble_latent: a level must be [SB*NV = {N}, C_l, h_l, w_l], not {tuple(t.shape)}")
+            raise ValueError(f"{who}: a level must be [SB*NV = {N}, C_l, h_l, w_l], not {tuple(t.shape)}")
     return levels
 
 
-def _assemble(lv, SB, NV):
+def _assemble(lv, SB, NV, fn="diner_assemble_latent"):
     """fp32 contiguous levels [SB*NV, C_l, h_l, w_l] -> the NHWC buffer [SB, NV, h, w, C]"""
     h, w = lv[0].shape[2:]
     out = torch.empty((SB, NV, h, w, sum(t.shape[1] for t in lv)), dtype=torch.float32, device=lv[0].device)
-    check(_lib.lib().diner_assemble_latent(C.byref(_levels_struct(lv)), len(lv), SB * NV, h, w, out.data_ptr(), _st(out.device)),
-          "diner_assemble_latent")
+    check(getattr(_lib.lib(), fn)(C.byref(_levels_struct(lv)), len(lv), SB * NV, h, w, out.data_ptr(), _st(out.device)), fn)
     return out
 
 
-def assemble_latent_backward(d_latent, level_shapes):
-    """Adjoint of :func:`assemble_latent`: d_latent of logical shape [SB, NV, C, h, w] (made NHWC-strided fp32 once if it is not) ->
-    the levels' gradients [SB*NV, C_l, h_l, w_l] in fp32 (``diner_assemble_latent_backward``: gather form, bitwise reproducible)."""
+def _assemble_backward(d_latent, level_shapes, fn):
     SB, NV, _, h, w = d_latent.shape
     g = d_latent.detach().permute(0, 1, 3, 4, 2)
     if g.dtype != torch.float32 or not g.is_contiguous():
         g = g.to(torch.float32).contiguous()
     grads = [torch.empty(tuple(s), dtype=torch.float32, device=g.device) for s in level_shapes]
-    check(_lib.lib().diner_assemble_latent_backward(g.data_ptr(), len(grads), SB * NV, h, w, C.byref(_levels_struct(grads)), _st(g.device)),
-          "diner_assemble_latent_backward")
+    check(getattr(_lib.lib(), fn)(g.data_ptr(), len(grads), SB * NV, h, w, C.byref(_levels_struct(grads)), _st(g.device)), fn)
     return grads
+
+
+def assemble_latent_backward(d_latent, level_shapes):
+    """Adjoint of :func:`assemble_latent`: d_latent of logical shape [SB, NV, C, h, w] (made NHWC-strided fp32 once if it is not) ->
+    the levels' gradients [SB*NV, C_l, h_l, w_l] in fp32 (``diner_assemble_latent_backward``: gather form, bitwise reproducible)."""
+    return _assemble_backward(d_latent, level_shapes, "diner_assemble_latent_backward")
+
+
+def assemble_latent_bicubic_backward(d_latent, level_shapes):
+    """Adjoint of :func:`assemble_latent_bicubic`, with :func:`assemble_latent_backward`'s contract
+    (``diner_assemble_latent_bicubic_backward``: gather form, bitwise reproducible)."""
+    return _assemble_backward(d_latent, level_shapes, "diner_assemble_latent_bicubic_backward")
 
 
 class _AssembleLatentFn(torch.autograd.Function):
@@ -214,12 +220,48 @@ def assemble_latent(levels, SB, NV, mode="bilinear"):
     [SB, NV, h, w, C] buffer, the layout the render and training kernels read -- :func:`latent_is_packed` is true for it and the renderer
     then takes the buffer as it is (no copy, no re-pack).  ``.shape``, ``grid_sample`` and indexing see an ordinary tensor.
     Differentiable with respect to every level (``diner_assemble_latent_backward``, deterministic)."""
-    levels = _assemble_check(levels, SB, NV, mode)
+    if mode == "bicubic":
+        raise NotImplementedError("assemble_latent: upsample mode 'bicubic' is not implemented by this function (it is bilinear, "
+                                  "align_corners=True): call assemble_latent_bicubic")
+    if mode != "bilinear":   # (the reference's nearest branch is unreachable: it compares with "nearest ", image_encoder.py:262)
+        raise NotImplementedError(f"assemble_latent: upsample mode {mode!r} is not implemented (the encoder's tail is bilinear, "
+                                  "align_corners=True)")
+    levels = _assemble_check(levels, SB, NV, "assemble_latent")
     SB, NV = int(SB), int(NV)
     if torch.is_grad_enabled() and any(t.requires_grad for t in levels):
         return _AssembleLatentFn.apply(SB, NV, *levels)
     with torch.no_grad():
         return _assemble([_f(t) for t in levels], SB, NV).permute(0, 1, 4, 2, 3)
+
+
+class _AssembleLatentBicubicFn(torch.autograd.Function):
+    """assemble_latent_bicubic with a backward: forward = diner_assemble_latent_bicubic (the no-grad call's values), backward = its
+    adjoint kernel"""
+
+    @staticmethod
+    def forward(ctx, SB, NV, *levels):
+        lv = [_f(t) for t in levels]
+        ctx.shapes, ctx.dtypes = [tuple(t.shape) for t in lv], [t.dtype for t in levels]
+        return _assemble(lv, SB, NV, "diner_assemble_latent_bicubic").permute(0, 1, 4, 2, 3)
+
+    @staticmethod
+    def backward(ctx, d_latent):
+        grads = assemble_latent_bicubic_backward(d_latent, ctx.shapes)
+        return (None, None, *[g.to(dt) if need else None for g, dt, need in zip(grads, ctx.dtypes, ctx.needs_input_grad[2:])])
+
+
+def assemble_latent_bicubic(levels, SB, NV):
+    """:func:`assemble_latent` for ``SpatialEncoder(upsample_interp="bicubic")``: every level is upsampled to ``levels[0]``'s (h, w) like
+    ``F.interpolate(mode="bicubic", align_corners=True)`` (ATen's upsample_bicubic2d: 16 taps, A = -0.75, clamped at the borders) and the
+    results are concatenated along the channels.  The same contract: the logical shape [SB, NV, C, h, w] over a contiguous
+    [SB, NV, h, w, C] buffer (:func:`latent_is_packed` is true for it), a level of the output's size bit-identical, differentiable with
+    respect to every level (``diner_assemble_latent_bicubic_backward``, deterministic)."""
+    levels = _assemble_check(levels, SB, NV, "assemble_latent_bicubic")
+    SB, NV = int(SB), int(NV)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in levels):
+        return _AssembleLatentBicubicFn.apply(SB, NV, *levels)
+    with torch.no_grad():
+        return _assemble([_f(t) for t in levels], SB, NV, "diner_assemble_latent_bicubic").permute(0, 1, 4, 2, 3)
 
 
 def nhwc_strided(t) -> bool:
@@ -335,14 +377,15 @@ def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMA
 def encode(model, images, depths, depths_std, extrinsics, intrinsics):
     """Drop-in for ``PixelNeRF.encode`` (reference src/models/pixelnerf.py:35-53) with ``SpatialEncoder.forward``
     (src/models/image_encoder.py:206-272) inside: images [SB,NV,3,H,W], depths, depths_std [SB,NV,1,H,W], extrinsics [SB,NV,4,4],
-    intrinsics [SB,NV,3,3].  The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`)
-    run on the HIP kernels; the model's own trunk modules (``model.encoder.model``: conv1, bn1, relu, maxpool, layer1..) run unchanged on
-    PyTorch in between.  Leaves the model in the state the reference's encode leaves it in, with ``encoder.latent`` in the layout the
-    render and training kernels read (:func:`latent_is_packed`).  ``model.encode = functools.partial(glue.encode, model)``."""
+    intrinsics [SB,NV,3,3].  The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`,
+    or :func:`assemble_latent_bicubic` for ``upsample_interp="bicubic"``) run on the HIP kernels; the model's own trunk modules
+    (``model.encoder.model``: conv1, bn1, relu, maxpool, layer1..) run unchanged on PyTorch in between.  Leaves the model in the state the
+    reference's encode leaves it in, with ``encoder.latent`` in the layout the render and training kernels read
+    (:func:`latent_is_packed`).  ``model.encode = functools.partial(glue.encode, model)``."""
     enc = model.encoder
-    if enc.upsample_interp != "bilinear":   # before any device work; there is no eager fallback
-        raise NotImplementedError(f"encode: upsample_interp {enc.upsample_interp!r} is not implemented (assemble_latent is bilinear, "
-                                  "align_corners=True)")
+    if enc.upsample_interp not in ("bilinear", "bicubic"):   # before any device work; there is no eager fallback
+        raise NotImplementedError(f"encode: upsample_interp {enc.upsample_interp!r} is not implemented (the two modes torch accepts with "
+                                  "align_corners=True, 'bilinear' and 'bicubic', are)")
     SB, NV, _, H, W = images.shape
     norm = getattr(model, "normalize_rgb", None)
     mean, std = getattr(norm, "mean", None), getattr(norm, "std", None)
@@ -363,7 +406,10 @@ def encode(model, images, depths, depths_std, extrinsics, intrinsics):
         if enc.num_layers > i:
             x = getattr(trunk, f"layer{i}")(x)
             levels.append(x)
-    enc.latent = assemble_latent(levels, SB, NV, mode=enc.upsample_interp)
+    if enc.upsample_interp == "bicubic":
+        enc.latent = assemble_latent_bicubic(levels, SB, NV)
+    else:
+        enc.latent = assemble_latent(levels, SB, NV, mode=enc.upsample_interp)
     model.poses = extrinsics
     model.c = intrinsics[:, :, :2, -1]
     model.focal = torch.stack((intrinsics[:, :, 0, 0], intrinsics[:, :, 1, 1]), dim=-1)

@@ -188,6 +188,27 @@ int diner_assemble_latent(const DinerLatentLevels *levels, int32_t n_levels, int
                           void *stream);
 int diner_assemble_latent_backward(const float *d_out_nhwc, int32_t n_levels, int64_t N, int32_t h, int32_t w,
                                    const DinerLatentLevels *levels_grad, void *stream);
+/* The same tail for SpatialEncoder's upsample_interp = "bicubic" (src/models/image_encoder.py:262-272 with
+ * F.interpolate(mode="bicubic", align_corners=True); "bilinear" and "bicubic" are the two modes torch accepts there): the same level
+ * descriptors, envelope (1..5 levels, every C_l a multiple of 8, C <= 1024, N <= 65535), output layout and refusals as the pair above, with
+ * messages that start with "assemble_latent_bicubic".  ATen's upsample_bicubic2d, per axis:
+ *   scale = (in - 1) / (out - 1) in fp32 (0 when out == 1);  src = scale * dst;  i = min((int)src, in - 1);  t = src - i;
+ *   taps i - 1, i, i + 1, i + 2, each clamped to [0, in - 1];  A = -0.75;
+ *   w0 = ((A (t + 1) - 5 A) (t + 1) + 8 A) (t + 1) - 4 A       w1 = ((A + 2) t - (A + 3)) t t + 1
+ *   w3 = ((A (2 - t) - 5 A) (2 - t) + 8 A) (2 - t) - 4 A       w2 = ((A + 2) (1 - t) - (A + 3)) (1 - t) (1 - t) + 1
+ *   out[n, y, x, off_l + c] = sum_i wy_i * (sum_j wx_j * level_l[n, c, iy_i, ix_j])   (rows inside, then columns; sums left to right).
+ * The four cubics are evaluated in their factored forms, w0 = A t (1 - t)^2, w1 = (1 - t) (1 + t - (A + 2) t^2), w2 = w1(1 - t),
+ * w3 = w0(1 - t): the same polynomials, each coefficient within a few ulp of itself (the Horner forms above leave up to 12 * 2^-24
+ * absolute on coefficients as small as 0.02, which the gradient of a level larger than the output would show).
+ * A level of the output's size is copied: bit-identical whatever it holds (t = 0 gives the weights (0, 1, 0, 0), but 0 * inf never occurs).
+ * diner_assemble_latent_bicubic_backward is the exact adjoint in gather form: every coarse texel sums weight * d_out over the fine pixels
+ * that have at least one clamped tap on it, rows outside, columns inside, ascending (no atomics: run-to-run deterministic); per axis the
+ * weight is the sum of the coefficients whose clamped tap is the texel (at a border several taps of one fine pixel land on it), from the
+ * same device function as the forward.  Every element of every level's gradient is WRITTEN. */
+int diner_assemble_latent_bicubic(const DinerLatentLevels *levels, int32_t n_levels, int64_t N, int32_t h, int32_t w, float *out_nhwc,
+                                  void *stream);
+int diner_assemble_latent_bicubic_backward(const float *d_out_nhwc, int32_t n_levels, int64_t N, int32_t h, int32_t w,
+                                           const DinerLatentLevels *levels_grad, void *stream);
 /* ---- once per encode(): conv1's input, the head of the encoder ----------------------------- */
 /* Replaces PixelNeRF.encode's Normalize (src/models/pixelnerf.py:44) and the head of SpatialEncoder.forward (pad_layer, linspace /
  * meshgrid / PositionalEncoding / interior zeroing / expand / cat, src/models/image_encoder.py:222-232) in one launch (New symbols only:

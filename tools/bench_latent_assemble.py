@@ -12,6 +12,16 @@ before glue.assemble_latent and on the new kernels, at two sizes:
 Device-event times, median over --steps after --warmup.  A record, not a gate: writes --out (profiles/latent_assemble.json).
 
     python tools/bench_latent_assemble.py [--steps 10] [--warmup 3] [--train-steps 3] [--sizes cfg3,train] [--out FILE]
+
+``--mode bicubic``: the tail of an encoder with upsample_interp="bicubic" at cfg3's pyramid, forward and backward, in one process, median
+of 5 runs after 2 warm-ups (device events), with the number of device launches of each (torch.profiler's device events, taken after the
+times):
+``aten`` = the sequence the reference runs on the same GPU, F.interpolate(mode="bicubic", align_corners=True) per level + cat +
+diner_pack_latent, and for the backward torch autograd of that sequence (the gradient arrives NCHW-strided: the transposed view of the
+NHWC buffer goes through cat's backward as it is); ``packed`` = diner_assemble_latent_bicubic / _backward.  There is no earlier bicubic
+path of this project to compare with.  Writes profiles/latent_assemble_bicubic.json.
+
+    python tools/bench_latent_assemble.py --mode bicubic [--out FILE]
 """
 from __future__ import annotations
 
@@ -29,14 +39,114 @@ SIZES = {"cfg3": dict(res=512, NV=4), "train": dict(res=256, NV=4)}
 PYRAMID = [(64, 1), (64, 2), (128, 4), (256, 8)]      # (channels, stride)
 
 
+def bicubic(out_path):
+    """--mode bicubic (see the module's docstring)"""
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    from diner_amd import _lib, glue
+    from diner_amd._lib import check
+    from synthetic import synth
+
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    STEPS, WARMUP = 5, 2
+
+    def timed(fn):
+        for _ in range(WARMUP):
+            fn()
+        ms = []
+        for _ in range(STEPS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
+
+    def launches(fn):
+        """device events (kernels and copies) of one call, as tools/bench_encoder_input.py counts them; raises when the profiler records
+        none: a count of 0 is not a result"""
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if "cuda" in str(getattr(e, "device_type", "")).lower())
+        if n == 0:
+            raise RuntimeError("torch.profiler recorded no device events")
+        return n
+
+    res, NV = SIZES["cfg3"]["res"], SIZES["cfg3"]["NV"]
+    sc = synth.make_scene(res, res, NV, seed=0, with_latent=False)
+    h, w = sc.latent_hw
+    g = torch.Generator(device=dev).manual_seed(1)
+    levels = [torch.randn((NV, c, -(-h // s), -(-w // s)), device=dev, generator=g) for c, s in PYRAMID]
+    Cc = sum(c for c, _ in PYRAMID)
+    d_nhwc = torch.randn((1, NV, h, w, Cc), device=dev, generator=g)
+    lat_bytes = d_nhwc.numel() * 4
+    rec = {"device": torch.cuda.get_device_name(0), "steps": STEPS, "warmup": WARMUP, "size": "cfg3", "N": NV, "C": Cc, "h": h, "w": w,
+           "latent_GB": lat_bytes / 1e9, "levels": [list(t.shape) for t in levels]}
+
+    def upcat(lv):
+        return torch.cat([F.interpolate(t, size=(h, w), mode="bicubic", align_corners=True) for t in lv], 1)
+
+    def fwd_aten():
+        with torch.no_grad():
+            lat = upcat(levels)
+            out = torch.empty((1, NV, h, w, Cc), dtype=torch.float32, device=dev)
+            check(L.diner_pack_latent(p(lat), NV, Cc, h, w, p(out), st()), "diner_pack_latent")
+        return out
+
+    def fwd_packed():
+        return glue.assemble_latent_bicubic(levels, 1, NV)
+
+    lv_g = [t.clone().requires_grad_(True) for t in levels]
+    lat_g = upcat(lv_g)               # the autograd graph of the ATen sequence, built once: its backward is what is timed
+    d_view = d_nhwc[0].permute(0, 3, 1, 2)
+
+    def bwd_aten():
+        return torch.autograd.grad(lat_g, lv_g, d_view, retain_graph=True)
+
+    shapes = [tuple(t.shape) for t in levels]
+
+    def bwd_packed():
+        return glue.assemble_latent_bicubic_backward(d_nhwc.permute(0, 1, 4, 2, 3), shapes)
+
+    a, b = fwd_packed().permute(0, 1, 3, 4, 2), fwd_aten()
+    rec["agreement"] = {"same_size_level_bit_identical": bool(torch.equal(a[..., :64], b[..., :64])),
+                        "forward_max_abs_diff": float((a - b).abs().max()),
+                        "backward_max_rel_diff": max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(bwd_packed(), bwd_aten()))}
+    del a, b
+    fns = (("forward_aten", fwd_aten), ("forward_packed", fwd_packed), ("backward_aten", bwd_aten), ("backward_packed", bwd_packed))
+    for key, fn in fns:
+        rec[key + "_ms"] = timed(fn)
+    for key, fn in fns:               # after every time is taken: the profiler slows the host
+        rec[key + "_launches"] = launches(fn)
+    need = lat_bytes + sum(t.numel() * 4 for t in levels)     # every level read once + the latent written once (forward); the reverse
+    rec["packed_GBps"] = {"forward": need / rec["forward_packed_ms"]["median"] / 1e6, "backward": need / rec["backward_packed_ms"]["median"] / 1e6}
+    print(json.dumps(rec), flush=True)
+    out = Path(out_path)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(rec, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("bilinear", "bicubic"), default="bilinear")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--train-steps", type=int, default=3)
     ap.add_argument("--sizes", default="cfg3,train")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "latent_assemble.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.mode == "bicubic":
+        return bicubic(a.out or str(ROOT / "profiles" / "latent_assemble_bicubic.json"))
+    a.out = a.out or str(ROOT / "profiles" / "latent_assemble.json")
 
     import numpy as np
     import torch
