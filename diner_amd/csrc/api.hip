@@ -822,7 +822,7 @@ static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatent
     return diner_composite(rays, z, rgbsigma, N, cfg->n_samples, white_bkgd, rgb_out, depth_out, weights_out, status, stream);
 }
 
-#define DINER_GEN_ENTRY_POINTS(SUFFIX, F16)                                                                                                  \
+#define DEFINE_GEN_ENTRY_POINTS(SUFFIX, F16)                                                                                                  \
     int diner_render_points_gen##SUFFIX(const DinerScene *scene, const DinerMlpShape *shape, const float *mlp_packed, const float *rays,     \
                                         const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)                            \
     {                                                                                                                                        \
@@ -868,12 +868,12 @@ static int render_image_gen(bool f16, const DinerScene *scene, const DinerLatent
                                 weights_out, status, stream);                                                                                \
     }
 
-DINER_GEN_ENTRY_POINTS(, false)
-DINER_GEN_ENTRY_POINTS(_f16, true)
-#undef DINER_GEN_ENTRY_POINTS
+DEFINE_GEN_ENTRY_POINTS(, false)
+DEFINE_GEN_ENTRY_POINTS(_f16, true)
+#undef DEFINE_GEN_ENTRY_POINTS
 
 /* ---- the bicubic latent lookup (points_mlp_gen_bc.hip, points_mlp_gen_f16_bc.hip, train_gen_bc.hip) ------------------------------ */
-#define DINER_GEN_BC_ENTRY_POINTS(SUFFIX, F16)                                                                                               \
+#define DEFINE_GEN_BC_ENTRY_POINTS(SUFFIX, F16)                                                                                               \
     int diner_render_points_gen##SUFFIX##_bc(const DinerScene *scene, int32_t padding, const DinerMlpShape *shape, const float *mlp_packed,  \
                                              const float *rays, const float *z, int64_t NR, int32_t K, float *rgbsigma_out, void *stream)    \
     {                                                                                                                                        \
@@ -899,9 +899,9 @@ DINER_GEN_ENTRY_POINTS(_f16, true)
                                 weights_out, status, stream, padding);                                                                       \
     }
 
-DINER_GEN_BC_ENTRY_POINTS(, false)
-DINER_GEN_BC_ENTRY_POINTS(_f16, true)
-#undef DINER_GEN_BC_ENTRY_POINTS
+DEFINE_GEN_BC_ENTRY_POINTS(, false)
+DEFINE_GEN_BC_ENTRY_POINTS(_f16, true)
+#undef DEFINE_GEN_BC_ENTRY_POINTS
 
 /* ---- lin_z hoisted into per-texel maps (linz_maps_gen.hip, points_mlp_gen_lz.hip, points_mlp_gen_f16_lz.hip and their _bc twins) -- */
 int64_t diner_linz_maps_gen_floats(const DinerScene *scene, const DinerMlpShape *shape)

@@ -6,10 +6,8 @@
 //
 // An exact fp32 GEMM (v_mfma_f32_32x32x2_f32) of the NHWC latent [texels, d_latent] with each lin_z[b] of the image diner_pack_mlp_gen
 // writes: 64 texels per workgroup, the A operand in the 128-KiB LDS image of points_mlp_gen.hip, d_latent above 512 in 512-column pieces,
-// the device gemm() and the <RB, CT> instantiations of that file.  One builder serves both precisions.
-#define DINER_GEN_IX     // the packers and check_shape stay in points_mlp_gen.hip
-#define DINER_GEN_MAPS   // of that file: the layout and gemm() only
-#include "points_mlp_gen.hip"
+// the device gemm() and the <RB, CT> instantiations of points_mlp_gen_kernel.hpp.  One builder serves both precisions.
+#include "points_mlp_gen_kernel.hpp"   // the layout and gemm() only
 
 namespace diner {
 namespace gen {

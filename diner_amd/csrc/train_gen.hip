@@ -10,16 +10,14 @@
 //   point_inputs_bwd_gen   the transpose of point_inputs_gen to the rays, cameras and depth maps (point_inputs_bwd_kernel of
 //                          train.hip for any F, ld_in and C), same per-row records and fixed-order reductions
 // train.hip is left as it is: its code objects (the standard path's) do not change with this file.
-// train_gen_bc.hip compiles this file a second time with DINER_TRAIN_GEN_BC defined: the two point-input kernels are then
-// point_inputs_gen_bc_kernel / point_inputs_bwd_gen_bc_kernel, the 16-tap bicubic lookup (common.hpp bicubic_footprint) and its
-// gradient with respect to the grid, next to bicubic_scatter_kernel -- in a code object of their own; the GEMM and the reductions stay here.
-#include "common.hpp"
+// The point-input kernels are templates on the lookup (train_gen_points.hpp): this file instantiates the 4-tap forms, train_gen_bc.hip the
+// 16-tap bicubic ones next to bicubic_scatter_kernel, in a code object of their own; the GEMM and the reductions are here.
+#include "train_gen_points.hpp"
 
 namespace diner {
 
 namespace train_gen {
 
-#ifndef DINER_TRAIN_GEN_BC
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -226,265 +224,7 @@ __global__ __launch_bounds__(256) void gemm_act_kernel(GemmArgs g)
     }
     epilogue(g, acc, m0, n0, wm, wn, lane);
 }
-#endif  // DINER_TRAIN_GEN_BC
 
-// ---- per-(view, point) MLP inputs of any num_freqs F and latent width C ---------------------------------------------------------
-// rows are view-major: row = v*P + p.  in [R, ld_in]: pixelnerf.py:128's 7 + 8F inputs in point_inputs_kernel's column order
-//   [x_cam 3 | sin(f_j x_cam + phi_j) 6F | R d_w 3 | depth_dist 1 | sin(f_j depth_dist + phi_j) 2F | 0 ...]
-// with sinf and the expression of the shape-general inference kernel (points_mlp_gen.hip); zlat [R, C]: the latent lookup of the
-// scene's DINER_INDEX_* mode from the NHWC latent; taps [R, 8]: its 4 texel indices (int bits) and weights.
-// Bicubic (DINER_TRAIN_GEN_BC): taps [R, 16] = the 4 columns and 4 rows of the footprint (int bits), then cx[4], cy[4].
-#ifdef DINER_TRAIN_GEN_BC
-#define point_inputs_gen_kernel point_inputs_gen_bc_kernel
-#define point_inputs_bwd_gen_kernel point_inputs_bwd_gen_bc_kernel
-#endif
-__global__ __launch_bounds__(64) void point_inputs_gen_kernel(DinerScene s, const float *__restrict__ latent_nhwc,
-                                                              const float *__restrict__ rays, const float *__restrict__ zsamp,
-                                                              int64_t NR, int K, int sb, int ix_interp, int ix_padding,
-                                                              float *__restrict__ in, int64_t ld_in, float *__restrict__ zlat,
-                                                              float *__restrict__ taps_out)
-{
-    const int64_t P = NR * (int64_t)K, row = blockIdx.x;
-    const int v = (int)(row / P);
-    const int64_t p = row - (int64_t)v * P;
-    const int lane = threadIdx.x;
-    const float *rp = rays + ((int64_t)sb * NR + p / K) * 8;
-    const float zz = zsamp[(int64_t)sb * P + p];
-    const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
-    const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
-    const View vw = load_view(s, sb, v);
-    float px, py, pz, u, w, dcx, dcy, dcz;
-    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // pixelnerf.py:91-93,105-108
-    rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                                           // :99-101
-    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;                    // :114-115
-    const int F = s.num_freqs, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
-    const float half_pi = 1.5707963267948966f;
-    for (int e = lane; e < ld_in; e += 64) {
-        float val;
-        if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-        else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-            val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-        else if (e == e_dir) val = delta;
-        else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-            val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else val = 0.0f;
-        in[row * ld_in + e] = val;
-    }
-    // footprint of the lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-#ifdef DINER_TRAIN_GEN_BC
-    const BicubicFoot f = bicubic_footprint(u, w, sxl, syl, s.w, s.h, ix_padding);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            taps_out[row * 16 + i] = __int_as_float(f.x[i]); taps_out[row * 16 + 4 + i] = __int_as_float(f.y[i]);
-            taps_out[row * 16 + 8 + i] = f.cx[i]; taps_out[row * 16 + 12 + i] = f.cy[i];
-        }
-    }
-    const float *lat = latent_nhwc + ((int64_t)sb * s.NV + v) * (int64_t)s.h * s.w * s.C;
-    for (int ch = lane; ch < s.C; ch += 64) {   // sum_j cy[j] * (sum_i cx[i] * texel_ij): the inference kernels' order and contraction
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float *lr = lat + (int64_t)f.y[j] * s.w * s.C + ch;
-            float t[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) t[i] = lr[(int64_t)f.x[i] * s.C];
-            const float rowv = __builtin_fmaf(t[3], f.cx[3], __builtin_fmaf(t[2], f.cx[2], __builtin_fmaf(t[1], f.cx[1], t[0] * f.cx[0])));
-            acc = j == 0 ? rowv * f.cy[0] : __builtin_fmaf(rowv, f.cy[j], acc);
-        }
-        zlat[row * s.C + ch] = acc;
-    }
-#else
-    const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
-    const int o[4] = {f.y0 * s.w + f.x0, f.y0 * s.w + f.x1, f.y1 * s.w + f.x0, f.y1 * s.w + f.x1};
-    const float wt[4] = {f.nw, f.ne, f.sw, f.se};
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { taps_out[row * 8 + i] = __int_as_float(o[i]); taps_out[row * 8 + 4 + i] = wt[i]; }
-    }
-    const float *lat = latent_nhwc + ((int64_t)sb * s.NV + v) * (int64_t)s.h * s.w * s.C;
-    for (int ch = lane; ch < s.C; ch += 64) {
-        float t[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t[i] = lat[(int64_t)o[i] * s.C + ch];
-        zlat[row * s.C + ch] = __builtin_fmaf(t[3], wt[3], __builtin_fmaf(t[2], wt[2], __builtin_fmaf(t[1], wt[1], t[0] * wt[0])));
-    }
-#endif
-}
-
-// ---- the transpose of point_inputs_gen_kernel to the geometric leaves (train.hip point_inputs_bwd_kernel for any F, ld_in, C) ---
-constexpr int CAMG_COLS = 24;   // d_o 3, d_d 3, d_R 9 (row-major), d_t 3, d_focal 2, d_c 2, d_image_shape 2
-constexpr int CAMG_BLOCKS = 256;   // per-view partial sums of the pose / intrinsics reduction (at most)
-
-// ATen's clip_coordinates_set_grad + reflect_coordinates_set_grad (align_corners=False)
-__device__ __forceinline__ float pad_coord_grad(float x, int size, int padding, float &g)
-{
-    g = 1.0f;
-    if (padding == DINER_INDEX_PAD_REFLECTION) {
-        float in = x + 0.5f;                  // reflect over [-0.5, size - 0.5]
-        float m = 1.0f;
-        if (in < 0.0f) { m = -1.0f; in = -in; }
-        const float span = (float)size, extra = fmodf(in, span);
-        const int flips = (int)floorf(in / span);
-        if (flips % 2 == 0) { g = m; x = extra - 0.5f; }
-        else { g = -m; x = span - extra - 0.5f; }
-    }
-    if (padding != DINER_INDEX_PAD_ZEROS) {
-        if (x <= 0.0f || x >= (float)(size - 1)) g = 0.0f;
-        x = clipf(x, (float)(size - 1));
-    }
-    return x;
-}
-
-__global__ __launch_bounds__(64) void point_inputs_bwd_gen_kernel(DinerScene s, const float *__restrict__ latent_nhwc,
-                                                                  const float *__restrict__ rays, const float *__restrict__ zsamp,
-                                                                  int64_t NR, int K, int sb, int ix_interp, int ix_padding,
-                                                                  const float *__restrict__ d_in, int64_t ld_in,
-                                                                  const float *__restrict__ d_zlat, float *__restrict__ rowg,
-                                                                  float *__restrict__ d_depths)
-{
-    const int64_t P = NR * (int64_t)K, row = blockIdx.x;
-    const int v = (int)(row / P);
-    const int64_t p = row - (int64_t)v * P;
-    const int lane = threadIdx.x;
-    const float *rp = rays + ((int64_t)sb * NR + p / K) * 8;
-    const float zz = zsamp[(int64_t)sb * P + p];
-    const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
-    const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
-    const View vw = load_view(s, sb, v);
-    float px, py, pz, u, w;
-    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // pixelnerf.py:91-93,105-108
-    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;
-
-    // positional encodings: d sin(f a + phi) / d a = f cos(f a + phi) (positional_encoding.py:45-49); lanes stride the inputs,
-    // each lane sums its own in a fixed order before the wave sums
-    const float *gin = d_in + row * ld_in;
-    const int F = s.num_freqs, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1, d_in_n = e_pe1 + 2 * F;
-    const float half_pi = 1.5707963267948966f;
-    float t_p[4] = {0.f, 0.f, 0.f, 0.f};   // -> x_cam.x, x_cam.y, x_cam.z, depth_dist
-    for (int e = lane; e < d_in_n; e += 64) {
-        const float g = gin[e];
-        if (e < 3) t_p[e] += g;
-        else if (e < e_pe3) {
-            const int j = (e - 3) / 3, i = (e - 3) % 3;
-            const float f = ldexpf(s.freq_factor, j >> 1), a = i == 0 ? px : i == 1 ? py : pz;
-            t_p[i] += g * cosf(__builtin_fmaf(a, f, (j & 1) ? half_pi : 0.0f)) * f;
-        } else if (e == e_dir) t_p[3] += g;
-        else if (e > e_dir) {
-            const int j = e - e_pe1;
-            const float f = ldexpf(s.freq_factor, j >> 1);
-            t_p[3] += g * cosf(__builtin_fmaf(delta, f, (j & 1) ? half_pi : 0.0f)) * f;
-        }
-    }
-
-    // grid_sample's gradient with respect to the grid (ATen, align_corners=False; nearest: 0)
-    float gix = 0.f, giy = 0.f, mx = 0.f, my = 0.f;
-#ifdef DINER_TRAIN_GEN_BC
-    {   // bicubic: d/d ix = sum_ij dcx[i] cy[j] texel_ij, d/d iy = sum_ij cx[i] dcy[j] texel_ij; the padding acts on the integer tap
-        // positions and puts no factor on the gradient (zeros: a tap outside the map has weight and derivative 0)
-        const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-        int xi[4], yi[4];
-        float cx[4], cy[4], dcx[4], dcy[4];
-        bicubic_axis(unnorm(u * sxl, (float)s.w / 2.0f), s.w, ix_padding, xi, cx, dcx);
-        bicubic_axis(unnorm(w * syl, (float)s.h / 2.0f), s.h, ix_padding, yi, cy, dcy);
-        mx = ((float)s.w / 2.0f) * sxl;   // d ix / d u
-        my = ((float)s.h / 2.0f) * syl;
-        const float *lat = latent_nhwc + ((int64_t)sb * s.NV + v) * (int64_t)s.h * s.w * s.C;
-        const float *dz = d_zlat + row * s.C;
-        for (int ch = lane * 4; ch < s.C; ch += 256) {   // C % 4 == 0
-            const float4 g = *(const float4 *)(dz + ch);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float rx = 0.f, rd = 0.f;   // sum_i cx[i] <g, texel_ij>, sum_i dcx[i] <g, texel_ij>
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float4 t = *(const float4 *)(lat + ((int64_t)yi[j] * s.w + xi[i]) * s.C + ch);
-                    const float d = g.x * t.x + g.y * t.y + g.z * t.z + g.w * t.w;
-                    rx += cx[i] * d; rd += dcx[i] * d;
-                }
-                gix += cy[j] * rd; giy += dcy[j] * rx;
-            }
-        }
-    }
-#else
-    if (ix_interp == DINER_INDEX_BILINEAR) {
-        const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-        float gx, gy;
-        const float ix = pad_coord_grad(unnorm(u * sxl, (float)s.w / 2.0f), s.w, ix_padding, gx);
-        const float iy = pad_coord_grad(unnorm(w * syl, (float)s.h / 2.0f), s.h, ix_padding, gy);
-        mx = gx * ((float)s.w / 2.0f) * sxl;   // d ix / d u
-        my = gy * ((float)s.h / 2.0f) * syl;
-        const float x0f = floorf(ix), y0f = floorf(iy);
-        const float fx = ix - x0f, ex = 1.0f - fx, fy = iy - y0f, ey = 1.0f - fy;
-        const bool xa = x0f >= 0.0f && x0f <= (float)(s.w - 1), xb = x0f + 1.0f >= 0.0f && x0f + 1.0f <= (float)(s.w - 1);
-        const bool ya = y0f >= 0.0f && y0f <= (float)(s.h - 1), yb = y0f + 1.0f >= 0.0f && y0f + 1.0f <= (float)(s.h - 1);
-        const int x0 = safe_idx(x0f, s.w), x1 = safe_idx(x0f + 1.0f, s.w), y0 = safe_idx(y0f, s.h), y1 = safe_idx(y0f + 1.0f, s.h);
-        const float kx[4] = {(xa && ya) ? -ey : 0.f, (xb && ya) ? ey : 0.f, (xa && yb) ? -fy : 0.f, (xb && yb) ? fy : 0.f};
-        const float ky[4] = {(xa && ya) ? -ex : 0.f, (xb && ya) ? -fx : 0.f, (xa && yb) ? ex : 0.f, (xb && yb) ? fx : 0.f};
-        const bool inm[4] = {xa && ya, xb && ya, xa && yb, xb && yb};
-        const int o[4] = {y0 * s.w + x0, y0 * s.w + x1, y1 * s.w + x0, y1 * s.w + x1};
-        const float *lat = latent_nhwc + ((int64_t)sb * s.NV + v) * (int64_t)s.h * s.w * s.C;
-        const float *dz = d_zlat + row * s.C;
-        for (int ch = lane * 4; ch < s.C; ch += 256) {   // C % 4 == 0
-            const float4 g = *(const float4 *)(dz + ch);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (!inm[i]) continue;   // (wave-uniform)
-                const float4 t = *(const float4 *)(lat + (int64_t)o[i] * s.C + ch);
-                const float d = g.x * t.x + g.y * t.y + g.z * t.z + g.w * t.w;
-                gix += kx[i] * d; giy += ky[i] * d;
-            }
-        }
-    }
-#endif
-    const float S0 = wave_sum(t_p[0]), S1 = wave_sum(t_p[1]), S2 = wave_sum(t_p[2]), Sd = wave_sum(t_p[3]);
-    gix = wave_sum(gix); giy = wave_sum(giy);
-    if (lane != 0) return;
-
-    if (d_depths) atomicAdd(d_depths + (((int64_t)sb * s.NV + v) * s.H + ddy) * s.W + ddx, Sd);   // the nearest depth texel
-    float gpx = S0, gpy = S1, gpz = S2 - Sd;                 // depth_dist = depth - x_cam.z
-    const float qu = px / pz, qw = py / pz;
-    const float Uu = qu * vw.fx + vw.cx, Uw = qw * vw.fy + vw.cy;
-    const float gu = gix * mx, gw = giy * my;
-    const float gUu = gu * 2.0f / s.image_w, gUw = gw * 2.0f / s.image_h;
-    const float g_iw = -gu * 2.0f * Uu / (s.image_w * s.image_w), g_ih = -gw * 2.0f * Uw / (s.image_h * s.image_h);
-    const float gqu = gUu * vw.fx, gqw = gUw * vw.fy;
-    gpx += gqu / pz; gpy += gqw / pz; gpz -= (gqu * qu + gqw * qw) / pz;
-    // x_cam = R x_w + t, dir_cam = R d_w (pixelnerf.py:92-101), x_w = o + z d (nerf_renderer.py:304-305)
-    const float gp[3] = {gpx, gpy, gpz}, gd[3] = {gin[e_pe3], gin[e_pe3 + 1], gin[e_pe3 + 2]}, xw[3] = {wx, wy, wz}, dw[3] = {dwx, dwy, dwz};
-    float *out = rowg + row * CAMG_COLS;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float gx = vw.r[j] * gp[0] + vw.r[3 + j] * gp[1] + vw.r[6 + j] * gp[2];
-        const float gdd = vw.r[j] * gd[0] + vw.r[3 + j] * gd[1] + vw.r[6 + j] * gd[2];
-        out[j] = gx;                      // d_o
-        out[3 + j] = gdd + zz * gx;       // d_d
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) out[6 + i * 3 + j] = gp[i] * xw[j] + gd[i] * dw[j];
-        out[15 + i] = gp[i];
-    }
-    out[18] = gUu * qu; out[19] = gUw * qw;   // focal
-    out[20] = gUu; out[21] = gUw;             // c
-    out[22] = g_iw; out[23] = g_ih;           // image_shape
-}
-
-#ifdef DINER_TRAIN_GEN_BC
-#undef point_inputs_gen_kernel
-#undef point_inputs_bwd_gen_kernel
-#endif
-
-#ifndef DINER_TRAIN_GEN_BC
 // The fixed-order reductions of the per-row records (train.hip's camg_* kernels, the same sums in the same order)
 __global__ __launch_bounds__(256) void camg_ray_reduce_kernel(const float *__restrict__ rowg, int64_t NR, int K, int NV, int sb,
                                                               const float *__restrict__ d_far, float *__restrict__ d_rays)
@@ -557,75 +297,8 @@ __global__ __launch_bounds__(256) void camg_view_final_kernel(const float *__res
         }
     }
 }
-#else
-// d_lat_nhwc[v][texel (x[i], y[j])][ch] += dz[row][ch] * cx[i] * cy[j] over the 16 taps of each row's record (grid_sample's input
-// gradient; float atomics on 256-byte contiguous rows, as train.hip's bilinear_scatter_kernel).  One wave walks SCATTER_RUN consecutive
-// rows (consecutive samples of a ray in one view, whose footprints move by a fraction of a texel per sample): contributions are summed
-// in registers while the 4 columns and 4 rows stay the same and flushed with one atomic per tap when they change.  A tap of weight 0
-// (zeros padding outside the map) adds nothing and is never flushed.  Several taps of one footprint may be the same texel (border /
-// reflection at the rim, maps smaller than the footprint): the atomics add them up.
-constexpr int SCATTER_RUN = 16;
-__global__ __launch_bounds__(64) void bicubic_scatter_kernel(const float *__restrict__ dz, const float *__restrict__ taps, int64_t P, int C,
-                                                             int h, int w, int NV, int sb, float *__restrict__ dlatent_nhwc)
-{
-    const int64_t R = P * NV, row0 = (int64_t)blockIdx.x * SCATTER_RUN;
-    const int64_t row1 = row0 + SCATTER_RUN < R ? row0 + SCATTER_RUN : R;
-    const int lane = threadIdx.x;
-    for (int ch = lane; ch < C; ch += 64) {
-        int cur[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // x[4], y[4] of the open run
-        int64_t cur_v = -1;
-        float acc[16];
-        unsigned used = 0;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) acc[t] = 0.f;
-        for (int64_t row = row0; row <= row1; ++row) {
-            const bool last = row == row1;
-            const int64_t v = last ? -1 : row / P;
-            int o[8];
-            bool same = !last && v == cur_v;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                o[i] = last ? -1 : __float_as_int(taps[row * 16 + i]);
-                if (!last) { const int hi = (i < 4 ? w : h) - 1; o[i] = o[i] < 0 ? 0 : (o[i] > hi ? hi : o[i]); }   // never outside the map
-                same = same && o[i] == cur[i];
-            }
-            if (!same) {  // wave-uniform
-                if (cur_v >= 0 && used) {
-                    float *lat = dlatent_nhwc + ((int64_t)sb * NV + cur_v) * h * w * C + ch;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (used >> (j * 4 + i) & 1u) atomicAdd(lat + ((int64_t)cur[4 + j] * w + cur[i]) * C, acc[j * 4 + i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) cur[i] = o[i];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) acc[t] = 0.f;
-                used = 0;
-                cur_v = v;
-            }
-            if (last) break;
-            const float g = dz[row * C + ch];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float gy = g * taps[row * 16 + 12 + j];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float wx = taps[row * 16 + 8 + i];
-                    if (wx != 0.0f && taps[row * 16 + 12 + j] != 0.0f) { acc[j * 4 + i] += gy * wx; used |= 1u << (j * 4 + i); }
-                }
-            }
-        }
-    }
-}
-#endif  // DINER_TRAIN_GEN_BC
 
 }  // namespace train_gen
-
-#ifndef DINER_TRAIN_GEN_BC
-int launch_train_camg_reduce(const float *, float *, int64_t, int, int, int, const float *, float *, float *, float *, float *, float *,
-                             hipStream_t);
 
 int launch_train_gemm_act(const float *A, const float *B, const float *bias, const float *S, float *C, int64_t M, int N, int K, int64_t sam,
                           int64_t sak, int64_t sbk, int64_t sbn, int64_t ldc, int64_t lds, int act_a, int act_b, int act_s, float beta,
@@ -649,9 +322,9 @@ int launch_train_point_inputs_gen(const DinerScene &s, const DinerLatentIndex &i
 {
     const int64_t R = NR * (int64_t)K * s.NV;
     if (R == 0) return DINER_OK;
-    hipLaunchKernelGGL(train_gen::point_inputs_gen_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp,
+    hipLaunchKernelGGL(train_gen::point_inputs_gen_kernel<false>, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp,
                        ix.padding, in, ld_in, zlat, taps);
-    return check_launch("train_gen::point_inputs_gen_kernel");
+    return check_launch("train_gen::point_inputs_gen_kernel<false>");
 }
 
 int launch_train_point_inputs_bwd_gen(const DinerScene &s, const DinerLatentIndex &ix, const float *latent_nhwc, const float *rays,
@@ -663,15 +336,14 @@ int launch_train_point_inputs_bwd_gen(const DinerScene &s, const DinerLatentInde
     const int64_t P = NR * (int64_t)K, R = P * s.NV;
     if (R == 0) return DINER_OK;
     float *rowg = workspace, *partial = workspace + R * CAMG_COLS;   // diner_train_camera_workspace_floats' layout
-    hipLaunchKernelGGL(point_inputs_bwd_gen_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp,
+    hipLaunchKernelGGL(point_inputs_bwd_gen_kernel<false>, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp,
                        ix.padding, d_in, ld_in, d_zlat, rowg, d_depths);
-    int rc = check_launch("train_gen::point_inputs_bwd_gen_kernel");
+    int rc = check_launch("train_gen::point_inputs_bwd_gen_kernel<false>");
     if (rc) return rc;
     return launch_train_camg_reduce(rowg, partial, NR, K, s.NV, sb, d_far, d_rays, d_poses, d_focal, d_c, d_image_shape, st);
 }
 
-// the fixed-order reductions of the rowg records [R, CAMG_COLS] to the rays and the per-view camera gradients (also behind
-// train_gen_bc.hip's backward)
+// (also behind train_gen_bc.hip's backward)
 int launch_train_camg_reduce(const float *rowg, float *partial, int64_t NR, int K, int NV, int sb, const float *d_far, float *d_rays,
                              float *d_poses, float *d_focal, float *d_c, float *d_image_shape, hipStream_t st)
 {
@@ -692,45 +364,5 @@ int launch_train_camg_reduce(const float *rowg, float *partial, int64_t NR, int 
     }
     return DINER_OK;
 }
-#else   // DINER_TRAIN_GEN_BC
-int launch_train_camg_reduce(const float *, float *, int64_t, int, int, int, const float *, float *, float *, float *, float *, float *,
-                             hipStream_t);   // train_gen.hip
-
-int launch_train_point_inputs_gen_bc(const DinerScene &s, int padding, const float *latent_nhwc, const float *rays, const float *z, int64_t NR,
-                                     int K, int sb, float *in, int64_t ld_in, float *zlat, float *taps, hipStream_t st)
-{
-    const int64_t R = NR * (int64_t)K * s.NV;
-    if (R == 0) return DINER_OK;
-    hipLaunchKernelGGL(train_gen::point_inputs_gen_bc_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, 0, padding,
-                       in, ld_in, zlat, taps);
-    return check_launch("train_gen::point_inputs_gen_bc_kernel");
-}
-
-int launch_train_point_inputs_bwd_gen_bc(const DinerScene &s, int padding, const float *latent_nhwc, const float *rays, const float *z,
-                                         int64_t NR, int K, int sb, const float *d_in, int64_t ld_in, const float *d_zlat, const float *d_far,
-                                         float *workspace, float *d_rays, float *d_poses, float *d_focal, float *d_c, float *d_image_shape,
-                                         float *d_depths, hipStream_t st)
-{
-    using namespace train_gen;
-    const int64_t P = NR * (int64_t)K, R = P * s.NV;
-    if (R == 0) return DINER_OK;
-    float *rowg = workspace, *partial = workspace + R * CAMG_COLS;   // diner_train_camera_workspace_floats' layout
-    hipLaunchKernelGGL(point_inputs_bwd_gen_bc_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, 0, padding, d_in,
-                       ld_in, d_zlat, rowg, d_depths);
-    const int rc = check_launch("train_gen::point_inputs_bwd_gen_bc_kernel");
-    if (rc) return rc;
-    return launch_train_camg_reduce(rowg, partial, NR, K, s.NV, sb, d_far, d_rays, d_poses, d_focal, d_c, d_image_shape, st);
-}
-
-int launch_train_bicubic_scatter(const float *dz, const float *taps, int64_t P, int C, int h, int w, int NV, int sb, float *dlatent_nhwc,
-                                 hipStream_t st)
-{
-    using namespace train_gen;
-    if (P * NV == 0) return DINER_OK;
-    hipLaunchKernelGGL(bicubic_scatter_kernel, dim3((unsigned)((P * NV + SCATTER_RUN - 1) / SCATTER_RUN)), dim3(64), 0, st, dz, taps, P, C, h, w, NV,
-                       sb, dlatent_nhwc);
-    return check_launch("train_gen::bicubic_scatter_kernel");
-}
-#endif  // DINER_TRAIN_GEN_BC
 
 }  // namespace diner

@@ -29,7 +29,7 @@ def test_no_flat_instructions(isa):
 
 
 def test_three_instantiations_on_fp32_mfma(isa):
-    names = set(re.findall(r"^(_ZN5diner3gen21points_mlp_gen_kernelILi(\d)ELi(\d)EE\S*):", isa, re.M))
+    names = set(re.findall(r"^(_ZN5diner3gen21points_mlp_gen_kernelINS0_7DefaultELi(\d)ELi(\d)EE\S*):", isa, re.M))
     assert {(rb, ct) for _, rb, ct in names} == {("1", "1"), ("2", "1"), ("2", "2")}
     for name, _, _ in names:
         body = isa[isa.index(name + ":"):]

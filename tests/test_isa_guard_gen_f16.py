@@ -12,7 +12,9 @@ import pytest
 ROOT = Path(__file__).resolve().parents[1]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CSRC = ROOT / "diner_amd" / "csrc"
-UNITS = {"points_mlp_gen_f16": "points_mlp_gen_f16_kernel", "points_mlp_gen_f16_ix": "points_mlp_gen_f16_ix_kernel"}
+# unit -> its instantiations of the kernel template (points_mlp_gen_f16_kernel.hpp): the mangled kernel name with the mode
+KERNEL = "points_mlp_gen_f16_kernel"
+UNITS = {"points_mlp_gen_f16": f"{KERNEL}INS0_7DefaultE", "points_mlp_gen_f16_ix": f"{KERNEL}INS0_2IxE"}
 
 
 @pytest.fixture(scope="module", params=sorted(UNITS))
@@ -33,7 +35,7 @@ def test_no_flat_instructions(unit):
 
 def test_three_instantiations_on_fp16_mfma(unit):
     kernel, isa = unit
-    names = set(re.findall(rf"^(_ZN5diner6genf16\d+{kernel}ILi(\d)ELi(\d)EE\S*):", isa, re.M))
+    names = set(re.findall(rf"^(_ZN5diner6genf16\d+{kernel}Li(\d)ELi(\d)EE\S*):", isa, re.M))
     assert {(rb, ct) for _, rb, ct in names} == {("1", "1"), ("2", "1"), ("2", "2")}
     for name, _, _ in names:
         body = isa[isa.index(name + ":"):]

@@ -12,9 +12,10 @@ import pytest
 ROOT = Path(__file__).resolve().parents[1]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CSRC = ROOT / "diner_amd" / "csrc"
-UNITS = {"points_mlp_gen_lz": "points_mlp_gen_lz_kernel", "points_mlp_gen_lz_bc": "points_mlp_gen_lz_bc_kernel",
-         "points_mlp_gen_f16_lz": "points_mlp_gen_f16_lz_kernel", "points_mlp_gen_f16_lz_bc": "points_mlp_gen_f16_lz_bc_kernel",
-         "linz_maps_gen": "linz_maps_gen_kernel"}
+# unit -> the mangled kernel name up to its <RB, CT>: the template's name and, for the point/MLP kernels, the mode
+UNITS = {"points_mlp_gen_lz": "points_mlp_gen_kernelINS0_2LzE", "points_mlp_gen_lz_bc": "points_mlp_gen_kernelINS0_4LzBcE",
+         "points_mlp_gen_f16_lz": "points_mlp_gen_f16_kernelINS0_2LzE", "points_mlp_gen_f16_lz_bc": "points_mlp_gen_f16_kernelINS0_4LzBcE",
+         "linz_maps_gen": "linz_maps_gen_kernelI"}
 
 
 @pytest.fixture(scope="module", params=sorted(UNITS))
@@ -29,6 +30,6 @@ def unit(request, tmp_path_factory):
 
 def test_no_flat_instructions(unit):
     kernel, isa = unit
-    assert len(set(re.findall(rf"^(_ZN5diner\w*?\d+{kernel}ILi\dELi\dEE\S*):", isa, re.M))) == 3, "the three <RB, CT> instantiations"
+    assert len(set(re.findall(rf"^(_ZN5diner\w*?\d+{kernel}Li\dELi\dEE\S*):", isa, re.M))) == 3, "the three <RB, CT> instantiations"
     flat = re.findall(r"^\s+(flat_\w+)", isa, re.M)
     assert not flat, sorted(set(flat))
