@@ -18,12 +18,13 @@
 //   gemm_panel_kernel  forward / dX in f16x3 arithmetic with the weight pre-split into fp16 planes
 // plus small per-point kernels (inputs/bilinear gather, view mean, head, compositing backward, bilinear
 // scatter-add, bias-gradient + max|.| reduction).  Measured rates: DESIGN.md section 4.4.
-#include "common.hpp"
+// The device helpers these GEMMs share with the shape-general units (tile loads, block -> tile map, hi/lo split, scale, epilogue) are
+// train_blocks.hpp's; the fixed-order reductions of the camera-gradient records are train_gen.hip's (launch_train_camg_reduce).
+#include "train_blocks.hpp"
 
 namespace diner {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace train_blocks;
 
 namespace train {
 
@@ -45,32 +46,7 @@ struct GemmArgs {
     int exp_a, exp_b;
 };
 
-// One operand tile (128 x 16, as [k][m]) = 512 float4, two per thread.  KC: the operand is contiguous along the
-// contraction index (float4 along k, transposed into the tile), else along the tile's long index.
-// Loads are unconditional (out-of-range pieces read a clamped in-range address and are zeroed by `ok` when the
-// tile is stored): a load under a branch makes hipcc wait for each one separately.
-template <bool KC>
-__device__ __forceinline__ unsigned tile_load(f32x4 (&v)[2], const float *__restrict__ base, int64_t s_long, int64_t s_k, int64_t l0,
-                                              int64_t l_end, int64_t k0, int64_t k_end, int tid)
-{
-    unsigned ok = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = tid + 256 * i;
-        if (KC) {
-            const int64_t l = l0 + (idx >> 2), k = k0 + (idx & 3) * 4;
-            const bool in = l < l_end && k < k_end;
-            ok |= (unsigned)in << i;
-            v[i] = *(const f32x4 *)(base + (l < l_end ? l : l_end - 1) * s_long + (k < k_end ? k : k_end - 4));
-        } else {
-            const int64_t k = k0 + (idx >> 5), l = l0 + (idx & 31) * 4;
-            const bool in = k < k_end && l < l_end;
-            ok |= (unsigned)in << i;
-            v[i] = *(const f32x4 *)(base + (k < k_end ? k : k_end - 1) * s_k + (l < l_end ? l : l_end - 4));
-        }
-    }
-    return ok;
-}
+// The fp32 operand tile (128 x 16, as [k][m]): tile_load<KC> of train_blocks.hpp brings it in, this stores it.
 template <bool KC>
 __device__ __forceinline__ void tile_store(float (*T)[LDT], const f32x4 (&v)[2], unsigned ok, int relu, int tid)
 {
@@ -91,75 +67,6 @@ __device__ __forceinline__ void tile_store(float (*T)[LDT], const f32x4 (&v)[2],
     }
 }
 
-// Block -> output tile.  Workgroups are dealt round-robin to the 8 XCDs (id % 8), each with its own L2: the
-// column blocks of one 128-row tile (they all read the same A tile, the big streamed operand) are given to
-// consecutive workgroups of ONE XCD, so A leaves HBM once instead of once per column block.
-__device__ __forceinline__ void tile_of(const GemmArgs &g, int64_t &m0, int &n0, int64_t lin = -1)
-{
-    const int64_t gm = (g.M + BM - 1) / BM;
-    if (lin < 0) lin = blockIdx.x;
-    const int gn = (g.N + BN - 1) / BN;
-    const int64_t full = gm / 8 * 8;
-    int64_t mt, nb;
-    if (lin < full * gn) { const int64_t j = lin / 8; nb = j % gn; mt = j / gn * 8 + lin % 8; }
-    else { const int64_t r = lin - full * gn; mt = full + r / gn; nb = r % gn; }
-    m0 = mt * BM;
-    n0 = (int)nb * BN;
-}
-
-// LDS slot of tile row l for an operand staged by the f16x3 kernel's transposing store (f16g::tile_store<false>): the 4 x 4 index
-// transpose inside every 16-row block (an involution), which makes that store conflict-free; the accumulator rows / columns
-// come out in slot order and are mapped back here.
-__device__ __forceinline__ int slot16(int x) { return (x & ~15) | ((x & 3) << 2) | ((x >> 2) & 3); }
-
-// C layout of the 32x32 MFMA accumulators: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
-// PA / PB: the A / B operand tile was staged in slot order (rows / columns of the tile permuted by slot16)
-template <bool PA = false, bool PB = false>
-__device__ __forceinline__ void epilogue(const GemmArgs &g, const f32x16 (&acc)[2][2], int64_t m0, int n0, int wm, int wn, int lane,
-                                         float unscale)
-{
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb) {
-        const int nc = wn + tb * 32 + (lane & 31), n = n0 + (PB ? slot16(nc) : nc);
-        if (n >= g.N) continue;
-        const float bias = (g.bias && blockIdx.z == 0) ? g.bias[n] : 0.0f;
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta) {
-            // all 16 reads of the tile (old C, mask) are issued before the first dependent store: one memory
-            // round trip per tile instead of one per element
-            const int mbl = wm + ta * 32 + 4 * (lane >> 5);
-            auto row_of = [&](int i) -> int64_t { const int r = mbl + (i & 3) + 8 * (i >> 2); return m0 + (PA ? slot16(r) : r); };
-            float old[16], msk[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { old[i] = 0.0f; msk[i] = 1.0f; }
-            if (g.accumulate && !g.atomic) {  // uniform branches, unconditional loads from clamped rows
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t m = row_of(i);
-                    old[i] = g.C[(m < g.M ? m : g.M - 1) * g.ldc + n];
-                }
-            }
-            if (g.S) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t m = row_of(i);
-                    msk[i] = g.S[(m < g.M ? m : g.M - 1) * g.lds_ + n];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int64_t m = row_of(i);
-                if (m >= g.M) continue;
-                float v = acc[ta][tb][i] * unscale + bias;
-                v = msk[i] > 0.0f ? v : 0.0f;
-                float *c = g.C + m * g.ldc + n;
-                if (g.atomic) atomicAdd(c, v);
-                else *c = old[i] + v;
-            }
-        }
-    }
-}
-
 // AK: A contiguous along k (sak == 1) else along m (sam == 1).  BNC: B contiguous along n (sbn == 1) else along k.
 // 4 waves as 2 x 2, each a 64 x 64 output (2 x 2 MFMA tiles); global loads of tile t+1 are in flight while tile t
 // is multiplied out of LDS (double-buffered, one barrier per k-step).
@@ -170,7 +77,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int64_t m0;
     int n0;
-    tile_of(g, m0, n0);
+    tile_of(g.M, g.N, BM, BN, blockIdx.x, m0, n0);
     const int64_t kbeg = (int64_t)blockIdx.z * g.k_chunk;
     const int64_t kend = kbeg + g.k_chunk < g.K ? kbeg + g.k_chunk : g.K;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -211,7 +118,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g)
         __syncthreads();
         buf ^= 1;
     }
-    epilogue(g, acc, m0, n0, wm, wn, lane, 1.0f);
+    epilogue<false, false>(g, acc, m0, n0, wm, wn, lane, blockIdx.z, 1.0f, [](float v, float s) { return s > 0.0f ? v : 0.0f; });
 }
 
 // ---- the same GEMM with fp32-grade fp16 arithmetic (precision "f16x3", the renderer's default) --------------------
@@ -221,94 +128,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g)
 // An image holds 16-byte units (u = k/8, row) at u*128 + (row ^ 4u): an MFMA fragment (8 consecutive k of one
 // row) is one conflict-free ds_read_b128.
 namespace f16g {
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 constexpr int BKH = 32, UNITS_T = (BKH / 8) * 128;
 
-__device__ __forceinline__ int unit(int u, int row) { return u * 128 + (row ^ (4 * u)); }
-
-__device__ __forceinline__ void scale_of(const unsigned int *amax, int static_exp, float &s, float &inv)
-{
-    int e = static_exp;
-    if (amax) {
-        const unsigned int b = *amax;
-        const int ex = (int)((b >> 23) & 0xffu) - 127;
-        e = (b == 0u) ? 0 : 13 - ex;
-    }
-    e = e < -100 ? -100 : e > 100 ? 100 : e;
-    s = __uint_as_float((unsigned int)(127 + e) << 23);
-    inv = __uint_as_float((unsigned int)(127 - e) << 23);
-}
-
-// One operand tile = 128 (long index l) x 32 (k) fp32 = 1024 float4, four per thread.
-// KC (contiguous along k): float4 along k.  else: a 4(k) x 4(l) micro-tile per thread, float4 along l.
 template <bool KC>
-__device__ __forceinline__ unsigned tile_load(f32x4 (&v)[4], const float *__restrict__ base, int64_t s_long, int64_t s_k, int64_t l0,
-                                              int64_t l_end, int64_t k0, int64_t k_end, int tid)
-{
-    unsigned ok = 0;  // unconditional loads from clamped addresses + a validity bit per piece (see train::tile_load)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (KC) {
-            const int idx = tid + 256 * i;
-            const int64_t l = l0 + (idx >> 3), k = k0 + (idx & 7) * 4;
-            ok |= (unsigned)(l < l_end && k < k_end) << i;
-            v[i] = *(const f32x4 *)(base + (l < l_end ? l : l_end - 1) * s_long + (k < k_end ? k : k_end - 4));
-        } else {
-            // thread = (k-quad kq4 of 8, l-quad lq4 of 32); a 16-lane group = 4 k-quads x 4 consecutive l-quads (see tile_store)
-            const int kq4 = (tid & 3) | ((tid >> 4) & 4), lq4 = ((tid >> 2) & 15) | ((tid >> 3) & 16);
-            const int64_t k = k0 + kq4 * 4 + i, l = l0 + lq4 * 4;
-            ok |= (unsigned)(k < k_end && l < l_end) << i;
-            v[i] = *(const f32x4 *)(base + (k < k_end ? k : k_end - 1) * s_k + (l < l_end ? l : l_end - 4));
-        }
-    }
-    return ok;
-}
-
-// (x * sc, floored) -> fp16 hi / lo pairs: hi = cvt_pk(t), lo = fma_mix(hi * -1 + t) rounded once to fp16 = (f16)(t - (float)hi) (the
-// difference is exact in fp32).  2.5 VALU slots per value (4.5 with the relu) where the C++ form costs hipcc about 8: scalar converts
-// both ways, v_pack; in the dW kernel that split, not the MFMAs, was the longest phase of a k-step.
-// RELU keeps NaN like torch.relu: v_cmp_ngt + v_cndmask, the 4 compares ahead of the 4 selects (gfx950: 2 wait states between a VALU
-// write of an SGPR and its VALU read).
-template <bool RELU>
-__device__ __forceinline__ void split4_pk(float x0, float x1, float x2, float x3, float sc, unsigned &h01, unsigned &h23, unsigned &l01, unsigned &l23)
-{
-    float t0, t1, t2, t3;
-    if constexpr (RELU) {
-        unsigned long long m0, m1, m2, m3;
-        asm volatile("v_mul_f32 %4, %12, %16\n\tv_mul_f32 %5, %13, %16\n\tv_mul_f32 %6, %14, %16\n\tv_mul_f32 %7, %15, %16\n\t"
-                     "v_cmp_ngt_f32_e64 %8, 0, %4\n\tv_cmp_ngt_f32_e64 %9, 0, %5\n\tv_cmp_ngt_f32_e64 %10, 0, %6\n\tv_cmp_ngt_f32_e64 %11, 0, %7\n\t"
-                     "v_cndmask_b32_e64 %4, 0, %4, %8\n\tv_cndmask_b32_e64 %5, 0, %5, %9\n\tv_cndmask_b32_e64 %6, 0, %6, %10\n\tv_cndmask_b32_e64 %7, 0, %7, %11\n\t"
-                     "v_cvt_pk_f16_f32 %0, %4, %5\n\tv_cvt_pk_f16_f32 %1, %6, %7\n\t"
-                     "v_fma_mixlo_f16 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mixlo_f16 %3, %1, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-                     "v_fma_mixhi_f16 %2, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %3, %1, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                     : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3)
-                     : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(sc));
-    } else {
-        asm volatile("v_mul_f32 %4, %8, %12\n\tv_mul_f32 %5, %9, %12\n\tv_mul_f32 %6, %10, %12\n\tv_mul_f32 %7, %11, %12\n\t"
-                     "v_cvt_pk_f16_f32 %0, %4, %5\n\tv_cvt_pk_f16_f32 %1, %6, %7\n\t"
-                     "v_fma_mixlo_f16 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mixlo_f16 %3, %1, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-                     "v_fma_mixhi_f16 %2, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %3, %1, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                     : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-                     : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(sc));
-    }
-}
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void put4(h8 *Thi, h8 *Tlo, int l, int kq, float x0, float x1, float x2, float x3, float floor_, float sc)
-{
-    u32x2 hi, lo;   // floor_ = 0 applies the relu, -inf does nothing (wave-uniform); NaN stays NaN
-    unsigned a, b, c, d;
-    if (floor_ == 0.0f) split4_pk<true>(x0, x1, x2, x3, sc, a, b, c, d);
-    else split4_pk<false>(x0, x1, x2, x3, sc, a, b, c, d);
-    hi.x = a; hi.y = b; lo.x = c; lo.y = d;
-    const int o = unit(kq >> 3, l) * 8 + (kq & 4);
-    *(u32x2 *)((_Float16 *)Thi + o) = hi;
-    *(u32x2 *)((_Float16 *)Tlo + o) = lo;
-}
-
-template <bool KC>
-__device__ __forceinline__ void tile_store(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4], unsigned ok, float floor_, float sc, int tid)
+__device__ __forceinline__ void tile_store(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4], unsigned ok, bool relu, float sc, int tid)
 {
     f32x4 x[4];
 #pragma unroll
@@ -323,7 +146,7 @@ __device__ __forceinline__ void tile_store(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4]
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + 256 * i;
-            put4(Thi, Tlo, idx >> 3, (idx & 7) * 4, x[i][0], x[i][1], x[i][2], x[i][3], floor_, sc);
+            put4(Thi, Tlo, idx >> 3, (idx & 7) * 4, x[i][0], x[i][1], x[i][2], x[i][3], relu, sc);
         }
     } else {
         // The thread holds 4 (k) x 4 (l); row l + c goes to LDS slot slot16(l + c) = (l & ~15) | 4c | (lq4 & 3).  ds_write_b64 is
@@ -333,7 +156,7 @@ __device__ __forceinline__ void tile_store(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4]
         const int kq4 = (tid & 3) | ((tid >> 4) & 4), lq4 = ((tid >> 2) & 15) | ((tid >> 3) & 16);
         const int kq = kq4 * 4, sl = ((lq4 * 4) & ~15) | (lq4 & 3);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) put4(Thi, Tlo, sl + 4 * c, kq, x[0][c], x[1][c], x[2][c], x[3][c], floor_, sc);
+        for (int c = 0; c < 4; ++c) put4(Thi, Tlo, sl + 4 * c, kq, x[0][c], x[1][c], x[2][c], x[3][c], relu, sc);
     }
 }
 
@@ -358,14 +181,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmArgs g)
         bz = (j / gridDim.x) * 8 + xcd;
         bx = j % gridDim.x;
     }
-    tile_of(g, m0, n0, bx);
+    tile_of(g.M, g.N, BM, BN, bx, m0, n0);
     const int64_t kbeg = bz * g.k_chunk;
     const int64_t kend = kbeg + g.k_chunk < g.K ? kbeg + g.k_chunk : g.K;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     float sa, ia, sb, ib;
     scale_of(g.amax_a, g.exp_a, sa, ia);
     scale_of(g.amax_b, g.exp_b, sb, ib);
-    const float fa = g.relu_a ? 0.0f : -__builtin_inff(), fb = g.relu_b ? 0.0f : -__builtin_inff();
+    const bool fa = g.relu_a, fb = g.relu_b;   // the operands' relu flags (wave-uniform)
     f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -429,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmArgs g)
         DINER_GEMM_STEP(1)
     }
 #undef DINER_GEMM_STEP
-    epilogue<!AK, BNC>(g, acc, m0, n0, wm, wn, lane, ia * ib);
+    epilogue<!AK, BNC>(g, acc, m0, n0, wm, wn, lane, blockIdx.z, ia * ib, [](float v, float s) { return s > 0.0f ? v : 0.0f; });
 }
 
 // ---- the weight-gradient GEMM of a 512 x 512 layer: dW[i][j] += sum_m dY[m][i] * relu?(X[m][j])  (reference: autograd of nn.Linear in
@@ -444,9 +267,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(GemmArgs g)
 // The 4 tiles of a row chunk run on ONE XCD (they read the same two operand slices: one HBM fetch, three L2 hits).
 // (Tried the generic split-K kernel for these gradients too: measured 1.54 ms against 1.056 ms, not kept.)
 namespace dw512 {
-using f16g::h8;
-using f16g::put4;
-using f16g::scale_of;
 constexpr int TM = 256, KS = 32, NT = 512;
 constexpr int PLANE = (KS / 8) * TM;                   // 16-byte units of one fp16 plane of one operand: 1024 = 16 KiB
 constexpr int LDS_BYTES = 2 * 4 * PLANE * 16;          // [2 buffers][A hi, A lo, B hi, B lo] = 128 KiB
@@ -500,13 +320,13 @@ __device__ __forceinline__ void store_tile(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4]
     _Float16 *ph = (_Float16 *)Thi + unit(kq >> 3, sl) * 8 + (kq & 4), *pl = (_Float16 *)Tlo + unit(kq >> 3, sl) * 8 + (kq & 4);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {   // slots sl + 4c: sl's bits 2, 3 are clear, and the unit's swizzle (row ^ 4u) only touches those: + 4c units... see below
-        f16g::u32x2 hi, lo;
+        u32x2 hi, lo;
         unsigned a, b, cc, d;
-        f16g::split4_pk<RELU>(x[0][c], x[1][c], x[2][c], x[3][c], sc, a, b, cc, d);
+        split4_pk<RELU>(x[0][c], x[1][c], x[2][c], x[3][c], sc, a, b, cc, d);
         hi.x = a; hi.y = b; lo.x = cc; lo.y = d;
         const int o = unit(kq >> 3, sl + 4 * c) * 8 + (kq & 4);
-        *(f16g::u32x2 *)((_Float16 *)Thi + o) = hi;
-        *(f16g::u32x2 *)((_Float16 *)Tlo + o) = lo;
+        *(u32x2 *)((_Float16 *)Thi + o) = hi;
+        *(u32x2 *)((_Float16 *)Tlo + o) = lo;
     }
     (void)ph; (void)pl;
 }
@@ -684,8 +504,6 @@ __global__ __launch_bounds__(256) void colsum_amax_kernel(const float *__restric
 // workgroups of a row panel sit on one XCD (one HBM read of A).  8 waves as 2 x 4, 64 x 64 outputs each, k-steps
 // of 32, LDS double-buffered; A is staged two steps ahead (HBM), the weights one step ahead (L2).
 namespace panel {
-using f16g::h4;
-using f16g::h8;
 constexpr int PM = 128, PNW = 256, PN = 512, PK = 32;
 constexpr int A_UNITS = (PK / 8) * PM, B_UNITS = (PK / 8) * PNW;  // 16-byte units (u = k/8, row) per image and stage
 constexpr int STAGE_UNITS = 2 * A_UNITS + 2 * B_UNITS;            // 48 KiB
@@ -742,15 +560,15 @@ __device__ __forceinline__ void store_a(h8 *T, const StageA &st, float floor_, f
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int idx = tid + 512 * i, row = idx >> 3, kq = (idx & 7) * 4;
-        f16g::u32x2 hi, lo;
+        u32x2 hi, lo;
         unsigned a, b, c, d;
-        if (floor_ == 0.0f) f16g::split4_pk<true>(st.a[i][0], st.a[i][1], st.a[i][2], st.a[i][3], sc, a, b, c, d);
-        else f16g::split4_pk<false>(st.a[i][0], st.a[i][1], st.a[i][2], st.a[i][3], sc, a, b, c, d);
+        if (floor_ == 0.0f) split4_pk<true>(st.a[i][0], st.a[i][1], st.a[i][2], st.a[i][3], sc, a, b, c, d);
+        else split4_pk<false>(st.a[i][0], st.a[i][1], st.a[i][2], st.a[i][3], sc, a, b, c, d);
         if (!((st.ok >> i) & 1u)) a = b = c = d = 0u;       // (a piece past the edge was loaded from a clamped, valid address)
         hi.x = a; hi.y = b; lo.x = c; lo.y = d;
         const int o = unit(kq >> 3, row, PM) * 8 + (kq & 4);
-        *(f16g::u32x2 *)((_Float16 *)Ahi + o) = hi;
-        *(f16g::u32x2 *)((_Float16 *)Alo + o) = lo;
+        *(u32x2 *)((_Float16 *)Ahi + o) = hi;
+        *(u32x2 *)((_Float16 *)Alo + o) = lo;
     }
 }
 __device__ __forceinline__ void store_b(h8 *T, const StageB &st, int tid)
@@ -781,8 +599,8 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(PanelArgs g)
     }
     const int wm = (wave >> 2) * 64, wn = (wave & 3) * 64;
     float sa, ia, sb, ib;
-    f16g::scale_of(g.amax_a, g.exp_a, sa, ia);
-    f16g::scale_of(nullptr, g.exp_b, sb, ib);
+    scale_of(g.amax_a, g.exp_a, sa, ia);
+    scale_of(nullptr, g.exp_b, sb, ib);
     const float fa = g.relu_a ? 0.0f : -__builtin_inff();
     f32x16 acc[2][2];
 #pragma unroll
@@ -893,7 +711,7 @@ __global__ void split_panel_kernel(const float *__restrict__ W, int K, int64_t l
     if (i >= (int64_t)PN * kpad) return;
     const int kk = (int)(i % PK), n = (int)((i / PK) % PN), ks = (int)(i / (PK * PN)), k = ks * PK + kk;
     float sc, inv;
-    f16g::scale_of(nullptr, exp_, sc, inv);
+    scale_of(nullptr, exp_, sc, inv);
     const float v = k < K ? (transpose ? W[(int64_t)k * ld + n] : W[(int64_t)n * ld + k]) * sc : 0.0f;
     const _Float16 hv = (_Float16)v;
     hi[i] = hv;
@@ -1041,7 +859,6 @@ __global__ __launch_bounds__(64) void point_inputs_kernel(DinerScene s, const fl
 // fraction of a texel per sample): contributions are summed in registers while the four texel indices stay the same
 // and flushed with one atomic per tap when they change -- float atomics run at a fixed memory-side rate (~1.3 TB/s of
 // added bytes), so fewer of them is the only lever.
-constexpr int SCATTER_RUN = 16;
 __global__ __launch_bounds__(64) void bilinear_scatter_kernel(const float *__restrict__ dz, const float *__restrict__ taps,
                                                               int64_t P, int C, int h, int w, int NV, int sb,
                                                               float *__restrict__ dlatent_nhwc)
@@ -1092,30 +909,7 @@ __global__ __launch_bounds__(64) void bilinear_scatter_kernel(const float *__res
 //   uv = ((x_cam.xy / x_cam.z) f + c) / image_shape * 2 - 1,  depth_dist = depth[nearest(uv)] - x_cam.z,  zlat = grid_sample(latent, uv).
 // Writes one record of CAMG_COLS floats per row (the reductions below sum them in a fixed order) and scatters d_depth_dist into
 // d_depths [SB,NV,H,W] (float atomics, as bilinear_scatter_kernel: several rows share a texel).
-constexpr int CAMG_COLS = 24;   // d_o 3, d_d 3, d_R 9 (row-major), d_t 3, d_focal 2, d_c 2, d_image_shape 2
-constexpr int CAMG_BLOCKS = 256;   // per-view partial sums of the pose / intrinsics reduction (at most)
-
-// ATen's clip_coordinates_set_grad + reflect_coordinates_set_grad (align_corners=False): the source coordinate of one axis after the
-// padding mode, and the factor its gradient picks up on the way back (border: 0 where clipped; reflection: the sign flips)
-__device__ __forceinline__ float pad_coord_grad(float x, int size, int padding, float &g)
-{
-    g = 1.0f;
-    if (padding == DINER_INDEX_PAD_REFLECTION) {
-        float in = x + 0.5f;                  // reflect over [-0.5, size - 0.5]
-        float m = 1.0f;
-        if (in < 0.0f) { m = -1.0f; in = -in; }
-        const float span = (float)size, extra = fmodf(in, span);
-        const int flips = (int)floorf(in / span);
-        if (flips % 2 == 0) { g = m; x = extra - 0.5f; }
-        else { g = -m; x = span - extra - 0.5f; }
-    }
-    if (padding != DINER_INDEX_PAD_ZEROS) {
-        if (x <= 0.0f || x >= (float)(size - 1)) g = 0.0f;
-        x = clipf(x, (float)(size - 1));
-    }
-    return x;
-}
-
+// (CAMG_COLS, the record's columns, and pad_coord_grad: train_blocks.hpp)
 __global__ __launch_bounds__(64) void point_inputs_bwd_kernel(DinerScene s, const float *__restrict__ latent_nhwc,
                                                               const float *__restrict__ rays, const float *__restrict__ zsamp,
                                                               int64_t NR, int K, int sb, int ix_interp, int ix_padding,
@@ -1224,81 +1018,6 @@ __global__ __launch_bounds__(64) void point_inputs_bwd_kernel(DinerScene s, cons
     out[18] = gUu * qu; out[19] = gUw * qw;   // focal
     out[20] = gUu; out[21] = gUw;             // c
     out[22] = g_iw; out[23] = g_ih;           // image_shape
-}
-
-// d_rays[sb][ray] = (sum over views and samples of d_o, d_d;  0 (near: sampler only);  d_far or 0) -- one thread per ray, fixed order
-__global__ __launch_bounds__(256) void camg_ray_reduce_kernel(const float *__restrict__ rowg, int64_t NR, int K, int NV, int sb,
-                                                              const float *__restrict__ d_far, float *__restrict__ d_rays)
-{
-    const int64_t ray = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ray >= NR) return;
-    const int64_t P = NR * K;
-    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int v = 0; v < NV; ++v)
-        for (int k = 0; k < K; ++k) {
-            const float *g = rowg + ((int64_t)v * P + ray * K + k) * CAMG_COLS;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) acc[c] += g[c];
-        }
-    float *o = d_rays + ((int64_t)sb * NR + ray) * 8;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) o[c] = acc[c];
-    o[6] = 0.0f;
-    o[7] = d_far ? d_far[(int64_t)sb * NR + ray] : 0.0f;
-}
-
-// per-view partial sums of the camera columns (6..23) over a contiguous chunk of the view's P rows: grid (blocks, NV)
-__global__ __launch_bounds__(256) void camg_view_partial_kernel(const float *__restrict__ rowg, int64_t P, float *__restrict__ partial)
-{
-    constexpr int NC = CAMG_COLS - 6;
-    __shared__ float red[NC][256];
-    const int v = blockIdx.y, t = threadIdx.x;
-    const int64_t chunk = (P + gridDim.x - 1) / gridDim.x, beg = blockIdx.x * chunk, end = beg + chunk < P ? beg + chunk : P;
-    float acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
-    for (int64_t p = beg + t; p < end; p += 256) {
-        const float *g = rowg + ((int64_t)v * P + p) * CAMG_COLS + 6;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] += g[c];
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) red[c][t] = acc[c];
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) red[c][t] += red[c][t + h];
-        __syncthreads();
-    }
-    if (t < NC) partial[((int64_t)v * gridDim.x + blockIdx.x) * NC + t] = red[t][0];
-}
-
-// final sums (fixed order): poses[sb][v] rows 0..2 (d_R | d_t), focal, c; image_shape += over all views (the caller zeroes it once)
-__global__ __launch_bounds__(256) void camg_view_final_kernel(const float *__restrict__ partial, int NV, int nblk, int sb,
-                                                              float *__restrict__ d_poses, float *__restrict__ d_focal,
-                                                              float *__restrict__ d_c, float *__restrict__ d_ishape)
-{
-    constexpr int NC = CAMG_COLS - 6;
-    for (int t = threadIdx.x; t < NV * NC; t += blockDim.x) {
-    const int v = t / NC, c = t - v * NC;
-    float sum = 0.f;
-    for (int b = 0; b < nblk; ++b) sum += partial[((int64_t)v * nblk + b) * NC + c];
-    const int64_t sv = (int64_t)sb * NV + v;
-    if (c < 9) { if (d_poses) d_poses[sv * 16 + (c / 3) * 4 + c % 3] = sum; }
-    else if (c < 12) { if (d_poses) d_poses[sv * 16 + (c - 9) * 4 + 3] = sum; }
-    else if (c < 14) { if (d_focal) d_focal[sv * 2 + c - 12] = sum; }
-    else if (c < 16) { if (d_c) d_c[sv * 2 + c - 14] = sum; }
-    else if (v == 0 && d_ishape) {
-        float tot = sum;
-        for (int u = 1; u < NV; ++u) {
-            float su = 0.f;
-            for (int b = 0; b < nblk; ++b) su += partial[((int64_t)u * nblk + b) * NC + c];
-            tot += su;
-        }
-        d_ishape[c - 16] += tot;
-    }
-    }
 }
 
 // [N,h*w,C] -> [N,C,h*w] (the layout of encoder.latent and of its gradient), tiled through LDS
@@ -1577,21 +1296,10 @@ int launch_train_point_inputs_bwd(const DinerScene &s, const DinerLatentIndex &i
     float *rowg = workspace, *partial = workspace + R * CAMG_COLS;
     hipLaunchKernelGGL(point_inputs_bwd_kernel, dim3((unsigned)R), dim3(64), 0, st, s, latent_nhwc, rays, z, NR, K, sb, ix.interp, ix.padding,
                        d_in56, d_zlat, rowg, d_depths);
-    int rc = check_launch("train::point_inputs_bwd_kernel");
+    const int rc = check_launch("train::point_inputs_bwd_kernel");
     if (rc) return rc;
-    if (d_rays) {
-        hipLaunchKernelGGL(camg_ray_reduce_kernel, dim3((unsigned)((NR + 255) / 256)), dim3(256), 0, st, rowg, NR, K, s.NV, sb, d_far, d_rays);
-        if ((rc = check_launch("train::camg_ray_reduce_kernel"))) return rc;
-    }
-    if (d_poses || d_focal || d_c || d_image_shape) {
-        const int64_t per = (P + 255) / 256;
-        const int nblk = (int)(per < CAMG_BLOCKS ? per : CAMG_BLOCKS);
-        hipLaunchKernelGGL(camg_view_partial_kernel, dim3((unsigned)nblk, (unsigned)s.NV), dim3(256), 0, st, rowg, P, partial);
-        if ((rc = check_launch("train::camg_view_partial_kernel"))) return rc;
-        hipLaunchKernelGGL(camg_view_final_kernel, dim3(1), dim3(256), 0, st, partial, s.NV, nblk, sb, d_poses, d_focal, d_c, d_image_shape);
-        if ((rc = check_launch("train::camg_view_final_kernel"))) return rc;
-    }
-    return DINER_OK;
+    // the fixed-order reductions of the records: the shape-general path's kernels (train_gen.hip), one copy for both paths
+    return launch_train_camg_reduce(rowg, partial, NR, K, s.NV, sb, d_far, d_rays, d_poses, d_focal, d_c, d_image_shape, st);
 }
 
 }  // namespace diner

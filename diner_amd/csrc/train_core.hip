@@ -18,14 +18,11 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "train_blocks.hpp"
 
 namespace diner {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace train_blocks;
 
 namespace train {
 namespace core {
@@ -53,19 +50,6 @@ struct Args {
     float *colsum;               // += column sums of C (NULL: skipped)
     unsigned int *amax_out;      // max= bits of max |C| (NULL: skipped)
 };
-
-__device__ __forceinline__ void scale_of(const unsigned int *amax, int static_exp, float &s, float &inv)
-{
-    int e = static_exp;
-    if (amax) {
-        const unsigned int b = *amax;
-        const int ex = (int)((b >> 23) & 0xffu) - 127;
-        e = (b == 0u) ? 0 : 13 - ex;
-    }
-    e = e < -100 ? -100 : e > 100 ? 100 : e;
-    s = __uint_as_float((unsigned int)(127 + e) << 23);
-    inv = __uint_as_float((unsigned int)(127 - e) << 23);
-}
 
 template <int N> __device__ __forceinline__ float acc_read()
 {
@@ -102,7 +86,7 @@ __global__ void pack_core_kernel(const float *__restrict__ W, int64_t ld, int tr
 // This lane's 16 float4 of A for tile `tile` -> the core's `net` grid (v[NET + 4*(8*tp + j) ..]: row 32*tp + c, k = 64w + 8j + 4h ..+3).
 // Issued before a layer block: the block's first counted vmcnt wait covers them (loads return in order), so their latency is
 // spent where the partner wave of the SIMD can use the MFMA pipe, and the next S phase finds the data in registers.
-// core registers R..R+3 (x sc, relu'd if RELU: NaN kept) -> fp16 hi / lo pairs; see split4_pk in train.hip
+// core registers R..R+3 (x sc, relu'd if RELU: NaN kept) -> fp16 hi / lo pairs; see split4_pk in train_blocks.hpp
 template <int R, bool RELU> __device__ __forceinline__ void split4_reg(float sc, unsigned &h01, unsigned &h23, unsigned &l01, unsigned &l23)
 {
     float t0, t1, t2, t3;

@@ -1,6 +1,7 @@
 // Shape-general training path: the building blocks that let diner_amd/training_gen.py train any ResnetFC / PositionalEncoding
 // shape of the inference envelope (include/diner_hip.h, "shape-general inference path") in exact fp32:
-//   gemm_act_kernel        the fp32 MFMA GEMM of train.hip (v_mfma_f32_32x32x2_f32, 128 x 128 x 16 tiles, double-buffered LDS)
+//   gemm_act_kernel        the fp32 MFMA GEMM of train.hip (v_mfma_f32_32x32x2_f32, 128 x 128 x 16 tiles, double-buffered LDS;
+//                          the tile loads and the block -> tile map are the shared ones of train_blocks.hpp)
 //                          with activation codes instead of relu flags:
 //                            C[m][n] (+)= sum_k actA(A[m][k]) * actB(B[k][n])  (+ bias[n]) (* act'(S[m][n]))
 //                          act = identity | ReLU | Softplus(beta, threshold 20) (resnetfc.py:49-52,124-127), act' its derivative
@@ -9,7 +10,8 @@
 //                          DINER_INDEX_* mode and its 4-tap footprint, for any num_freqs F and latent width C
 //   point_inputs_bwd_gen   the transpose of point_inputs_gen to the rays, cameras and depth maps (point_inputs_bwd_kernel of
 //                          train.hip for any F, ld_in and C), same per-row records and fixed-order reductions
-// train.hip is left as it is: its code objects (the standard path's) do not change with this file.
+// The fixed-order reductions of the per-row records (camg_* kernels, launch_train_camg_reduce) are here for both training paths:
+// train.hip's point_inputs_bwd_kernel writes the same records and ends in the same call.
 // The point-input kernels are templates on the lookup (train_gen_points.hpp): this file instantiates the 4-tap forms, train_gen_bc.hip the
 // 16-tap bicubic ones next to bicubic_scatter_kernel, in a code object of their own; the GEMM and the reductions are here.
 #include "train_gen_points.hpp"
@@ -17,9 +19,6 @@
 namespace diner {
 
 namespace train_gen {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 16, LDT = 132;  // block tile; LDS tile row stride (floats, 16-byte aligned rows)
 
@@ -35,60 +34,6 @@ struct GemmArgs {
     int accumulate, atomic;
     int64_t k_chunk;             // split-K: blockIdx.z handles k in [z*k_chunk, (z+1)*k_chunk)
 };
-
-// Softplus(beta) as torch evaluates it (x * beta > 20: linear): the formula of points_mlp_gen.hip's helper
-__device__ __forceinline__ float softplus(float v, float beta)
-{
-    const float xb = v * beta;
-    return xb > 20.0f ? v : log1pf(expf(xb)) / beta;
-}
-
-__device__ __forceinline__ float act_fwd(float x, int act, float beta)
-{
-    if (act == DINER_ACT_RELU) return x < 0.0f ? 0.0f : x;   // keeps NaN, like torch.relu
-    if (act == DINER_ACT_SOFTPLUS) return softplus(x, beta);
-    return x;
-}
-
-// g * act'(s) as autograd evaluates it: ReLU threshold_backward ([s > 0]); Softplus softplus_backward
-// (z = exp(beta s), g * z / (z + 1), g where beta s > 20)
-__device__ __forceinline__ float act_bwd(float g, float s, int act, float beta)
-{
-    if (act == DINER_ACT_RELU) return s > 0.0f ? g : 0.0f;
-    if (act == DINER_ACT_SOFTPLUS) {
-        const float xb = s * beta;
-        if (xb > 20.0f) return g;
-        const float z = expf(xb);
-        return g * z / (z + 1.0f);
-    }
-    return g;
-}
-
-// One operand tile (128 x 16, as [k][m]) = 512 float4, two per thread (train.hip tile_load).  KC: the operand is contiguous along
-// the contraction index, else along the tile's long index.  Loads are unconditional from clamped in-range addresses; `ok` zeroes
-// the out-of-range pieces when the tile is stored.
-template <bool KC>
-__device__ __forceinline__ unsigned tile_load(f32x4 (&v)[2], const float *__restrict__ base, int64_t s_long, int64_t s_k, int64_t l0,
-                                              int64_t l_end, int64_t k0, int64_t k_end, int tid)
-{
-    unsigned ok = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = tid + 256 * i;
-        if (KC) {
-            const int64_t l = l0 + (idx >> 2), k = k0 + (idx & 3) * 4;
-            const bool in = l < l_end && k < k_end;
-            ok |= (unsigned)in << i;
-            v[i] = *(const f32x4 *)(base + (l < l_end ? l : l_end - 1) * s_long + (k < k_end ? k : k_end - 4));
-        } else {
-            const int64_t k = k0 + (idx >> 5), l = l0 + (idx & 31) * 4;
-            const bool in = k < k_end && l < l_end;
-            ok |= (unsigned)in << i;
-            v[i] = *(const f32x4 *)(base + (k < k_end ? k : k_end - 1) * s_k + (l < l_end ? l : l_end - 4));
-        }
-    }
-    return ok;
-}
 
 // the operand transform happens here, once per staged element; out-of-range pieces are 0 (not act(0): Softplus(0) != 0)
 template <bool KC>
@@ -116,19 +61,8 @@ __device__ __forceinline__ void tile_store(float (*T)[LDT], const f32x4 (&v)[2],
     }
 }
 
-// Block -> output tile, XCD-aware (train.hip tile_of): the column blocks of one row tile go to consecutive workgroups of one XCD
-__device__ __forceinline__ void tile_of(const GemmArgs &g, int64_t &m0, int &n0)
-{
-    const int64_t gm = (g.M + BM - 1) / BM, lin = blockIdx.x;
-    const int gn = (g.N + BN - 1) / BN;
-    const int64_t full = gm / 8 * 8;
-    int64_t mt, nb;
-    if (lin < full * gn) { const int64_t j = lin / 8; nb = j % gn; mt = j / gn * 8 + lin % 8; }
-    else { const int64_t r = lin - full * gn; mt = full + r / gn; nb = r % gn; }
-    m0 = mt * BM;
-    n0 = (int)nb * BN;
-}
-
+// This kernel's own epilogue, not train_blocks.hpp's epilogue<PA, PB>: it forms the row index in 64-bit steps (m0 + mbl + ...), the shared one
+// in 32-bit ones before adding m0, and hipcc allocates this kernel's registers differently around the other form.
 // C layout of the 32x32 MFMA accumulators: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
 __device__ __forceinline__ void epilogue(const GemmArgs &g, const f32x16 (&acc)[2][2], int64_t m0, int n0, int wm, int wn, int lane)
 {
@@ -181,7 +115,7 @@ __global__ __launch_bounds__(256) void gemm_act_kernel(GemmArgs g)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int64_t m0;
     int n0;
-    tile_of(g, m0, n0);
+    tile_of(g.M, g.N, BM, BN, blockIdx.x, m0, n0);
     const int64_t kbeg = (int64_t)blockIdx.z * g.k_chunk;
     const int64_t kend = kbeg + g.k_chunk < g.K ? kbeg + g.k_chunk : g.K;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -225,7 +159,8 @@ __global__ __launch_bounds__(256) void gemm_act_kernel(GemmArgs g)
     epilogue(g, acc, m0, n0, wm, wn, lane);
 }
 
-// The fixed-order reductions of the per-row records (train.hip's camg_* kernels, the same sums in the same order)
+// The fixed-order reductions of the per-row records, for both training paths (train.hip's point_inputs_bwd_kernel writes the same
+// records): d_rays[sb][ray] = (sum over views and samples of d_o, d_d;  0 (near: sampler only);  d_far or 0) -- one thread per ray
 __global__ __launch_bounds__(256) void camg_ray_reduce_kernel(const float *__restrict__ rowg, int64_t NR, int K, int NV, int sb,
                                                               const float *__restrict__ d_far, float *__restrict__ d_rays)
 {
@@ -246,6 +181,7 @@ __global__ __launch_bounds__(256) void camg_ray_reduce_kernel(const float *__res
     o[7] = d_far ? d_far[(int64_t)sb * NR + ray] : 0.0f;
 }
 
+// per-view partial sums of the camera columns (6..23) over a contiguous chunk of the view's P rows: grid (blocks, NV)
 __global__ __launch_bounds__(256) void camg_view_partial_kernel(const float *__restrict__ rowg, int64_t P, float *__restrict__ partial)
 {
     constexpr int NC = CAMG_COLS - 6;
@@ -272,6 +208,7 @@ __global__ __launch_bounds__(256) void camg_view_partial_kernel(const float *__r
     if (t < NC) partial[((int64_t)v * gridDim.x + blockIdx.x) * NC + t] = red[t][0];
 }
 
+// final sums (fixed order): poses[sb][v] rows 0..2 (d_R | d_t), focal, c; image_shape += over all views (the caller zeroes it once)
 __global__ __launch_bounds__(256) void camg_view_final_kernel(const float *__restrict__ partial, int NV, int nblk, int sb,
                                                               float *__restrict__ d_poses, float *__restrict__ d_focal,
                                                               float *__restrict__ d_c, float *__restrict__ d_ishape)
@@ -343,7 +280,7 @@ int launch_train_point_inputs_bwd_gen(const DinerScene &s, const DinerLatentInde
     return launch_train_camg_reduce(rowg, partial, NR, K, s.NV, sb, d_far, d_rays, d_poses, d_focal, d_c, d_image_shape, st);
 }
 
-// (also behind train_gen_bc.hip's backward)
+// (behind every point-input backward: this file's, train_gen_bc.hip's and train.hip's)
 int launch_train_camg_reduce(const float *rowg, float *partial, int64_t NR, int K, int NV, int sb, const float *d_far, float *d_rays,
                              float *d_poses, float *d_focal, float *d_c, float *d_image_shape, hipStream_t st)
 {

@@ -13,7 +13,6 @@ namespace train_gen {
 // in registers while the 4 columns and 4 rows stay the same and flushed with one atomic per tap when they change.  A tap of weight 0
 // (zeros padding outside the map) adds nothing and is never flushed.  Several taps of one footprint may be the same texel (border /
 // reflection at the rim, maps smaller than the footprint): the atomics add them up.
-constexpr int SCATTER_RUN = 16;
 __global__ __launch_bounds__(64) void bicubic_scatter_kernel(const float *__restrict__ dz, const float *__restrict__ taps, int64_t P, int C,
                                                              int h, int w, int NV, int sb, float *__restrict__ dlatent_nhwc)
 {

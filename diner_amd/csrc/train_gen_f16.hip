@@ -3,25 +3,20 @@
 //   gemm_act_f16x3_kernel  C[m][n] (+)= sum_k actA(A[m][k]) * actB(B[k][n])  (+ bias[n]) (* act'(S[m][n]))
 //                          every operand element: activation in fp32, times a power of two (2^exp, or the one that maps *amax into
 //                          [2^13, 2^14)), split into fp16 hi + lo; three v_mfma_f32_32x32x16_f16 per product (lo*hi, hi*lo, hi*hi), fp32
-//                          accumulation, C divided by the two scales; the derivative in the epilogue is fp32 (train_gen.hip's act_bwd).
+//                          accumulation, C divided by the two scales; the derivative in the epilogue is fp32 (act_bwd).
 //                          128 x 128 x 32 block tiles, 4 waves as 2 x 2, LDS images double-buffered, 3-stage pipeline.
 //                          BPRE: the B operand (a weight) arrives pre-split (split_weight_kernel): its tile is four 16-byte loads per
 //                          thread that go to LDS as they are -- no VALU work, no bounds (the planes are zero-padded to whole tiles).
 //   split_weight_kernel    fp16 hi / lo planes of a weight matrix of any (N, K), either orientation, made once per parameter version
 // plus the C entry points (diner_train_gemm_act_f16x3, diner_train_gemm_act_f16x3_w, diner_train_split_weight).  A translation unit of
-// its own: the code objects of train.hip and train_gen.hip stay what they were.
-#include <math.h>
-
-#include "common.hpp"
+// its own (a code object of its own); the tile loads, the split, the scale and the epilogue are the shared ones of train_blocks.hpp.
+#include "train_blocks.hpp"
 
 namespace diner {
 
 namespace train_gen_f16 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace train_blocks;
 
 constexpr int BM = 128, BN = 128, BKH = 32;
 constexpr int UNITS_T = (BKH / 8) * 128;   // 16-byte units of one fp16 plane of one operand tile
@@ -41,70 +36,6 @@ struct GemmArgs {
     const unsigned int *amax_a, *amax_b;
     int exp_a, exp_b;
 };
-
-// train_gen.hip's activation and derivative, formula for formula
-__device__ __forceinline__ float softplus(float v, float beta)
-{
-    const float xb = v * beta;
-    return xb > 20.0f ? v : log1pf(expf(xb)) / beta;
-}
-
-__device__ __forceinline__ float act_bwd(float g, float s, int act, float beta)
-{
-    if (act == DINER_ACT_RELU) return s > 0.0f ? g : 0.0f;
-    if (act == DINER_ACT_SOFTPLUS) {
-        const float xb = s * beta;
-        if (xb > 20.0f) return g;
-        const float z = expf(xb);
-        return g * z / (z + 1.0f);
-    }
-    return g;
-}
-
-// LDS image of an operand tile: 16-byte units (u = k/8, row) at u*128 + (row ^ 4u); an MFMA fragment (8 consecutive k of one row) is one
-// conflict-free ds_read_b128
-__device__ __forceinline__ int unit(int u, int row) { return u * 128 + (row ^ (4 * u)); }
-
-// slot of tile row l for an operand staged by the transposing store (tile_store<false>): the 4 x 4 index transpose inside every 16-row
-// block (an involution); makes that store conflict-free, the accumulator rows / columns come out in slot order and are mapped back
-__device__ __forceinline__ int slot16(int x) { return (x & ~15) | ((x & 3) << 2) | ((x >> 2) & 3); }
-
-__device__ __forceinline__ void scale_of(const unsigned int *amax, int static_exp, float &s, float &inv)
-{
-    int e = static_exp;
-    if (amax) {
-        const unsigned int b = *amax;
-        const int ex = (int)((b >> 23) & 0xffu) - 127;
-        e = (b == 0u) ? 0 : 13 - ex;
-    }
-    e = e < -100 ? -100 : e > 100 ? 100 : e;
-    s = __uint_as_float((unsigned int)(127 + e) << 23);
-    inv = __uint_as_float((unsigned int)(127 - e) << 23);
-}
-
-// One streamed operand tile = 128 (long index l) x 32 (k) fp32 = 1024 float4, four per thread.  KC (contiguous along k): float4 along
-// k.  else: a 4(k) x 4(l) micro-tile per thread, float4 along l.  Unconditional loads from clamped addresses + a validity bit per piece.
-template <bool KC>
-__device__ __forceinline__ unsigned tile_load(f32x4 (&v)[4], const float *__restrict__ base, int64_t s_long, int64_t s_k, int64_t l0,
-                                              int64_t l_end, int64_t k0, int64_t k_end, int tid)
-{
-    unsigned ok = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (KC) {
-            const int idx = tid + 256 * i;
-            const int64_t l = l0 + (idx >> 3), k = k0 + (idx & 7) * 4;
-            ok |= (unsigned)(l < l_end && k < k_end) << i;
-            v[i] = *(const f32x4 *)(base + (l < l_end ? l : l_end - 1) * s_long + (k < k_end ? k : k_end - 4));
-        } else {
-            const int kq4 = (tid & 3) | ((tid >> 4) & 4), lq4 = ((tid >> 2) & 15) | ((tid >> 3) & 16);
-            const int64_t k = k0 + kq4 * 4 + i, l = l0 + lq4 * 4;
-            ok |= (unsigned)(k < k_end && l < l_end) << i;
-            v[i] = *(const f32x4 *)(base + (k < k_end ? k : k_end - 1) * s_k + (l < l_end ? l : l_end - 4));
-        }
-    }
-    return ok;
-}
 
 // A pre-split weight tile: 128 rows x 32 halfs x {hi, lo} = 2 x 512 16-byte units, two per plane and thread (pieces 0, 1: hi; 2, 3: lo),
 // carried as raw 16-byte words.  The planes are whole tiles (rows padded to 128, k to 32): no bounds, past the last k-step the
@@ -130,44 +61,6 @@ __device__ __forceinline__ void tile_store_w(h8 *Thi, h8 *Tlo, const f32x4 (&v)[
         *(f32x4 *)&Thi[o] = v[i];
         *(f32x4 *)&Tlo[o] = v[2 + i];
     }
-}
-
-// (x * sc, floored) -> fp16 hi / lo pairs in packed assembly: hi = cvt_pk(t), lo = fma_mix(hi * -1 + t) rounded once to fp16
-// = (f16)(t - (float)hi) (the difference is exact in fp32).  RELU keeps NaN like torch.relu (v_cmp_ngt + v_cndmask).
-template <bool RELU>
-__device__ __forceinline__ void split4_pk(float x0, float x1, float x2, float x3, float sc, unsigned &h01, unsigned &h23, unsigned &l01, unsigned &l23)
-{
-    float t0, t1, t2, t3;
-    if constexpr (RELU) {
-        unsigned long long m0, m1, m2, m3;
-        asm volatile("v_mul_f32 %4, %12, %16\n\tv_mul_f32 %5, %13, %16\n\tv_mul_f32 %6, %14, %16\n\tv_mul_f32 %7, %15, %16\n\t"
-                     "v_cmp_ngt_f32_e64 %8, 0, %4\n\tv_cmp_ngt_f32_e64 %9, 0, %5\n\tv_cmp_ngt_f32_e64 %10, 0, %6\n\tv_cmp_ngt_f32_e64 %11, 0, %7\n\t"
-                     "v_cndmask_b32_e64 %4, 0, %4, %8\n\tv_cndmask_b32_e64 %5, 0, %5, %9\n\tv_cndmask_b32_e64 %6, 0, %6, %10\n\tv_cndmask_b32_e64 %7, 0, %7, %11\n\t"
-                     "v_cvt_pk_f16_f32 %0, %4, %5\n\tv_cvt_pk_f16_f32 %1, %6, %7\n\t"
-                     "v_fma_mixlo_f16 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mixlo_f16 %3, %1, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-                     "v_fma_mixhi_f16 %2, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %3, %1, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                     : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3)
-                     : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(sc));
-    } else {
-        asm volatile("v_mul_f32 %4, %8, %12\n\tv_mul_f32 %5, %9, %12\n\tv_mul_f32 %6, %10, %12\n\tv_mul_f32 %7, %11, %12\n\t"
-                     "v_cvt_pk_f16_f32 %0, %4, %5\n\tv_cvt_pk_f16_f32 %1, %6, %7\n\t"
-                     "v_fma_mixlo_f16 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mixlo_f16 %3, %1, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-                     "v_fma_mixhi_f16 %2, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %3, %1, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                     : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-                     : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(sc));
-    }
-}
-
-__device__ __forceinline__ void put4(h8 *Thi, h8 *Tlo, int l, int kq, float x0, float x1, float x2, float x3, bool relu, float sc)
-{
-    u32x2 hi, lo;   // relu is wave-uniform; NaN stays NaN
-    unsigned a, b, c, d;
-    if (relu) split4_pk<true>(x0, x1, x2, x3, sc, a, b, c, d);
-    else split4_pk<false>(x0, x1, x2, x3, sc, a, b, c, d);
-    hi.x = a; hi.y = b; lo.x = c; lo.y = d;
-    const int o = unit(kq >> 3, l) * 8 + (kq & 4);
-    *(u32x2 *)((_Float16 *)Thi + o) = hi;
-    *(u32x2 *)((_Float16 *)Tlo + o) = lo;
 }
 
 // The operand transform happens here, once per staged element, in fp32 and before the scale and the split; out-of-range pieces are
@@ -203,65 +96,6 @@ __device__ __forceinline__ void tile_store(h8 *Thi, h8 *Tlo, const f32x4 (&v)[4]
     }
 }
 
-// Block -> output tile, XCD-aware (train_gen.hip tile_of): the column blocks of one row tile go to consecutive workgroups of one XCD
-__device__ __forceinline__ void tile_of(const GemmArgs &g, int64_t lin, int64_t &m0, int &n0)
-{
-    const int64_t gm = (g.M + BM - 1) / BM;
-    const int gn = (g.N + BN - 1) / BN;
-    const int64_t full = gm / 8 * 8;
-    int64_t mt, nb;
-    if (lin < full * gn) { const int64_t j = lin / 8; nb = j % gn; mt = j / gn * 8 + lin % 8; }
-    else { const int64_t r = lin - full * gn; mt = full + r / gn; nb = r % gn; }
-    m0 = mt * BM;
-    n0 = (int)nb * BN;
-}
-
-// C layout of the 32x32 MFMA accumulators: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5).  PA / PB: the A / B tile was staged in
-// slot order.  All 16 reads of a tile (old C, S) are issued before the first dependent store.
-template <bool PA, bool PB>
-__device__ __forceinline__ void epilogue(const GemmArgs &g, const f32x16 (&acc)[2][2], int64_t m0, int n0, int wm, int wn, int lane, int64_t bz,
-                                         float unscale)
-{
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb) {
-        const int nc = wn + tb * 32 + (lane & 31), n = n0 + (PB ? slot16(nc) : nc);
-        if (n >= g.N) continue;
-        const float bias = (g.bias && bz == 0) ? g.bias[n] : 0.0f;
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta) {
-            const int mbl = wm + ta * 32 + 4 * (lane >> 5);
-            auto row_of = [&](int i) -> int64_t { const int r = mbl + (i & 3) + 8 * (i >> 2); return m0 + (PA ? slot16(r) : r); };
-            float old[16], msk[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { old[i] = 0.0f; msk[i] = 1.0f; }
-            if (g.accumulate && !g.atomic) {  // uniform branches, unconditional loads from clamped rows
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t m = row_of(i);
-                    old[i] = g.C[(m < g.M ? m : g.M - 1) * g.ldc + n];
-                }
-            }
-            if (g.S) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int64_t m = row_of(i);
-                    msk[i] = g.S[(m < g.M ? m : g.M - 1) * g.lds_ + n];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int64_t m = row_of(i);
-                if (m >= g.M) continue;
-                float v = acc[ta][tb][i] * unscale + bias;
-                if (g.S) v = act_bwd(v, msk[i], g.act_s, g.beta);
-                float *c = g.C + m * g.ldc + n;
-                if (g.atomic) atomicAdd(c, v);
-                else *c = old[i] + v;
-            }
-        }
-    }
-}
-
 // AK: A contiguous along k (sak == 1) else along m.  BNC: B contiguous along n (sbn == 1) else along k.  BPRE: B pre-split (then BNC is
 // false: the planes are k-contiguous).  SP: Softplus on a staged operand.
 // The k-loop is train.hip's 3-stage pipeline: while tile t is multiplied out of LDS buffer t&1, tile t+1 sits in registers (split and
@@ -285,7 +119,7 @@ __global__ __launch_bounds__(256, (AK && !BNC) ? 2 : 1) void gemm_act_f16x3_kern
         bz = (j / gridDim.x) * 8 + xcd;
         bx = j % gridDim.x;
     }
-    tile_of(g, bx, m0, n0);
+    tile_of(g.M, g.N, BM, BN, bx, m0, n0);
     const int64_t kbeg = bz * g.k_chunk;
     const int64_t kend = kbeg + g.k_chunk < g.K ? kbeg + g.k_chunk : g.K;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -360,7 +194,8 @@ __global__ __launch_bounds__(256, (AK && !BNC) ? 2 : 1) void gemm_act_f16x3_kern
 #undef DINER_GEMM_STEP
 #undef DINER_LOAD_B
 #undef DINER_STORE_B
-    epilogue<!AK, BNC && !BPRE>(g, acc, m0, n0, wm, wn, lane, bz, ia * ib);
+    epilogue<!AK, BNC && !BPRE>(g, acc, m0, n0, wm, wn, lane, bz, ia * ib,
+                                [&](float v, float s) { return g.S ? act_bwd(v, s, g.act_s, g.beta) : v; });
 }
 
 // fp16 hi / lo planes of a weight for the BPRE kernel: plane[n][k] = split(B[k][n] * 2^exp) for n < N, k < K, 0 in the padding

@@ -3,15 +3,13 @@
 // lookup (common.hpp bicubic_footprint) and its gradient with respect to the grid (instantiated by train_gen_bc.hip, next to
 // bicubic_scatter_kernel, in a code object of their own).
 #pragma once
-#include "common.hpp"
+#include "train_blocks.hpp"
 
 namespace diner {
 
-// the fixed-order reductions of the rowg records [R, CAMG_COLS] to the rays and the per-view camera gradients (train_gen.hip)
-int launch_train_camg_reduce(const float *rowg, float *partial, int64_t NR, int K, int NV, int sb, const float *d_far, float *d_rays,
-                             float *d_poses, float *d_focal, float *d_c, float *d_image_shape, hipStream_t st);
-
 namespace train_gen {
+
+using namespace train_blocks;
 
 // ---- per-(view, point) MLP inputs of any num_freqs F and latent width C ---------------------------------------------------------
 // rows are view-major: row = v*P + p.  in [R, ld_in]: pixelnerf.py:128's 7 + 8F inputs in point_inputs_kernel's column order
@@ -100,29 +98,6 @@ __global__ __launch_bounds__(64) void point_inputs_gen_kernel(DinerScene s, cons
 }
 
 // ---- the transpose of point_inputs_gen_kernel to the geometric leaves (train.hip point_inputs_bwd_kernel for any F, ld_in, C) ---
-constexpr int CAMG_COLS = 24;   // d_o 3, d_d 3, d_R 9 (row-major), d_t 3, d_focal 2, d_c 2, d_image_shape 2
-constexpr int CAMG_BLOCKS = 256;   // per-view partial sums of the pose / intrinsics reduction (at most)
-
-// ATen's clip_coordinates_set_grad + reflect_coordinates_set_grad (align_corners=False)
-__device__ __forceinline__ float pad_coord_grad(float x, int size, int padding, float &g)
-{
-    g = 1.0f;
-    if (padding == DINER_INDEX_PAD_REFLECTION) {
-        float in = x + 0.5f;                  // reflect over [-0.5, size - 0.5]
-        float m = 1.0f;
-        if (in < 0.0f) { m = -1.0f; in = -in; }
-        const float span = (float)size, extra = fmodf(in, span);
-        const int flips = (int)floorf(in / span);
-        if (flips % 2 == 0) { g = m; x = extra - 0.5f; }
-        else { g = -m; x = span - extra - 0.5f; }
-    }
-    if (padding != DINER_INDEX_PAD_ZEROS) {
-        if (x <= 0.0f || x >= (float)(size - 1)) g = 0.0f;
-        x = clipf(x, (float)(size - 1));
-    }
-    return x;
-}
-
 template <bool BC>
 __global__ __launch_bounds__(64) void point_inputs_bwd_gen_kernel(DinerScene s, const float *__restrict__ latent_nhwc,
                                                                   const float *__restrict__ rays, const float *__restrict__ zsamp,

@@ -186,6 +186,112 @@ def _mlp_params(mlp):
 CAMERA_INPUTS = ("rays", "poses", "focal", "c", "image_shape", "depths")
 
 
+# ---- the scaffolding both autograd functions (_RenderFn here, training_gen._RenderGenFn) stand on: everything around the MLP's layer
+# schedule and the point-input calls
+
+def prepare_latent(L, latent, dev, st):
+    """-> lat, lat_nhwc, packed: the NHWC latent the gathers read -- the latent's own buffer when it is packed
+    (glue.assemble_latent's layout; lat is None), else a copy made by diner_pack_latent of the fp32 NCHW tensor ``lat``."""
+    if latent_is_packed(latent):
+        return None, latent.detach().permute(0, 1, 3, 4, 2), True
+    lat = latent.detach().to(torch.float32).contiguous()
+    SBl, NVl, Cl, hl, wl = lat.shape
+    lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)   # coalesced texel reads for the gather
+    check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+    return lat, lat_nhwc, False
+
+
+def remember_versions(ctx, params, latent, cams):
+    """backward() re-reads the parameters and the latent (their fp32 views alias the live tensors): remember their versions, as
+    ctx.save_for_backward would, so that an in-place update between forward and backward is an error instead of a silently wrong dX
+    (optimizer.step / EMA copy_ under gradient accumulation).  The geometric leaves ``cams`` are held (as the reference's graph holds
+    them), so that a caller's temporary rays stay checkable."""
+    ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
+    ctx.cam_versions = [(t, t._version) for t in cams]
+
+
+def check_versions(ctx, who):
+    for t, ver in [(ref(), ver) for ref, ver in ctx.versions] + ctx.cam_versions:
+        if t is None or t._version != ver:
+            raise RuntimeError(f"{who}: one of the variables needed for gradient computation (an MLP parameter, "
+                               "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
+                               "between forward and backward")
+
+
+def composite_backward(L, ctx, d_rgb, d_depth, d_weights, want_far, st):
+    """-> d_rgbsigma [SB,NR,K,4], d_far [SB,NR] or None: the compositing backward of ctx's render (want_far: the same, and the
+    gradient of rays[..., 7] through delta_inf = far - z_K)."""
+    rays, z, rgbsigma = ctx.rays, ctx.z, ctx.rgbsigma
+    dev = rays.device
+    SB, NR, K = z.shape
+    c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    d_rgb, d_depth, d_weights = c(d_rgb), c(d_depth), c(d_weights)
+    if d_rgb is None:
+        d_rgb = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev)
+    d_rgbsigma = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=dev)
+    white = int(bool(ctx.renderer.white_bkgd))
+    if not want_far:
+        check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
+                                         _p(d_rgbsigma), st), "diner_composite_backward")
+        return d_rgbsigma, None
+    d_far = torch.empty((SB, NR), dtype=torch.float32, device=dev)
+    check(L.diner_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
+                                         _p(d_rgbsigma), _p(d_far), st), "diner_composite_backward_far")
+    return d_rgbsigma, d_far
+
+
+def camera_grad_buffers(L, want, scene, SB, NR, K, dev):
+    """-> (g_rays, g_poses, g_focal, g_c, g_ishape, g_depths), workspace: the gradient buffers of the wanted geometric leaves (None:
+    not wanted; zeroed where the kernels accumulate into them) and the point-input backward's workspace."""
+    NV = scene.NV
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    z0 = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
+    bufs = (f(SB, NR, 8) if want["rays"] else None,
+            z0((SB, NV, 4, 4)) if want["poses"] else None,
+            f(SB, NV, 2) if want["focal"] else None,
+            f(SB, NV, 2) if want["c"] else None,
+            z0(2) if want["image_shape"] else None,
+            z0((SB, NV, scene.H, scene.W)) if want["depths"] else None)
+    return bufs, f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
+
+
+def latent_grad_out(L, d_lat_nhwc, lat_shape, packed, st):
+    """The latent's gradient as autograd wants it: for a packed latent the NHWC buffer in the latent's own strides
+    (glue.assemble_latent's backward reads it as it is), else its NCHW transpose."""
+    if packed:
+        return d_lat_nhwc.permute(0, 1, 4, 2, 3)
+    SBl, NVl, Cl, hl, wl = lat_shape
+    d_lat = torch.empty(lat_shape, dtype=torch.float32, device=d_lat_nhwc.device)
+    check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+    return d_lat
+
+
+def camera_grads_out(bufs, cam_shapes):
+    """The six camera gradients (CAMERA_INPUTS order) in the callers' shapes; ``bufs`` None: none was wanted."""
+    if bufs is None:
+        return (None,) * 6
+    g_rays, g_poses, g_focal, g_c, g_ishape, g_depths = bufs
+    sh_poses, sh_focal, sh_c, sh_ishape, sh_depths = cam_shapes
+    return (g_rays,
+            None if g_poses is None else g_poses[..., :sh_poses[-2], :].reshape(sh_poses),   # ([.., 3, 4] poses: rows 0..2)
+            None if g_focal is None else g_focal.reshape(sh_focal),
+            None if g_c is None else g_c.reshape(sh_c),
+            None if g_ishape is None else g_ishape.reshape(sh_ishape),
+            None if g_depths is None else g_depths.reshape(sh_depths))
+
+
+def camera_leaves(model, rays):
+    """The geometric tensors autograd can differentiate the render with respect to (CAMERA_INPUTS order)."""
+    return (rays, model.poses, model.focal, model.c, model.image_shape, model.encoder.depths)
+
+
+def camera_inputs(model, rays):
+    """-> cams, f32: the geometric leaves and their fp32 contiguous copies (graph-preserving: the gradient flows back to the caller's
+    dtype), which the autograd functions take in the leaves' place."""
+    cams = camera_leaves(model, rays)
+    return cams, [t.to(torch.float32).contiguous() for t in cams]
+
+
 class _RenderFn(torch.autograd.Function):
     """(rays, latent, poses, focal, c, image_shape, depths, *mlp_params) -> (rgb, depth, weights) for fixed samples.
 
@@ -203,21 +309,9 @@ class _RenderFn(torch.autograd.Function):
         NV, P = scene.NV, NR * K
         R = NV * P
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        ctx.lat_packed = latent_is_packed(latent)
-        if ctx.lat_packed:   # glue.assemble_latent's layout: the gathers read the latent's own buffer
-            lat, lat_nhwc = None, latent.detach().permute(0, 1, 3, 4, 2)
-        else:
-            lat = latent.detach().to(torch.float32).contiguous()
-            SBl, NVl, Cl, hl, wl = lat.shape
-            lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)   # coalesced texel reads for the gather
-            check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+        lat, lat_nhwc, ctx.lat_packed = prepare_latent(L, latent, dev, st)
         prm = [p.detach().to(torch.float32).contiguous() for p in params]
-        # backward() re-reads these tensors (they alias the live parameters): remember their versions, as
-        # ctx.save_for_backward would, so that an in-place update between forward and backward is an error instead of a
-        # silently wrong dX (optimizer.step / EMA copy_ under gradient accumulation)
-        ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
-        # the geometric leaves: held (as the reference's graph holds them), so that a caller's temporary rays stay checkable
-        ctx.cam_versions = [(t, t._version) for t in cams]
+        remember_versions(ctx, params, latent, cams)
         w_in56 = torch.zeros((HID, 56), dtype=torch.float32, device=dev)
         w_in56[:, :55] = prm[0]
         rgbsigma = f(SB, NR, K, 4)
@@ -277,11 +371,7 @@ class _RenderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_rgb, d_depth, d_weights):
         L = _lib.lib()
-        for t, ver in [(ref(), ver) for ref, ver in ctx.versions] + ctx.cam_versions:
-            if t is None or t._version != ver:
-                raise RuntimeError("diner_amd.training: one of the variables needed for gradient computation (an MLP parameter, "
-                                   "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
-                                   "between forward and backward")
+        check_versions(ctx, "diner_amd.training")
         # which geometric leaves want a gradient (inputs 6 and 8..12: rays, poses, focal, c, image_shape, depths)
         want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[6],) + tuple(ctx.needs_input_grad[8:13])))
         cam_any = any(want.values())
@@ -293,29 +383,10 @@ class _RenderFn(torch.autograd.Function):
         NV, P = scene.NV, NR * K
         R = NV * P
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-        d_rgb, d_depth, d_weights = c(d_rgb), c(d_depth), c(d_weights)
-        if d_rgb is None:
-            d_rgb = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev)
-        d_rgbsigma = f(SB, NR, K, 4)
-        d_far = None
-        if want["rays"]:   # the same, and far's gradient (delta_inf = far - z_K)
-            d_far = f(SB, NR)
-            check(L.diner_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K,
-                                                 int(bool(ctx.renderer.white_bkgd)), _p(d_rgbsigma), _p(d_far), st), "diner_composite_backward_far")
-        else:
-            check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K,
-                                             int(bool(ctx.renderer.white_bkgd)), _p(d_rgbsigma), st), "diner_composite_backward")
+        d_rgbsigma, d_far = composite_backward(L, ctx, d_rgb, d_depth, d_weights, want["rays"], st)
+        cam_bufs = None
         if cam_any:
-            sh_poses, sh_focal, sh_c, sh_ishape, sh_depths = ctx.cam_shapes
-            z0 = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
-            g_rays = f(SB, NR, 8) if want["rays"] else None
-            g_poses = z0((SB, NV, 4, 4)) if want["poses"] else None
-            g_focal = f(SB, NV, 2) if want["focal"] else None
-            g_c = f(SB, NV, 2) if want["c"] else None
-            g_ishape = z0(2) if want["image_shape"] else None
-            g_depths = z0((SB, NV, scene.H, scene.W)) if want["depths"] else None
-            ws = f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
+            cam_bufs, ws = camera_grad_buffers(L, want, scene, SB, NR, K, dev)
             lat_nhwc = ctx.keep[1]
             ix = ctx.ix if ctx.ix is not None else _lib.DinerLatentIndex(0, 0)
         g = [torch.zeros_like(p) for p in prm]          # parameter gradients (fp32, accumulated atomically)
@@ -366,31 +437,15 @@ class _RenderFn(torch.autograd.Function):
                 d_in56 = f(R, 56)
                 linear_bwd_x(d_xv, ctx.w_in56, None, d_in56, prec=prec, amax=a_xs)
                 check(L.diner_train_point_inputs_backward(C.byref(scene), C.byref(ix), _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in56),
-                                                          _p(d_zl), _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c),
-                                                          _p(g_ishape), _p(g_depths), st), "diner_train_point_inputs_backward")
+                                                          _p(d_zl), _p(d_far), _p(ws), *map(_p, cam_bufs), st),
+                      "diner_train_point_inputs_backward")
             check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, HID, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                   "diner_train_bilinear_scatter")
-        if ctx.lat_packed:   # the gradient in the latent's own (NHWC) strides: glue.assemble_latent's backward reads it as it is
-            d_lat = d_lat_nhwc.permute(0, 1, 4, 2, 3)
-        else:
-            d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
-            check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+        d_lat = latent_grad_out(L, d_lat_nhwc, ctx.lat_shape, ctx.lat_packed, st)
         g[0] = g_in56[:, :55].contiguous()
         g[1] = g[3].clone()  # lin_in's bias sees the same dY as lin_z[0]'s: x = lin_in(..) + lin_z[0](z)
-        cam = (None,) * 6
-        if cam_any:
-            cam = (g_rays,
-                   None if g_poses is None else g_poses[..., :sh_poses[-2], :].reshape(sh_poses),   # ([.., 3, 4] poses: rows 0..2)
-                   None if g_focal is None else g_focal.reshape(sh_focal),
-                   None if g_c is None else g_c.reshape(sh_c),
-                   None if g_ishape is None else g_ishape.reshape(sh_ishape),
-                   None if g_depths is None else g_depths.reshape(sh_depths))
+        cam = camera_grads_out(cam_bufs, ctx.cam_shapes)
         return (None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
-
-
-def camera_leaves(model, rays):
-    """The geometric tensors autograd can differentiate the render with respect to (CAMERA_INPUTS order)."""
-    return (rays, model.poses, model.focal, model.c, model.image_shape, model.encoder.depths)
 
 
 def render_with_grad(renderer, model, rays, z, scene, keep=None):
@@ -398,6 +453,5 @@ def render_with_grad(renderer, model, rays, z, scene, keep=None):
     (poses, focal, c, image_shape) and depth maps (encoder.depths) when they require grad."""
     params = _mlp_params(model.mlp_fine)
     ix = renderer._latent_index(model)   # the encoder's lookup mode (None: bilinear / border)
-    cams = camera_leaves(model, rays)
-    f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
+    cams, f32 = camera_inputs(model, rays)
     return _RenderFn.apply(renderer, scene, ix, keep, cams, z, *f32[:1], model.encoder.latent, *f32[1:], *params)

@@ -23,18 +23,10 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .glue import latent_is_packed
-from .training import CAMERA_INPUTS, EXP_ACT, EXP_W, camera_leaves
+from .training import (CAMERA_INPUTS, EXP_ACT, EXP_W, _p, _st, camera_grad_buffers, camera_grads_out, camera_inputs, camera_leaves,
+                       check_versions, composite_backward, latent_grad_out, prepare_latent, remember_versions)
 
 K_CHUNK = 4096  # rows per split of the weight-gradient GEMMs (multiple of 32)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _st(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class Act:
@@ -198,18 +190,9 @@ class _RenderGenFn(torch.autograd.Function):
         H, F = shape.d_hidden, shape.num_freqs
         ld_in = 8 * (F + 1)
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        ctx.lat_packed = latent_is_packed(latent)
-        if ctx.lat_packed:   # glue.assemble_latent's layout: the gathers read the latent's own buffer
-            lat, lat_nhwc = None, latent.detach().permute(0, 1, 3, 4, 2)
-        else:
-            lat = latent.detach().to(torch.float32).contiguous()
-            SBl, NVl, Cl, hl, wl = lat.shape
-            lat_nhwc = torch.empty((SBl, NVl, hl, wl, Cl), dtype=torch.float32, device=dev)
-            check(L.diner_pack_latent(_p(lat), SBl * NVl, Cl, hl, wl, _p(lat_nhwc), st), "diner_pack_latent")
+        lat, lat_nhwc, ctx.lat_packed = prepare_latent(L, latent, dev, st)
         prm = [p.detach().to(torch.float32).contiguous() for p in params]
-        # backward() re-reads these tensors: an in-place update between forward and backward must be an error (training._RenderFn)
-        ctx.versions = [(weakref.ref(p), p._version) for p in params] + [(weakref.ref(latent), latent._version)]
-        ctx.cam_versions = [(t, t._version) for t in cams]
+        remember_versions(ctx, params, latent, cams)
         w_in = torch.zeros((H, ld_in), dtype=torch.float32, device=dev)   # lin_in's weight, zero-padded to the input's ld_in columns
         w_in[:, :shape.d_in] = prm[0]
 
@@ -264,11 +247,7 @@ class _RenderGenFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_rgb, d_depth, d_weights):
         L = _lib.lib()
-        for t, ver in [(ref(), ver) for ref, ver in ctx.versions] + ctx.cam_versions:
-            if t is None or t._version != ver:
-                raise RuntimeError("diner_amd.training_gen: one of the variables needed for gradient computation (an MLP parameter, "
-                                   "encoder.latent, or a ray / camera / depth-map tensor) has been modified by an inplace operation "
-                                   "between forward and backward")
+        check_versions(ctx, "diner_amd.training_gen")
         # which geometric leaves want a gradient (inputs 8 and 10..14: rays, poses, focal, c, image_shape, depths)
         want = dict(zip(CAMERA_INPUTS, (ctx.needs_input_grad[8],) + tuple(ctx.needs_input_grad[10:15])))
         cam_any = any(want.values())
@@ -281,30 +260,10 @@ class _RenderGenFn(torch.autograd.Function):
         NV, P = scene.NV, NR * K
         R = NV * P
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-        d_rgb, d_depth, d_weights = c(d_rgb), c(d_depth), c(d_weights)
-        if d_rgb is None:
-            d_rgb = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev)
-        d_rgbsigma = f(SB, NR, K, 4)
-        d_far = None
-        white = int(bool(ctx.renderer.white_bkgd))
-        if want["rays"]:
-            d_far = f(SB, NR)
-            check(L.diner_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
-                                                 _p(d_rgbsigma), _p(d_far), st), "diner_composite_backward_far")
-        else:
-            check(L.diner_composite_backward(_p(rays), _p(z), _p(rgbsigma), _p(d_rgb), _p(d_depth), _p(d_weights), SB * NR, K, white,
-                                             _p(d_rgbsigma), st), "diner_composite_backward")
+        d_rgbsigma, d_far = composite_backward(L, ctx, d_rgb, d_depth, d_weights, want["rays"], st)
+        cam_bufs = None
         if cam_any:
-            sh_poses, sh_focal, sh_c, sh_ishape, sh_depths = ctx.cam_shapes
-            z0 = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
-            g_rays = f(SB, NR, 8) if want["rays"] else None
-            g_poses = z0((SB, NV, 4, 4)) if want["poses"] else None
-            g_focal = f(SB, NV, 2) if want["focal"] else None
-            g_c = f(SB, NV, 2) if want["c"] else None
-            g_ishape = z0(2) if want["image_shape"] else None
-            g_depths = z0((SB, NV, scene.H, scene.W)) if want["depths"] else None
-            ws = f(int(L.diner_train_camera_workspace_floats(NR, K, NV)))
+            cam_bufs, ws = camera_grad_buffers(L, want, scene, SB, NR, K, dev)
         bicubic = isinstance(ctx.ix, int)
         ixp = C.byref(ctx.ix) if ctx.ix is not None and not bicubic else None
         lat_nhwc = ctx.keep[1]
@@ -361,27 +320,16 @@ class _RenderGenFn(torch.autograd.Function):
                 bwd, name = ((L.diner_train_point_inputs_backward_gen_bc, "diner_train_point_inputs_backward_gen_bc") if bicubic else
                              (L.diner_train_point_inputs_backward_gen, "diner_train_point_inputs_backward_gen"))
                 check(bwd(C.byref(scene), ctx.ix if bicubic else ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(d_in), ld_in, _p(d_zl),
-                          _p(d_far), _p(ws), _p(g_rays), _p(g_poses), _p(g_focal), _p(g_c), _p(g_ishape), _p(g_depths), st), name)
+                          _p(d_far), _p(ws), *map(_p, cam_bufs), st), name)
             if lay.nlz and bicubic:
                 check(L.diner_train_bicubic_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                       "diner_train_bicubic_scatter")
             elif lay.nlz:
                 check(L.diner_train_bilinear_scatter(_p(d_zl), _p(taps), P, scene.C, scene.h, scene.w, NV, sb, _p(d_lat_nhwc), st),
                       "diner_train_bilinear_scatter")
-        if ctx.lat_packed:   # the gradient in the latent's own (NHWC) strides: glue.assemble_latent's backward reads it as it is
-            d_lat = d_lat_nhwc.permute(0, 1, 4, 2, 3)
-        else:
-            d_lat = torch.empty(ctx.lat_shape, dtype=torch.float32, device=dev)
-            check(L.diner_train_nhwc_to_nchw(_p(d_lat_nhwc), SBl * NVl, Cl, hl, wl, _p(d_lat), st), "diner_train_nhwc_to_nchw")
+        d_lat = latent_grad_out(L, d_lat_nhwc, ctx.lat_shape, ctx.lat_packed, st)
         g[0] = g_in[:, :shape.d_in].contiguous()
-        cam = (None,) * 6
-        if cam_any:
-            cam = (g_rays,
-                   None if g_poses is None else g_poses[..., :sh_poses[-2], :].reshape(sh_poses),   # ([.., 3, 4] poses: rows 0..2)
-                   None if g_focal is None else g_focal.reshape(sh_focal),
-                   None if g_c is None else g_c.reshape(sh_c),
-                   None if g_ishape is None else g_ishape.reshape(sh_ishape),
-                   None if g_depths is None else g_depths.reshape(sh_depths))
+        cam = camera_grads_out(cam_bufs, ctx.cam_shapes)
         return (None, None, None, None, None, None, None, None, cam[0], d_lat) + cam[1:] + tuple(g)
 
 
@@ -395,7 +343,6 @@ def render_with_grad(renderer, model, rays, z, scene, shape, keep=None, f16=Fals
     # the encoder's lookup mode (None: bilinear / border; an int: bicubic with that padding, renderer.bicubic_index)
     pad = renderer._bicubic_pad(model)
     ix = int(pad) if pad is not None else renderer._latent_index(model)
-    cams = camera_leaves(model, rays)
-    f32 = [t.to(torch.float32).contiguous() for t in cams]   # graph-preserving: the gradient flows back to the caller's dtype
+    cams, f32 = camera_inputs(model, rays)
     return _RenderGenFn.apply(renderer, scene, ix, keep, cams, shape, bool(f16), z, *f32[:1], model.encoder.latent, *f32[1:], *params)
 

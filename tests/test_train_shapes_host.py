@@ -221,3 +221,14 @@ def test_fixture_digests_match_the_generator(name):
     assert data["z_fill"].shape == (1, NR, K) and data["rgb"].shape == (1, NR, 3)
     assert all(f"g_norm/{k}" in data.files for k in w)
     assert ("grad/rays" in data.files) == cfg["leaves"]
+
+
+SHARED_SCAFFOLDING = ["_p", "_st", "prepare_latent", "remember_versions", "check_versions", "composite_backward", "camera_grad_buffers",
+                      "latent_grad_out", "camera_grads_out", "camera_leaves", "camera_inputs"]
+
+
+def test_both_autograd_functions_share_one_scaffolding():
+    """training_gen takes the pieces around the layer schedule from training (the same function objects): no second copy to keep in step."""
+    from diner_amd import training, training_gen
+    for name in SHARED_SCAFFOLDING:
+        assert getattr(training_gen, name) is getattr(training, name), name
