@@ -20,6 +20,8 @@ N_BLOCKS, COMBINE = 5, 3
 # the ABI version THIS binding (the argument lists in SYMBOLS below) is written against = DINER_ABI_VERSION of include/diner_hip.h
 ABI_VERSION = 3
 PRECISIONS = {"fp32": 0, "f16x3": 1}
+# DINER_ROUND_* of include/diner_hip.h (diner_frames_u8)
+ROUNDINGS = {"save_image": 0, "video": 1}
 # DINER_ACT_* of include/diner_hip.h (diner_train_gemm_act)
 ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
 
@@ -84,7 +86,7 @@ INDEX_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
 
 
 # every symbol include/diner_hip.h declares: name -> (restype, argtypes)
-_I64, _I32, _U64, _P, _F32 = C.c_int64, C.c_int32, C.c_uint64, C.c_void_p, C.c_float
+_I64, _I32, _U64, _P, _F32, _F64 = C.c_int64, C.c_int32, C.c_uint64, C.c_void_p, C.c_float, C.c_double
 SYMBOLS = {
     "diner_last_error": (C.c_char_p, []),
     "diner_version": (C.c_int, []),
@@ -218,6 +220,14 @@ SYMBOLS = {
     "diner_photo_loss_workspace_floats": (_I64, [_I32, _I32, _I32, _I32]),
     "diner_photo_loss": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "diner_photo_loss_backward": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    # frame output and image scores: depth range, colour map, frames as bytes, l1 / l2 / psnr / ssim (csrc/frame_out.hip; the ABI version
+    # stays 3: new entry points only)
+    "diner_depth_range_workspace_floats": (_I64, [_I64, _I32, _I32]),
+    "diner_depth_range": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
+    "diner_depth_cmap": (C.c_int, [_P, _I64, _I32, _I32, _P, _F64, _F64, _I32, _I32, _P, _I32, _P, _P]),
+    "diner_frames_u8": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _F64, _F64, _I32, _I32, _P, _I32, _P, _P, _P]),
+    "diner_image_scores_workspace_floats": (_I64, [_I64, _I32, _I32]),
+    "diner_image_scores": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P]),
     # lin_z hoisted into per-texel maps on the shape-general kernels: the *_gen_ix argument lists, then precision (PRECISIONS), the bicubic
     # padding (-1: not bicubic, else INDEX_PADDING) and the maps of diner_pack_linz_maps_gen (the ABI version stays 3: new entry points only)
     "diner_linz_maps_gen_floats": (_I64, [C.POINTER(DinerScene), C.POINTER(DinerMlpShape)]),

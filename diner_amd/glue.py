@@ -13,7 +13,10 @@ images normalised and replicate-padded, plus the positional encoding of the padd
 and both around the model's own CNN trunk: :func:`encode`, with ``PixelNeRF.encode``'s signature (reference
 ``src/models/pixelnerf.py:35-53`` + ``SpatialEncoder.forward``, ``src/models/image_encoder.py:206-272``);
 and a training step around the renderer: :func:`gen_rays_at` (gen_rays at the selected pixels only), :func:`photo_loss` (ground-truth
-gather, MSE and antibias loss) and :func:`calc_losses`, which assembles ``DINER.calc_losses`` (reference ``src/models/diner.py:217-290``).
+gather, MSE and antibias loss) and :func:`calc_losses`, which assembles ``DINER.calc_losses`` (reference ``src/models/diner.py:217-290``);
+and the way from a rendered frame to its files and scores: :func:`torch_cmap` (reference ``src/util/torch_helpers.py:43-76``),
+:func:`frames_u8` (the quantisation of ``save_image`` and ``save_torch_video``, ``src/models/diner.py:129-133, :209-214``) and
+:func:`image_scores` (l1, l2, psnr, ssim of ``evaluate_folder``, ``src/evaluation/eval_suite.py:63-68``).
 """
 from __future__ import annotations
 
@@ -657,3 +660,190 @@ def calc_losses(nerf, renderer, batch, znear, zfar, pix_idcs, patch=None, w_vgg=
     else:
         loss_antibias = 0.
     return dict(rgb_fine=loss_fine, vgg_fine=loss_vgg, antibias=loss_antibias, total=total)
+
+
+# ---- frame output and image scores (csrc/frame_out.hip) --------------------------------------------------------------------------------
+_tables = {}       # (key, device, kind) -> the float64 / quantised uint8 table on the device; "viridis" -> the shipped table on the host
+
+
+def _cmap_table(cmap):
+    """(cache key or None, float64 CPU tensor [nc + 3, 3]) of a colour map: the shipped viridis, a [nc + 3, 3] tensor, or any other
+    name through matplotlib"""
+    if isinstance(cmap, torch.Tensor):
+        if cmap.dim() != 2 or cmap.shape[1] != 3 or cmap.shape[0] < 4 or cmap.dtype != torch.float64:
+            raise ValueError("a colour table must be a float64 tensor [N + 3, 3] (N colours, then under, over, bad)")
+        return None, cmap.detach()
+    if cmap == "viridis":
+        if "viridis" not in _tables:
+            from .viridis_lut import VIRIDIS_LUT   # matplotlib's 259-row table (256 colours, under, over, bad) as a literal
+            _tables["viridis"] = torch.tensor(VIRIDIS_LUT, dtype=torch.float64)
+        return "viridis", _tables["viridis"]
+    try:
+        import matplotlib
+    except ImportError as e:
+        raise ImportError(f"the colour map {cmap!r} is looked up through matplotlib, which is not importable here (only 'viridis' ships "
+                          "with diner_amd); pass the [N + 3, 3] float64 table instead") from e
+    import numpy as np
+    cm = matplotlib.colormaps[cmap]
+    cm._init()                                          # fills _lut [N + 3, 4]: the colours, under, over, bad
+    return str(cmap), torch.from_numpy(np.ascontiguousarray(cm._lut[:, :3], dtype=np.float64))
+
+
+def _quantise_table(table, rounding):
+    """the float64 table as bytes by diner_frames_u8's rule for ``rounding``, in double (what the reference does to the float64 colours)"""
+    if rounding == "save_image":
+        v = table * 255.0 + 0.5
+    else:
+        v = table * 255.0
+    return torch.nan_to_num(v, nan=0.0).clamp(0.0, 255.0).to(torch.uint8)       # the cast truncates
+
+
+def _device_table(cmap, dev, rounding=None):
+    key, table = _cmap_table(cmap)
+    slot = (key, dev, rounding)
+    if key is not None and slot in _tables:
+        return _tables[slot]
+    t = (table if rounding is None else _quantise_table(table, rounding)).to(dev).contiguous()
+    if key is not None:
+        _tables[slot] = t
+    return t
+
+
+def _depth32(x, who):
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"{who}: a float32 (or half / bfloat16) tensor is needed: the kernels read fp32, and a float64 input would be rounded")
+    if not x.is_cuda:
+        raise RuntimeError(f"diner_amd.glue.{who} runs on the GPU only")
+    return _f(x)
+
+
+def depth_range(depth):
+    """depth [N,1,H,W] (or [N,H,W]) -> float64 [N,2] on the device: each image's (min, max), exact; a NaN anywhere in an image makes both
+    NaN, as ``np.min`` / ``np.max`` do (reference src/util/torch_helpers.py:64-65).  No host synchronisation."""
+    d = _depth32(depth, "depth_range")
+    if d.dim() == 4 and d.shape[1] == 1:
+        d = d[:, 0]
+    if d.dim() != 3 or d.numel() == 0:
+        raise ValueError("depth_range: depth must be [N, 1, H, W] or [N, H, W] with at least one pixel")
+    N, H, W = d.shape
+    L = _lib.lib()
+    n = int(L.diner_depth_range_workspace_floats(N, H, W))
+    if n < 0:
+        raise ValueError(f"depth_range: bad sizes N={N}, H={H}, W={W}")
+    ws = torch.empty(n, dtype=torch.float32, device=d.device)
+    out = torch.empty((N, 2), dtype=torch.float64, device=d.device)
+    check(L.diner_depth_range(d.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(), _st(d.device)), "diner_depth_range")
+    return out
+
+
+def _limits(d, vmin, vmax):
+    """(range pointer or None, vmin, vmax, has_vmin, has_vmax, keep-alive): a limit of None or 0 is taken per image from the data -- the
+    reference's ``vmin if vmin else np.min(...)`` (src/util/torch_helpers.py:64-65), which treats a given 0 as absent"""
+    has_lo, has_hi = bool(vmin), bool(vmax)
+    rng = None if has_lo and has_hi else depth_range(d)
+    return (None if rng is None else rng.data_ptr(), float(vmin) if has_lo else 0.0, float(vmax) if has_hi else 0.0, int(has_lo), int(has_hi),
+            rng)
+
+
+def torch_cmap(x, cmap="viridis", vmin=None, vmax=None):
+    """Drop-in for the reference's ``torch_cmap`` (src/util/torch_helpers.py:43-76) that stays on the device: x (B,1,H,W), (1,H,W) or (H,W)
+    -> the same shape with 3 channels, float64, on ``x``'s device, bit-equal to the reference (numpy in float64 and matplotlib 3.10's
+    ``Colormap._get_rgba_and_mask``; csrc/frame_out.hip states the index rule).  An image whose range is flat is black (0 / 0 selects the
+    "bad" colour), as in the reference.
+
+    ``cmap``: "viridis" (the table ships with the package), any other matplotlib name (looked up lazily; ``ImportError`` without
+    matplotlib), or a float64 tensor [N + 3, 3].  ``vmin`` / ``vmax``: one scalar each, or None for the image's own minimum / maximum
+    (computed on the device, no host synchronisation).  A ``vmin`` or ``vmax`` of 0 counts as absent: that is the reference's
+    ``vmin if vmin else ...``.  Per-image arrays of limits are not supported."""
+    d = _depth32(x, "torch_cmap")
+    shape = x.shape
+    if d.dim() < 2 or d.dim() > 4:
+        raise ValueError("torch_cmap: x must be (B,1,H,W), (1,H,W) or (H,W)")
+    d = d.reshape((1,) * (4 - d.dim()) + tuple(shape))
+    if d.shape[1] != 1 or d.numel() == 0:
+        raise ValueError("torch_cmap: x must have one channel and at least one pixel")
+    N, _, H, W = d.shape
+    table = _device_table(cmap, d.device)
+    rng, lo, hi, has_lo, has_hi, _keep = _limits(d, vmin, vmax)
+    out = torch.empty((N, 3, H, W), dtype=torch.float64, device=d.device)
+    check(_lib.lib().diner_depth_cmap(d.data_ptr(), N, H, W, rng, lo, hi, has_lo, has_hi, table.data_ptr(), table.shape[0] - 3,
+                                      out.data_ptr(), _st(d.device)), "diner_depth_cmap")
+    return out.reshape(list(shape[:-3]) + [3] + list(shape[-2:]))
+
+
+def frames_u8(rgb, depth=None, *, rounding="save_image", stacked=False, cmap="viridis", vmin=None, vmax=None):
+    """Frames as the image / video writers take them, in one kernel: rgb [..,3,H,W] (and depth [..,1,H,W], coloured as :func:`torch_cmap`
+    does) -> uint8 HWC on the device.  Returns ``rgb_u8`` [..,H,W,3]; with a depth ``(rgb_u8, depth_u8)``, or, with ``stacked=True``, one
+    tensor [..,2H,W,3] with the colour above the depth -- ``cat((rgbs, depths), dim=-2)`` of ``create_cam_sweep`` (reference
+    src/models/diner.py:209).  ``rounding``:
+
+    * ``"save_image"``: ``(uint8) clamp(x * 255 + 0.5, 0, 255)``, torchvision's ``save_image`` (diner.py:129-133);
+    * ``"video"``: ``(uint8) (double(x) * 255)``, ``save_torch_video`` (src/util/torch_helpers.py:91).
+
+    A value outside the byte range saturates and NaN gives 0 (numpy's cast is undefined there).  The depth's colours are quantised from
+    the float64 table by the same rule, so they equal the reference's bytes for its float64 colour map.  Ground-truth and source images
+    go through the same function; quantising ``gt`` here gives the bytes the reference scores after its PNG round trip (PNG is lossless)."""
+    if rounding not in _lib.ROUNDINGS:
+        raise ValueError(f"frames_u8: rounding must be one of {sorted(_lib.ROUNDINGS)}")
+    c = _depth32(rgb, "frames_u8")
+    if c.dim() < 3 or c.shape[-3] != 3 or c.numel() == 0:
+        raise ValueError("frames_u8: rgb must be [.., 3, H, W] with at least one pixel")
+    lead, (H, W) = tuple(c.shape[:-3]), c.shape[-2:]
+    c = c.reshape(-1, 3, H, W)
+    N, dev = c.shape[0], c.device
+    L = _lib.lib()
+    if depth is None:
+        if stacked:
+            raise ValueError("frames_u8: stacked=True needs a depth")
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+        check(L.diner_frames_u8(c.data_ptr(), None, N, H, W, _lib.ROUNDINGS[rounding], 0, None, 0.0, 0.0, 0, 0, None, 0, out.data_ptr(), None,
+                                _st(dev)), "diner_frames_u8")
+        return out.reshape(lead + (H, W, 3))
+    d = _depth32(depth, "frames_u8")
+    if d.dim() < 3 or tuple(d.shape[-3:]) != (1, H, W) or d.numel() != N * H * W:
+        raise ValueError(f"frames_u8: depth must be [.., 1, {H}, {W}] for the same {N} frames")
+    d = d.reshape(N, 1, H, W)
+    table = _device_table(cmap, dev, rounding)
+    rng, lo, hi, has_lo, has_hi, _keep = _limits(d, vmin, vmax)
+    out = torch.empty((N, 2 * H if stacked else H, W, 3), dtype=torch.uint8, device=dev)
+    out_d = None if stacked else torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+    check(L.diner_frames_u8(c.data_ptr(), d.data_ptr(), N, H, W, _lib.ROUNDINGS[rounding], int(stacked), rng, lo, hi, has_lo, has_hi,
+                            table.data_ptr(), table.shape[0] - 3, out.data_ptr(), None if stacked else out_d.data_ptr(), _st(dev)),
+          "diner_frames_u8")
+    if stacked:
+        return out.reshape(lead + (2 * H, W, 3))
+    return out.reshape(lead + (H, W, 3)), out_d.reshape(lead + (H, W, 3))
+
+
+def image_scores(pred_u8, gt_u8):
+    """The scores ``evaluate_folder`` takes from a PNG pair (reference src/evaluation/eval_suite.py:63-68), for uint8 HWC images
+    [..,H,W,3] on the device (what :func:`frames_u8` returns): a dict ``ssim, psnr, l2, l1`` of float64 tensors [N] (N = the leading
+    dimensions flattened) on the device, without a host synchronisation.  ``ssim`` is skimage's ``structural_similarity(pred, gt,
+    channel_axis=-1, data_range=1)`` with its defaults (uniform 7 x 7 window, sample covariance), ``psnr`` its
+    ``peak_signal_noise_ratio`` (+inf for equal images), ``l2`` / ``l1`` the mean squared / absolute difference of ``uint8 / 255``.
+    The sums are exact integers and each window's value is formed in float64, so the results differ from the reference's float32
+    evaluation by that evaluation's own rounding.  Two calls agree bit for bit.  LPIPS stays on PyTorch."""
+    for t in (pred_u8, gt_u8):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError("image_scores takes uint8 HWC images: quantise float frames with glue.frames_u8 first")
+    if pred_u8.shape != gt_u8.shape:
+        raise ValueError(f"image_scores: the shapes differ: {tuple(pred_u8.shape)} and {tuple(gt_u8.shape)}")
+    if pred_u8.dim() < 3 or pred_u8.shape[-1] != 3:
+        raise ValueError("image_scores: images must be [.., H, W, 3]")
+    H, W = pred_u8.shape[-3:-1]
+    if H < 7 or W < 7:
+        raise ValueError(f"image_scores: a {H} x {W} image is smaller than the 7 x 7 window")
+    if not (pred_u8.is_cuda and gt_u8.is_cuda):
+        raise RuntimeError("diner_amd.glue.image_scores runs on the GPU only")
+    p, g = pred_u8.detach().reshape(-1, H, W, 3).contiguous(), gt_u8.detach().reshape(-1, H, W, 3).contiguous()
+    N, dev = p.shape[0], p.device
+    if N == 0:
+        raise ValueError("image_scores: no images")
+    L = _lib.lib()
+    n = int(L.diner_image_scores_workspace_floats(N, H, W))
+    if n < 0:
+        raise ValueError(f"image_scores: bad sizes N={N}, H={H}, W={W}")
+    ws = torch.empty(n // 2, dtype=torch.float64, device=dev)
+    out = torch.empty((4, N), dtype=torch.float64, device=dev)
+    check(L.diner_image_scores(p.data_ptr(), g.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(), _st(dev)), "diner_image_scores")
+    return dict(ssim=out[0], psnr=out[1], l2=out[2], l1=out[3])

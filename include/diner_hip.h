@@ -723,6 +723,51 @@ int diner_train_gemm_act_f16x3_w(const float *A, int64_t sam, const void *Bhi, c
                                  int64_t lds, float *C, int64_t ldc, int64_t M, int32_t N, int32_t K, int32_t act_a, int32_t act_s,
                                  float beta, int32_t accumulate, const void *amax_a, int32_t exp_a, int32_t exp_b, void *stream);
 
+/* ---- frame output and image scores (frame_out.hip; glue.torch_cmap, glue.frames_u8, glue.image_scores): what the reference's
+ * evaluation path does with a rendered frame -- create_prediction_folder (src/models/diner.py:100-136), create_cam_sweep (:138-215) and
+ * the scoring loop of evaluate_folder (src/evaluation/eval_suite.py:62-73) -- without leaving the device.  New symbols only:
+ * DINER_ABI_VERSION stays 3.  Every function: N images of H x W pixels, contiguous; before any launch DINER_E_INVALID for a NULL
+ * pointer or a non-positive size, DINER_E_UNSUPPORTED for H W >= 2^31 or N > 65535.  None synchronises with the host. ------------- */
+/* np.min / np.max per image (src/util/torch_helpers.py:64-65): depth [N,1,H,W] fp32 -> range_out [N,2] = (min, max) as doubles, exact;
+ * a NaN anywhere in an image makes both of its values NaN.  Two stages: (min, max) per workgroup into `workspace`
+ * (diner_depth_range_workspace_floats floats; -1 for bad sizes), then one thread per image walks them in block order. */
+int64_t diner_depth_range_workspace_floats(int64_t N, int32_t H, int32_t W);
+int diner_depth_range(const float *depth, int64_t N, int32_t H, int32_t W, double *range_out, float *workspace, void *stream);
+/* torch_cmap (src/util/torch_helpers.py:43-76): out [N,3,H,W] float64 = rows of `table` [ncolors + 3, 3] float64 (the colours, then
+ * under, over, bad: matplotlib's Colormap._lut without alpha), picked in double as numpy and matplotlib 3.10
+ * (Colormap._get_rgba_and_mask) do: t = ((double) d - vmin) / (vmax - vmin), xa = t ncolors, xa == ncolors counts as ncolors - 1,
+ * row ncolors if xa < 0, else ncolors + 1 if xa >= ncolors, else ncolors + 2 if xa is NaN, else (int) xa.  A flat image gives 0 / 0 =
+ * NaN: the bad row (black), as the reference does.  vmin / vmax: the scalar when has_vmin / has_vmax, else image n's range[n][0] /
+ * range[n][1] (diner_depth_range's output, read on the device; range may be NULL when both are given). */
+int diner_depth_cmap(const float *depth, int64_t N, int32_t H, int32_t W, const double *range, double vmin, double vmax, int32_t has_vmin,
+                     int32_t has_vmax, const double *table, int32_t ncolors, double *out, void *stream);
+/* Frames as bytes in one pass: rgb [N,3,H,W] fp32 and optionally depth [N,1,H,W] fp32 (NULL: none) -> HWC uint8.  stacked = 0:
+ * rgb_out [N,H,W,3] and depth_out [N,H,W,3]; stacked = 1 (needs a depth; depth_out is not read): rgb_out [N,2H,W,3] with the colour
+ * above the depth, create_cam_sweep's cat((rgbs, depths), dim=-2) (diner.py:209).  rounding:
+ *   DINER_ROUND_SAVE_IMAGE  (uint8) clamp(x 255 + 0.5, 0, 255), multiply and add two fp32 roundings (torchvision save_image, diner.py:129-133)
+ *   DINER_ROUND_VIDEO       (uint8) ((double) x 255.0)   (save_torch_video, torch_helpers.py:91, on frames the float64 colour map promoted)
+ * Our own definition where numpy's / torch's cast is undefined: the value saturates to [0, 255] and NaN gives 0.
+ * The depth half is the byte row table_u8 [ncolors + 3, 3] of diner_depth_cmap's index (vmin / vmax / range as there): the caller
+ * quantises the float64 table once by the same rule, in double.  16-byte loads and 12 bytes stored per lane when W % 4 == 0 and the
+ * pointers are aligned (inputs 16, outputs 4 bytes), else one pixel per lane. */
+#define DINER_ROUND_SAVE_IMAGE 0
+#define DINER_ROUND_VIDEO 1
+int diner_frames_u8(const float *rgb, const float *depth, int64_t N, int32_t H, int32_t W, int32_t rounding, int32_t stacked,
+                    const double *range, double vmin, double vmax, int32_t has_vmin, int32_t has_vmax, const uint8_t *table_u8,
+                    int32_t ncolors, uint8_t *rgb_out, uint8_t *depth_out, void *stream);
+/* The scores of evaluate_folder (eval_suite.py:63-68) for N pairs of HWC uint8 images [N,H,W,3], as it computes them from the PNG pair
+ * (uint8 / 255, data_range = 1, channel_axis = -1): scores_out [4,N] doubles = ssim, psnr, l2, l1.
+ *   l1 = sum |d| / (255 3 H W), l2 = sum d^2 / (255^2 3 H W), psnr = 10 log10(1 / l2) (+inf for equal images);
+ *   ssim: skimage's structural_similarity with its defaults -- uniform 7 x 7 window, sample covariance (cov_norm = 49 / 48), K1 = 0.01,
+ *   K2 = 0.03, S = (2 mx my + C1)(2 vxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)), the mean over the (H - 6)(W - 6) whole windows
+ *   (its crop by 3) per channel, then the mean of the three channel means.
+ * All sums are exact integers; each window's S is formed in fp64 from them (equal images give exactly 1).  One fp64 partial set per
+ * workgroup in `workspace` (diner_image_scores_workspace_floats floats, 8-byte aligned; -1 for bad sizes), added in block order: no
+ * atomics, two runs agree bit for bit.  H < 7 or W < 7: DINER_E_INVALID (skimage raises ValueError there). */
+int64_t diner_image_scores_workspace_floats(int64_t N, int32_t H, int32_t W);
+int diner_image_scores(const uint8_t *pred, const uint8_t *gt, int64_t N, int32_t H, int32_t W, double *scores_out, float *workspace,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
