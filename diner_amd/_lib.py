@@ -239,6 +239,12 @@ SYMBOLS = {
     "diner_render_image_gen_lz": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerMlpShape), _P,
                                             C.POINTER(DinerTargetCam), C.POINTER(DinerSamplerCfg), _I32, _U64, _P, _P, _P, _P, _P, _P, _P,
                                             _I32, _I32, _P]),
+    # rendering inside a scene bounding box: hit pixels with the box's near / far, the compact rays, the frame from the compact results
+    # (csrc/ray_box.hip; the ABI version stays 3: new entry points only)
+    "diner_ray_box_select_workspace_floats": (_I64, [_I32, _I32, _I32]),
+    "diner_ray_box_select": (C.c_int, [C.POINTER(DinerTargetCam), _I32, _P, _F32, _F32, _P, _P, _P, _P, _P, _P]),
+    "diner_gen_rays_box": (C.c_int, [C.POINTER(DinerTargetCam), _I32, _P, _F32, _F32, _P, _P, C.POINTER(C.c_int32), _I32, _P, _P]),
+    "diner_frame_from_hits": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

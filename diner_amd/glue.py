@@ -16,7 +16,9 @@ and a training step around the renderer: :func:`gen_rays_at` (gen_rays at the se
 gather, MSE and antibias loss) and :func:`calc_losses`, which assembles ``DINER.calc_losses`` (reference ``src/models/diner.py:217-290``);
 and the way from a rendered frame to its files and scores: :func:`torch_cmap` (reference ``src/util/torch_helpers.py:43-76``),
 :func:`frames_u8` (the quantisation of ``save_image`` and ``save_torch_video``, ``src/models/diner.py:129-133, :209-214``) and
-:func:`image_scores` (l1, l2, psnr, ssim of ``evaluate_folder``, ``src/evaluation/eval_suite.py:63-68``).
+:func:`image_scores` (l1, l2, psnr, ssim of ``evaluate_folder``, ``src/evaluation/eval_suite.py:63-68``);
+and rendering inside a scene bounding box: :func:`ray_box` (``FacescapeDataSet.get_near_far`` + ``get_mask_at_box``,
+``src/data/facescape.py:128-185``, on the project's rays), :func:`box_rays` (the hit pixels' rays, compacted) and :func:`frame_from_hits`.
 """
 from __future__ import annotations
 
@@ -847,3 +849,125 @@ def image_scores(pred_u8, gt_u8):
     out = torch.empty((4, N), dtype=torch.float64, device=dev)
     check(L.diner_image_scores(p.data_ptr(), g.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(), _st(dev)), "diner_image_scores")
     return dict(ssim=out[0], psnr=out[1], l2=out[2], l1=out[3])
+
+
+# ---- rendering inside a scene bounding box (csrc/ray_box.hip) ----------------------------------------------------------------------------
+BOX_OFFSET = (-0.01, 0.01)    # get_near_far's boffset (reference src/data/facescape.py:153)
+
+
+def _box_args(extrinsics, intrinsics, W, H, z_near, z_far, bounds, box_offset, who):
+    """the cameras as a DinerTargetCam, the bounds as fp32 [SB,2,3] on the cameras' device, the two offsets; + what keeps them alive"""
+    if not isinstance(extrinsics, torch.Tensor) or not extrinsics.is_cuda:
+        raise RuntimeError(f"diner_amd.glue.{who} runs on the GPU only")
+    if extrinsics.dim() != 3 or tuple(extrinsics.shape[1:]) != (4, 4) or tuple(intrinsics.shape) != (extrinsics.shape[0], 3, 3):
+        raise ValueError(f"{who}: extrinsics must be [SB,4,4] and intrinsics [SB,3,3]")
+    H, W = int(H), int(W)
+    if H < 0 or W < 0:
+        raise ValueError(f"{who}: negative image size H={H}, W={W}")
+    dev, SB = extrinsics.device, extrinsics.shape[0]
+    e, k = _f(extrinsics), _f(intrinsics).to(dev)
+    zn, zf = _per_camera(z_near, SB, dev), _per_camera(z_far, SB, dev)
+    if not isinstance(bounds, torch.Tensor):
+        import numpy as np
+        bounds = torch.from_numpy(np.array(bounds, dtype=np.float32))       # (a copy: the array may be read-only)
+    b = bounds.detach().to(device=dev, dtype=torch.float32)
+    if tuple(b.shape) == (2, 3):
+        b = b.expand(SB, 2, 3)
+    if tuple(b.shape) != (SB, 2, 3):
+        raise ValueError(f"{who}: bounds must be [SB = {SB}, 2, 3] or [2, 3] (min corner, max corner), not {tuple(b.shape)}")
+    b = b.contiguous()
+    lo, hi = (float(v) for v in box_offset)
+    cam = _lib.DinerTargetCam()
+    cam.extrinsics, cam.intrinsics, cam.z_near, cam.z_far, cam.H, cam.W = e.data_ptr(), k.data_ptr(), zn.data_ptr(), zf.data_ptr(), H, W
+    return cam, b, lo, hi, (e, k, zn, zf)
+
+
+def _ray_box_select(cam, SB, b, lo, hi, dev, want_near_far):
+    """-> near_far [SB,H W,2] or None, idx [SB,H W], slot [SB,H W], count [SB] (int32, on the device)"""
+    L = _lib.lib()
+    npix = cam.H * cam.W
+    n = int(L.diner_ray_box_select_workspace_floats(SB, cam.H, cam.W))
+    if n < 0:
+        raise ValueError(f"ray_box: bad sizes SB={SB}, H={cam.H}, W={cam.W}")
+    ws = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    near_far = torch.empty((SB, npix, 2), dtype=torch.float32, device=dev) if want_near_far else None
+    idx = torch.empty((SB, npix), dtype=torch.int32, device=dev)
+    slot = torch.empty((SB, npix), dtype=torch.int32, device=dev)
+    count = torch.zeros(SB, dtype=torch.int32, device=dev)
+    check(L.diner_ray_box_select(C.byref(cam), SB, b.data_ptr(), lo, hi, None if near_far is None else near_far.data_ptr(), idx.data_ptr(),
+                                 slot.data_ptr(), count.data_ptr(), ws.data_ptr(), _st(dev)), "diner_ray_box_select")
+    return near_far, idx, slot, count
+
+
+@torch.no_grad()
+def ray_box(extrinsics, intrinsics, W, H, z_near, z_far, bounds, box_offset=BOX_OFFSET):
+    """The device form of ``FacescapeDataSet.get_near_far`` + ``get_mask_at_box`` (reference src/data/facescape.py:128-185) on the project's
+    rays (:func:`gen_rays`: pixel centres, unit directions): extrinsics [SB,4,4], intrinsics [SB,3,3], z_near / z_far [SB] (or one value),
+    ``bounds`` [SB,2,3] or [2,3] (min corner, max corner; a tensor on any device or an array, e.g. ``load_face_bounds``' result)
+    -> ``near`` [SB,H,W], ``far`` [SB,H,W] (fp32), ``mask`` [SB,H,W] (bool).  The box is ``bounds[0] + box_offset[0]`` ..
+    ``bounds[1] + box_offset[1]``; near / far are the ray's signed entry / exit parameters clamped to [z_near, z_far]; a pixel whose ray
+    misses the box holds z_near, z_far.  Two deliberate differences from ``get_near_far``: a box behind the camera is a miss (the
+    reference's unsigned distances mirror it to the front), and a camera inside the box gets ``near = z_near`` (the reference takes the
+    nearer face, which may be the one behind the camera).  Carries no gradient: near and far are constants of any later backward."""
+    cam, b, lo, hi, _keep = _box_args(extrinsics, intrinsics, W, H, z_near, z_far, bounds, box_offset, "ray_box")
+    SB, dev = b.shape[0], b.device
+    near_far, _, slot, _ = _ray_box_select(cam, SB, b, lo, hi, dev, True)
+    near_far = near_far.view(SB, cam.H, cam.W, 2)
+    return near_far[..., 0], near_far[..., 1], (slot >= 0).view(SB, cam.H, cam.W)
+
+
+@torch.no_grad()
+def box_rays(extrinsics, intrinsics, W, H, z_near, z_far, bounds, box_offset=BOX_OFFSET):
+    """The rays of :func:`ray_box`'s hit pixels only, compacted in pixel order (the arguments are :func:`ray_box`'s)
+    -> ``(rays [SB,B,8], idx [SB,B], slot [SB,H*W], counts [SB])`` with ``B = counts.max()``:
+
+    * ``rays[sb, j]`` for ``j < counts[sb]``: :func:`gen_rays`' ray at pixel ``idx[sb, j]`` (origin and direction bit for bit) with
+      components 6, 7 = the box's near, far of that ray; from ``counts[sb]`` on: padding that repeats the scene's last hit (a scene
+      without hits repeats pixel 0 with z_near, z_far) -- render it, never read its results;
+    * ``idx`` (int32): the hit pixels ``x + y * W`` ascending, -1 in the padding; ``slot`` (int32): the rank of each pixel among its
+      scene's hits or -1, what :func:`frame_from_hits` gathers through; ``counts`` (int32, on the device).
+
+    Reads the counts on the host: one synchronisation of SB ints.  ``B = 0`` gives empty tensors and no second launch.  ``rays`` can be
+    fed to ``renderer.forward`` like any other rays, under autograd too (near is a constant there, far enters through the last
+    sample's interval only)."""
+    cam, b, lo, hi, _keep = _box_args(extrinsics, intrinsics, W, H, z_near, z_far, bounds, box_offset, "box_rays")
+    SB, dev = b.shape[0], b.device
+    _, idx, slot, count = _ray_box_select(cam, SB, b, lo, hi, dev, False)
+    host = count.cpu()                                       # the one synchronisation
+    B = int(host.max()) if SB else 0
+    rays = torch.empty((SB, B, 8), dtype=torch.float32, device=dev)
+    if B > 0:
+        host_c = (C.c_int32 * SB)(*host.tolist())
+        check(_lib.lib().diner_gen_rays_box(C.byref(cam), SB, b.data_ptr(), lo, hi, idx.data_ptr(), count.data_ptr(), host_c, B,
+                                            rays.data_ptr(), _st(dev)), "diner_gen_rays_box")
+    return rays, idx[:, :B], slot, count
+
+
+@torch.no_grad()
+def frame_from_hits(rgb_c, depth_c, slot, H, W, white_bkgd, return_mask=False):
+    """The frame of a boxed render from its compact results: rgb_c [SB,B,3], depth_c [SB,B] (what ``renderer.forward`` returned for
+    :func:`box_rays`' rays), ``slot`` [SB,H*W] (:func:`box_rays`) -> ``rgb`` [SB,3,H,W], ``depth`` [SB,1,H,W] in the reference's image
+    layout (views of pixel-major buffers, as ``render_image`` returns them).  A missed pixel is the background: 1 with ``white_bkgd``
+    else 0, depth 0.  One thread per pixel gathers: every output element is written.  ``return_mask=True`` adds ``mask`` [SB,1,H,W]
+    (bool)."""
+    if not isinstance(slot, torch.Tensor) or not slot.is_cuda:
+        raise RuntimeError("diner_amd.glue.frame_from_hits runs on the GPU only")
+    H, W = int(H), int(W)
+    if slot.dim() != 2 or slot.dtype != torch.int32 or slot.shape[1] != H * W:
+        raise ValueError(f"frame_from_hits: slot must be int32 [SB, H*W = {H * W}]")
+    SB, dev = slot.shape[0], slot.device
+    c, d = _f(rgb_c), _f(depth_c)
+    if c.dim() != 3 or c.shape[0] != SB or c.shape[2] != 3 or tuple(d.shape) != tuple(c.shape[:2]):
+        raise ValueError(f"frame_from_hits: rgb_c must be [SB = {SB}, B, 3] and depth_c [SB, B]")
+    B = c.shape[1]
+    s = slot.contiguous()
+    rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
+    mask = torch.empty((SB, H * W), dtype=torch.uint8, device=dev) if return_mask else None
+    check(_lib.lib().diner_frame_from_hits(c.data_ptr() if B else None, d.data_ptr() if B else None, s.data_ptr(), SB, B, H, W,
+                                           int(bool(white_bkgd)), rgb.data_ptr(), depth.data_ptr(),
+                                           None if mask is None else mask.data_ptr(), _st(dev)), "diner_frame_from_hits")
+    out = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2), depth.view(SB, H, W, 1).permute(0, 3, 1, 2)
+    if return_mask:
+        return out + (mask.view(SB, 1, H, W).bool(),)
+    return out

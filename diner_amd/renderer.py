@@ -242,6 +242,7 @@ class NeRFRendererDGS(torch.nn.Module):
         # "points_mlp", "points_mlp_gen" or "points_mlp_gen_f16", with "_lz" appended when linz_maps_any_shape's maps were read), `last_binding` = "torch_ops" or "ctypes", `effective_precision` = the arithmetic that ran.
         self._mlp_gen_key = self._mlp_gen_pack = None
         self.last_route = self.last_binding = self.effective_precision = None
+        self.last_box_hits = None     # after render_image(bounds=...): the number of rays rendered per scene (a list of ints)
         self._warned_precision = False
         self._force_gen = False      # test-only: run the standard shape on the shape-general kernel as well
         # Training (autograd through forward() / composite()) of a model of any shape of the shape-general envelope: the exact fp32
@@ -993,7 +994,8 @@ class NeRFRendererDGS(torch.nn.Module):
         self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
-    def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False):
+    def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False, bounds=None,
+                     box_offset=(-0.01, 0.01), return_mask=False):
         """The render half of ``DINER.predict_imgs_from_batch`` (reference src/models/diner.py:75-97) without the
         ray-batch loop and without a rays tensor round trip: ``gen_rays`` (src/util/cam_geometry.py:36-79) is evaluated
         inside the sampler kernel (``diner_render_image``), the whole target image is ONE launch per stage (no 4096-ray
@@ -1002,12 +1004,52 @@ class NeRFRendererDGS(torch.nn.Module):
         ``encoder.depths`` requiring grad) or one of the four target-camera arguments requiring grad -- the same frame, bit for bit,
         gets a ``grad_fn``: its backward re-runs the training path (``forward()``'s arithmetic under autograd) on the saved rays and
         samples in chunks of ``grad_chunk_rays`` rays and takes the rays' gradient on to the target cameras (``_RenderImageFn``).
+        With ``bounds`` ([SB,2,3] or [2,3]: the subject's axis-aligned box, e.g. ``load_face_bounds``' result) only the rays that meet
+        the box ``bounds + box_offset`` are rendered, their samples spread over the box's own depth interval instead of
+        [z_near, z_far]: ``glue.box_rays`` -> ``forward()``'s inference routing on the compact rays (any route, with its non-finite
+        check, ``last_route`` and ``last_binding``) -> ``glue.frame_from_hits``; a missed pixel is the background colour with depth 0.
+        ``last_box_hits`` then holds each scene's number of rendered rays; a box no ray meets returns the background without a render
+        launch.  Inference only: under autograd it raises ``NotImplementedError`` (train inside a box with ``glue.box_rays`` +
+        ``forward()``).  Without ``bounds`` nothing changes.
         :param target_extrinsics: [SB,4,4] world->cam;  target_intrinsics: [SB,3,3];  z_near, z_far: [SB] or scalars
-        :return: rgb [SB,3,H,W] (, depth [SB,1,H,W])"""
-        if torch.is_grad_enabled() and (self._wants_grad(model, None) or any(
-                isinstance(t, torch.Tensor) and t.requires_grad for t in (target_extrinsics, target_intrinsics, z_near, z_far))):
+        :param return_mask: (with ``bounds``) also return the hit mask [SB,1,H,W] (bool)
+        :return: rgb [SB,3,H,W] (, depth [SB,1,H,W]) (, mask [SB,1,H,W])"""
+        grad = torch.is_grad_enabled() and (self._wants_grad(model, None) or any(
+            isinstance(t, torch.Tensor) and t.requires_grad for t in (target_extrinsics, target_intrinsics, z_near, z_far)))
+        if bounds is not None:
+            if grad:
+                raise NotImplementedError(
+                    "render_image(bounds=...) is inference only: the chunked backward of a boxed frame is not implemented.  To train "
+                    "inside a box, take the hit rays from glue.box_rays and call forward() on them; or wrap the call in torch.no_grad().")
+            return self._render_image_box(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth, bounds, box_offset,
+                                          return_mask)
+        if return_mask:
+            raise ValueError("render_image: return_mask needs bounds (without a box every pixel is rendered)")
+        if grad:
             return self._render_image_grad(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth)
         return self._render_image(model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth)
+
+    @torch.no_grad()
+    def _render_image_box(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth, bounds, box_offset,
+                          return_mask):
+        """render_image inside a box: the hit rays (one host synchronisation of SB counts), forward()'s inference routing on them, the
+        gather back to the frame"""
+        from . import glue
+        H, W = int(H), int(W)
+        rays, _idx, slot, counts = glue.box_rays(target_extrinsics, target_intrinsics, W, H, z_near, z_far, bounds, box_offset)
+        self.last_box_hits = [int(c) for c in counts.tolist()]
+        SB, B, dev = rays.shape[0], rays.shape[1], rays.device
+        if B > 0:
+            fine = self.forward(model, rays).fine
+            rgb_c, depth_c = fine.rgb, fine.depth
+            if self.finite_check != "off":
+                self.check_finite()                                   # once per frame: a NaN image never leaves this function
+        else:
+            rgb_c = torch.empty((SB, 0, 3), dtype=torch.float32, device=dev)
+            depth_c = torch.empty((SB, 0), dtype=torch.float32, device=dev)
+        rgb, depth, *mask = glue.frame_from_hits(rgb_c, depth_c, slot, H, W, self.white_bkgd, return_mask=return_mask)
+        out = (rgb, *((depth,) if return_depth else ()), *mask)
+        return out if len(out) > 1 else rgb
 
     def _render_image_grad(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth):
         shape = self._validate(model)

@@ -768,6 +768,45 @@ int64_t diner_image_scores_workspace_floats(int64_t N, int32_t H, int32_t W);
 int diner_image_scores(const uint8_t *pred, const uint8_t *gt, int64_t N, int32_t H, int32_t W, double *scores_out, float *workspace,
                        void *stream);
 
+/* ---- rendering inside a scene bounding box (ray_box.hip; glue.ray_box, glue.box_rays, glue.frame_from_hits;
+ * NeRFRendererDGS.render_image(bounds=)): the rays of a target camera that meet an axis-aligned box, each with the box's own depth
+ * interval, compacted in pixel order, and the way back from the compact results to a frame.  The device form of
+ * FacescapeDataSet.get_near_far / get_mask_at_box (src/data/facescape.py:128-185) on gen_rays' rays (pixel centres, unit directions).
+ * New symbols only: DINER_ABI_VERSION stays 3.
+ *   box      b_min = bounds[sb][0] + box_lo, b_max = bounds[sb][1] + box_hi (bounds [SB,2,3] fp32 on the device; the reference's
+ *            boffset is (-0.01, 0.01))
+ *   faces    a direction component with |d| < 1e-5 becomes 1e-5; per face plane t = (b - o) / d, SIGNED; the face counts when the point
+ *            t d + o lies within eps = 1e-6 of the box in the two other axes; t0 / t1 = the smallest / largest t of the faces that count
+ *   result   near = max(t0, z_near), far = min(t1, z_far); a hit: two or more faces count and far > near
+ * Two deliberate differences from get_near_far, which takes the unsigned distances |p - o| and their min / max:
+ *   - a box behind the camera is a miss (the reference mirrors it to the front);
+ *   - a camera inside the box gets near = z_near (the reference takes the nearer face, which may be the one behind the camera).
+ * A ray through an edge or a corner meets more than two faces within eps: a hit here, a miss for the reference's "exactly two" count.
+ * Every function, before any launch: DINER_E_INVALID for a NULL pointer, a negative size or a misaligned buffer, DINER_E_UNSUPPORTED for
+ * H W >= 2^31 or SB > 65535; SB = 0 or H W = 0: DINER_OK, nothing is launched.  No atomics: two runs give the same bytes. ------------- */
+/* Every pixel of the SB cameras (cam->H x cam->W) against its scene's box.
+ *   near_far [SB,H W,2]  optional (NULL: not written; 8-byte aligned): a miss holds the camera's z_near, z_far
+ *   idx      [SB,H W]    the first count[sb] entries: the hit pixels x + y W, ascending; the others -1
+ *   slot     [SB,H W]    the rank of the pixel among its scene's hits (idx[sb][slot] = pixel), or -1
+ *   count    [SB]
+ * Three passes: each workgroup of 256 pixels ranks its hits and stores their number in `workspace`
+ * (diner_ray_box_select_workspace_floats 4-byte words, 4-byte aligned; -1 for bad sizes), one workgroup per scene scans the numbers,
+ * the third pass adds the offsets. */
+int64_t diner_ray_box_select_workspace_floats(int32_t SB, int32_t H, int32_t W);
+int diner_ray_box_select(const DinerTargetCam *cam, int32_t SB, const float *bounds, float box_lo, float box_hi, float *near_far,
+                         int32_t *idx, int32_t *slot, int32_t *count, float *workspace, void *stream);
+/* The compact rays [SB,B,8] (16-byte aligned) from diner_ray_box_select's idx and count (on the device): entry j < count[sb] is
+ * gen_rays' ray at pixel idx[sb][j] -- origin and direction those of the full image, bit for bit -- with components 6, 7 = that ray's
+ * near, far of the box.  Entries from count[sb] on are padding: they repeat the scene's last hit; a scene without hits repeats pixel 0
+ * with the camera's z_near, z_far.  count_host (optional, [SB] on the HOST): DINER_E_INVALID when B is below one of them. */
+int diner_gen_rays_box(const DinerTargetCam *cam, int32_t SB, const float *bounds, float box_lo, float box_hi, const int32_t *idx,
+                       const int32_t *count, const int32_t *count_host, int32_t B, float *rays, void *stream);
+/* The frame from the compact results rgb_c [SB,B,3], depth_c [SB,B] (NULL allowed when B = 0), one thread per pixel:
+ * rgb_out [SB,H W,3] = slot >= 0 ? rgb_c[sb][slot] : (white_bkgd ? 1 : 0), depth_out [SB,H W] = slot >= 0 ? depth_c[sb][slot] : 0,
+ * mask_out [SB,H W] bytes (optional) = slot >= 0.  Every output element is written: nothing needs clearing first. */
+int diner_frame_from_hits(const float *rgb_c, const float *depth_c, const int32_t *slot, int32_t SB, int32_t B, int32_t H, int32_t W,
+                          int32_t white_bkgd, float *rgb_out, float *depth_out, uint8_t *mask_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
