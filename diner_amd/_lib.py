@@ -22,6 +22,8 @@ ABI_VERSION = 3
 PRECISIONS = {"fp32": 0, "f16x3": 1}
 # DINER_ROUND_* of include/diner_hip.h (diner_frames_u8)
 ROUNDINGS = {"save_image": 0, "video": 1}
+# DINER_BG_* of include/diner_hip.h (diner_decode_image_u8)
+BG_RULES = {"none": 0, "below_half": 1, "below_one": 2}
 # DINER_ACT_* of include/diner_hip.h (diner_train_gemm_act)
 ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
 
@@ -245,6 +247,11 @@ SYMBOLS = {
     "diner_ray_box_select": (C.c_int, [C.POINTER(DinerTargetCam), _I32, _P, _F32, _F32, _P, _P, _P, _P, _P, _P]),
     "diner_gen_rays_box": (C.c_int, [C.POINTER(DinerTargetCam), _I32, _P, _F32, _F32, _P, _P, C.POINTER(C.c_int32), _I32, _P, _P]),
     "diner_frame_from_hits": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    # the datasets' image bytes and Multiface's depth planes (csrc/image_wire.hip; the ABI version stays 3: new entry points only)
+    "diner_decode_image_u8": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _F32, _I32, _I32, _P, _P, _P]),
+    "diner_decode_depth_u16_mf": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _P, _P, _P, _P]),
+    "diner_encoder_input_u8": (C.c_int, [_P, _P, _I32, _I32, _F32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P, _P, _F32, _F32, _F32, _F32,
+                                         _F32, _F32, _P, _P]),
 }
 
 _lib = None

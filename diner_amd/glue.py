@@ -360,13 +360,43 @@ class _EncoderInputFn(torch.autograd.Function):
         return encoder_input_backward(d_out, ctx.pad, ctx.F, ctx.std).reshape(ctx.shape).to(ctx.dtype), None, None, None, None
 
 
-def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+def _encoder_input_u8(images, alpha, fmt, pad, F, mean, std):
+    """uint8 images [..., H, W, C] (, alpha [..., H, W]) -> [N, 3 + Cpe, H + 2 pad, W + 2 pad]: diner_encoder_input_u8"""
+    from . import wire
+    px, a, N, H, W, Cc, rule = wire.image_source(images, alpha, fmt, images.device, "encoder_input")
+    Cpe = _pe_channels(pad, F)
+    Hp, Wp = H + 2 * pad, W + 2 * pad
+    if pad < 0 or Hp < 2 or Wp < 2:
+        raise ValueError(f"encoder_input: bad sizes N={N}, H={H}, W={W}, image_padding={pad}")
+    xs, ys = _coords(Hp, Wp, px.device) if Cpe else (None, None)
+    out = torch.empty((N, 3 + Cpe, Hp, Wp), dtype=torch.float32, device=px.device)
+    check(_lib.lib().diner_encoder_input_u8(px.data_ptr(), None if a is None else a.data_ptr(), Cc, rule, float(fmt.bg), int(bool(fmt.gamma)),
+                                            int(bool(fmt.symmetric_range)), N, H, W, pad, F, xs.data_ptr() if Cpe else None,
+                                            ys.data_ptr() if Cpe else None, *mean, *std, out.data_ptr(), _st(px.device)),
+          "diner_encoder_input_u8")
+    return out
+
+
+def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMAGENET_STD, *, alpha=None, image_format=None):
     """conv1's input in one kernel (reference src/models/pixelnerf.py:44 + src/models/image_encoder.py:222-232): ``images``
     [..., 3, H, W] -> [N, 3 + Cpe, H + 2 image_padding, W + 2 image_padding] in fp32, N = the product of the leading dimensions.
     Channels 0..2: ``(images - mean) / std`` replicate-padded by ``image_padding``, bit-equal to ``Normalize`` + ``ReplicationPad2d``;
     with ``padding_pe >= 0`` and ``image_padding > 0`` the Cpe = 2 (1 + 2 padding_pe) channels of ``PositionalEncoding(padding_pe,
     freq_factor=pi, d_in=2)`` of the pixel coordinates follow, zero over the image's own pixels.
-    Differentiable with respect to the images (``diner_encoder_input_backward``, deterministic)."""
+    Differentiable with respect to the images (``diner_encoder_input_backward``, deterministic).
+    ``images`` of dtype uint8 are the datasets' bytes [..., H, W, C] (``alpha``: an optional uint8 plane [..., H, W]), read by the
+    arithmetic of ``image_format`` (a ``wire.ImageFormat``, required): the result is that of ``wire.decode_image_u8``'s rgb put through
+    this function, bit for bit, in one launch and without the fp32 images (``diner_encoder_input_u8``; bytes carry no gradient)."""
+    if isinstance(images, torch.Tensor) and images.dtype == torch.uint8:
+        if image_format is None:
+            raise ValueError("encoder_input: uint8 images need image_format (a wire.ImageFormat)")
+        if not images.is_cuda:
+            raise RuntimeError("diner_amd.glue.encoder_input runs on the GPU only")
+        pad, F = int(image_padding), max(int(padding_pe), -1)
+        with torch.no_grad():
+            return _encoder_input_u8(images, alpha, image_format, pad, F, _three(mean, "mean"), _three(std, "std"))
+    if image_format is not None or alpha is not None:
+        raise ValueError("encoder_input: image_format and alpha go with uint8 images only")
     if not isinstance(images, torch.Tensor) or images.dim() < 3 or images.shape[-3] != 3:
         raise ValueError("encoder_input: images must be [..., 3, H, W]")
     if not images.is_cuda:
@@ -379,10 +409,12 @@ def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMA
         return _encoder_input(_f(images).reshape(-1, *images.shape[-3:]), pad, F, mean, std)
 
 
-def encode(model, images, depths, depths_std, extrinsics, intrinsics):
+def encode(model, images, depths, depths_std, extrinsics, intrinsics, image_format=None, alpha=None):
     """Drop-in for ``PixelNeRF.encode`` (reference src/models/pixelnerf.py:35-53) with ``SpatialEncoder.forward``
     (src/models/image_encoder.py:206-272) inside: images [SB,NV,3,H,W], depths, depths_std [SB,NV,1,H,W], extrinsics [SB,NV,4,4],
-    intrinsics [SB,NV,3,3].  The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`,
+    intrinsics [SB,NV,3,3].  Or from the source views' bytes: images uint8 [SB,NV,H,W,C] with ``image_format`` (a ``wire.ImageFormat``)
+    and optionally ``alpha`` uint8 [SB,NV,H,W], as :func:`encoder_input` takes them.
+    The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`,
     or :func:`assemble_latent_bicubic` for ``upsample_interp="bicubic"``) run on the HIP kernels; the model's own trunk modules
     (``model.encoder.model``: conv1, bn1, relu, maxpool, layer1..) run unchanged on PyTorch in between.  Leaves the model in the state the
     reference's encode leaves it in, with ``encoder.latent`` in the layout the render and training kernels read
@@ -391,14 +423,25 @@ def encode(model, images, depths, depths_std, extrinsics, intrinsics):
     if enc.upsample_interp not in ("bilinear", "bicubic"):   # before any device work; there is no eager fallback
         raise NotImplementedError(f"encode: upsample_interp {enc.upsample_interp!r} is not implemented (the two modes torch accepts with "
                                   "align_corners=True, 'bilinear' and 'bicubic', are)")
-    SB, NV, _, H, W = images.shape
+    if images.dtype == torch.uint8:   # the refusals of a byte source come before the model is touched
+        from . import wire
+        if image_format is None:
+            raise ValueError("encode: uint8 images need image_format (a wire.ImageFormat)")
+        if images.dim() != 5:
+            raise ValueError(f"encode: uint8 images must be [SB, NV, H, W, C], not {tuple(images.shape)}")
+        wire.image_source(images, alpha, image_format, images.device, "encode")
+        SB, NV, H, W, _ = images.shape
+    else:
+        if image_format is not None or alpha is not None:
+            raise ValueError("encode: image_format and alpha go with uint8 images only")
+        SB, NV, _, H, W = images.shape
     norm = getattr(model, "normalize_rgb", None)
     mean, std = getattr(norm, "mean", None), getattr(norm, "std", None)
     enc.depths, enc.depths_std = depths, depths_std
     enc.normals = depth2normal(depths.flatten(0, 1), intrinsics.flatten(0, 1)).reshape(SB, NV, 3, H, W)
     enc.nviews, enc.nobjects = NV, SB
     x = encoder_input(images, enc.image_padding, enc.padding_pe, IMAGENET_MEAN if mean is None else mean,
-                      IMAGENET_STD if std is None else std)
+                      IMAGENET_STD if std is None else std, alpha=alpha, image_format=image_format)
     trunk = enc.model
     x = trunk.relu(trunk.bn1(trunk.conv1(x)))
     levels = [x]

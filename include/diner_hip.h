@@ -807,6 +807,51 @@ int diner_gen_rays_box(const DinerTargetCam *cam, int32_t SB, const float *bound
 int diner_frame_from_hits(const float *rgb_c, const float *depth_c, const int32_t *slot, int32_t SB, int32_t B, int32_t H, int32_t W,
                           int32_t white_bkgd, float *rgb_out, float *depth_out, uint8_t *mask_out, void *stream);
 
+/* ---- the datasets' image bytes and Multiface's depth planes, decoded on the device (csrc/image_wire.hip) ------------------------------
+ * The other half of the upstream wire format (PNG decoding stays on the host).  New symbols only:
+ * DINER_ABI_VERSION stays 3.  pixels [N,H,W,C] uint8, interleaved as np.asarray(PIL.Image) gives them, C = 3 or 4; alpha (optional)
+ * [N,H,W] uint8, a plane of its own that wins over a fourth channel (Multiface keeps alpha in a file of its own).  Replaces
+ * FacescapeDataSet.read_rgba (src/data/facescape.py:59-66), DTUDataSet.read_rgb after its PIL resize (src/data/dtu.py:83-88), and
+ * MultiFaceDataset.read_img / read_alpha / gammaCorrect (src/data/multiface.py:65-95) with the white fill of :322-323.
+ * Per pixel, one fp32 rounding per operation, in this order:
+ *   1. v = (float)byte / 255.0f, a = (float)alpha_byte / 255.0f   (true divisions)
+ *   2. gamma != 0 (gammaCorrect + the clip(0, 1) of multiface.py:68), per channel c with s = (1.4f, 1.1f, 1.6f):
+ *        t = (v s_c) / 1.1f;  t = clamp(t - float(3/255), 0, 2);  t = float((1 / (1 - 3/255)) 0.95) t;  t = sqrt(t) (correctly rounded);
+ *        t = clamp(t - float(15/255), 0, 2);  v = clamp(t, 0, 1)
+ *   3. symmetric_range != 0: v = v 2 - 1 (two operations)
+ *   4. the background fill, written last with `bg` as given (it is NOT mapped to the symmetric range, as in the reference):
+ *        DINER_BG_BELOW_HALF (facescape.py:65): the three channels = bg where a < 0.5f;  DINER_BG_BELOW_ONE (multiface.py:322-323): where
+ *        a < 1.0f;  DINER_BG_NONE: no fill.
+ * rgb_out [N,3,H,W], alpha_out [N,1,H,W] = a (optional) fp32; every element is written, no atomics.  With W % 4 == 0, pixels 16-byte
+ * (C = 4) or 4-byte (C = 3) aligned, alpha 4-byte and the outputs 16-byte aligned a thread takes 4 pixels (16- / 4-byte loads, 16-byte
+ * stores); otherwise one: the same bits either way.
+ * Before any launch: DINER_E_INVALID for a NULL pixels / rgb_out, C not 3 or 4, an unknown rule, a rule other than DINER_BG_NONE or
+ * an alpha_out without any alpha (neither C == 4 nor a plane), N / H / W <= 0; DINER_E_UNSUPPORTED for H W >= 2^31, N > 65535 or more
+ * workgroups than one launch's grid holds (2^31 - 1 of 256 threads). */
+#define DINER_BG_NONE 0
+#define DINER_BG_BELOW_HALF 1
+#define DINER_BG_BELOW_ONE 2
+int diner_decode_image_u8(const uint8_t *pixels, const uint8_t *alpha, int64_t N, int32_t H, int32_t W, int32_t C, int32_t bg_rule, float bg,
+                          int32_t gamma, int32_t symmetric_range, float *rgb_out, float *alpha_out, void *stream);
+/* Multiface's depth planes: MultiFaceDataset.read_depth (src/data/multiface.py:103-109) and the std of :305-311.  depth, conf
+ * (optional) uint16 [N,H,W] -> depth_out, std_out (and mask_out = depth > 0, optional) [N,H/stride,W/stride] fp32, nearest-subsampled
+ * by `stride` as diner_decode_depth_u16:  depth = u16 * mul0 (the reference: 1e-4f);  std = max(std_a * (conf * mul0) + std_b, 0), a
+ * multiplication and an addition (:309-310, std_a = -1.582e-2, std_b = 1.649e-2), or const_std without a confidence plane (:307,
+ * 1e-3f);  std = 0 where depth == 0 (:311).
+ * Before any launch: DINER_E_INVALID for a NULL depth / depth_out / std_out, N < 0, H / W / stride <= 0 or a stride that does not
+ * divide H and W; DINER_E_UNSUPPORTED for H W >= 2^31, N > 65535 or more workgroups than one launch's grid holds.  N = 0: DINER_OK,
+ * nothing is launched. */
+int diner_decode_depth_u16_mf(const uint16_t *depth, const uint16_t *conf, int64_t N, int32_t H, int32_t W, int32_t stride, float mul0,
+                              float std_a, float std_b, float const_std, float *depth_out, float *std_out, float *mask_out, void *stream);
+/* conv1's input straight from the bytes: diner_encoder_input (above; src/models/pixelnerf.py:44, src/models/image_encoder.py:222-232)
+ * applied to diner_decode_image_u8's rgb, bit for bit, without the fp32 images in between -- the same kernel with a loader that decodes
+ * the pixel (steps 1..4) where the fp32 one reads it.  The arguments of diner_decode_image_u8's source and format, then those of
+ * diner_encoder_input; both functions' refusals.  No adjoint: bytes carry no gradient. */
+int diner_encoder_input_u8(const uint8_t *pixels, const uint8_t *alpha, int32_t C, int32_t bg_rule, float bg, int32_t gamma,
+                           int32_t symmetric_range, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t pe_freqs, const float *xs,
+                           const float *ys, float mean0, float mean1, float mean2, float std0, float std1, float std2, float *out,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
