@@ -24,6 +24,8 @@ PRECISIONS = {"fp32": 0, "f16x3": 1}
 ROUNDINGS = {"save_image": 0, "video": 1}
 # DINER_BG_* of include/diner_hip.h (diner_decode_image_u8)
 BG_RULES = {"none": 0, "below_half": 1, "below_one": 2}
+# DINER_RESIZE_* of include/diner_hip.h (diner_resize_table)
+RESIZE_MODES = {"bilinear_aa": 1, "bilinear": 2, "bicubic_u8": 3}
 # DINER_ACT_* of include/diner_hip.h (diner_train_gemm_act)
 ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
 
@@ -252,6 +254,14 @@ SYMBOLS = {
     "diner_decode_depth_u16_mf": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _P, _P, _P, _P]),
     "diner_encoder_input_u8": (C.c_int, [_P, _P, _I32, _I32, _F32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P, _P, _F32, _F32, _F32, _F32,
                                          _F32, _F32, _P, _P]),
+    # the image resizes fused with the byte decode (csrc/image_resize.hip; the ABI version stays 3: new entry points only); the tables
+    # of diner_resize_table are host arrays
+    "diner_resize_taps": (C.c_int, [_I32, _I32, _I32]),
+    "diner_resize_table": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P]),
+    "diner_decode_image_u8_resized": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _F32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P,
+                                                _I32, _P, _P, _P, _P]),
+    "diner_resize_u8": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P, _P]),
+    "diner_decode_depth_u16_mf_nearest": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _P, _P, _P, _P]),
 }
 
 _lib = None

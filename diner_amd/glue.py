@@ -377,7 +377,8 @@ def _encoder_input_u8(images, alpha, fmt, pad, F, mean, std):
     return out
 
 
-def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMAGENET_STD, *, alpha=None, image_format=None):
+def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMAGENET_STD, *, alpha=None, image_format=None, size=None,
+                  antialias=True):
     """conv1's input in one kernel (reference src/models/pixelnerf.py:44 + src/models/image_encoder.py:222-232): ``images``
     [..., 3, H, W] -> [N, 3 + Cpe, H + 2 image_padding, W + 2 image_padding] in fp32, N = the product of the leading dimensions.
     Channels 0..2: ``(images - mean) / std`` replicate-padded by ``image_padding``, bit-equal to ``Normalize`` + ``ReplicationPad2d``;
@@ -386,7 +387,9 @@ def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMA
     Differentiable with respect to the images (``diner_encoder_input_backward``, deterministic).
     ``images`` of dtype uint8 are the datasets' bytes [..., H, W, C] (``alpha``: an optional uint8 plane [..., H, W]), read by the
     arithmetic of ``image_format`` (a ``wire.ImageFormat``, required): the result is that of ``wire.decode_image_u8``'s rgb put through
-    this function, bit for bit, in one launch and without the fp32 images (``diner_encoder_input_u8``; bytes carry no gradient)."""
+    this function, bit for bit, in one launch and without the fp32 images (``diner_encoder_input_u8``; bytes carry no gradient).
+    With ``size`` = (h, w) other than (H, W) the bytes are decoded and resized first (``wire.decode_image_u8(.., size=, antialias=)``,
+    the resize kernels) and the floats take the route above: the same bits as calling the two in turn."""
     if isinstance(images, torch.Tensor) and images.dtype == torch.uint8:
         if image_format is None:
             raise ValueError("encoder_input: uint8 images need image_format (a wire.ImageFormat)")
@@ -394,9 +397,15 @@ def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMA
             raise RuntimeError("diner_amd.glue.encoder_input runs on the GPU only")
         pad, F = int(image_padding), max(int(padding_pe), -1)
         with torch.no_grad():
+            if size is not None:
+                from . import wire
+                if wire._hw(size, "encoder_input") != tuple(images.shape[-3:-1]):
+                    rgb = wire.decode_image_u8(images, alpha, image_format, want_alpha=False, device=images.device, size=size,
+                                               antialias=antialias)[0]
+                    return _encoder_input(rgb, pad, F, _three(mean, "mean"), _three(std, "std"))
             return _encoder_input_u8(images, alpha, image_format, pad, F, _three(mean, "mean"), _three(std, "std"))
-    if image_format is not None or alpha is not None:
-        raise ValueError("encoder_input: image_format and alpha go with uint8 images only")
+    if image_format is not None or alpha is not None or size is not None:
+        raise ValueError("encoder_input: image_format, alpha and size go with uint8 images only")
     if not isinstance(images, torch.Tensor) or images.dim() < 3 or images.shape[-3] != 3:
         raise ValueError("encoder_input: images must be [..., 3, H, W]")
     if not images.is_cuda:
@@ -409,11 +418,12 @@ def encoder_input(images, image_padding, padding_pe, mean=IMAGENET_MEAN, std=IMA
         return _encoder_input(_f(images).reshape(-1, *images.shape[-3:]), pad, F, mean, std)
 
 
-def encode(model, images, depths, depths_std, extrinsics, intrinsics, image_format=None, alpha=None):
+def encode(model, images, depths, depths_std, extrinsics, intrinsics, image_format=None, alpha=None, image_size=None, antialias=True):
     """Drop-in for ``PixelNeRF.encode`` (reference src/models/pixelnerf.py:35-53) with ``SpatialEncoder.forward``
     (src/models/image_encoder.py:206-272) inside: images [SB,NV,3,H,W], depths, depths_std [SB,NV,1,H,W], extrinsics [SB,NV,4,4],
     intrinsics [SB,NV,3,3].  Or from the source views' bytes: images uint8 [SB,NV,H,W,C] with ``image_format`` (a ``wire.ImageFormat``)
-    and optionally ``alpha`` uint8 [SB,NV,H,W], as :func:`encoder_input` takes them.
+    and optionally ``alpha`` uint8 [SB,NV,H,W], as :func:`encoder_input` takes them; ``image_size`` = (h, w): the bytes are resized to the
+    size of the depths and intrinsics first (:func:`encoder_input`'s ``size`` and ``antialias``).
     The head (:func:`encoder_input`), the normals (:func:`depth2normal`) and the tail (:func:`assemble_latent`,
     or :func:`assemble_latent_bicubic` for ``upsample_interp="bicubic"``) run on the HIP kernels; the model's own trunk modules
     (``model.encoder.model``: conv1, bn1, relu, maxpool, layer1..) run unchanged on PyTorch in between.  Leaves the model in the state the
@@ -431,9 +441,11 @@ def encode(model, images, depths, depths_std, extrinsics, intrinsics, image_form
             raise ValueError(f"encode: uint8 images must be [SB, NV, H, W, C], not {tuple(images.shape)}")
         wire.image_source(images, alpha, image_format, images.device, "encode")
         SB, NV, H, W, _ = images.shape
+        if image_size is not None:
+            H, W = wire._hw(image_size, "encode")
     else:
-        if image_format is not None or alpha is not None:
-            raise ValueError("encode: image_format and alpha go with uint8 images only")
+        if image_format is not None or alpha is not None or image_size is not None:
+            raise ValueError("encode: image_format, alpha and image_size go with uint8 images only")
         SB, NV, _, H, W = images.shape
     norm = getattr(model, "normalize_rgb", None)
     mean, std = getattr(norm, "mean", None), getattr(norm, "std", None)
@@ -441,7 +453,8 @@ def encode(model, images, depths, depths_std, extrinsics, intrinsics, image_form
     enc.normals = depth2normal(depths.flatten(0, 1), intrinsics.flatten(0, 1)).reshape(SB, NV, 3, H, W)
     enc.nviews, enc.nobjects = NV, SB
     x = encoder_input(images, enc.image_padding, enc.padding_pe, IMAGENET_MEAN if mean is None else mean,
-                      IMAGENET_STD if std is None else std, alpha=alpha, image_format=image_format)
+                      IMAGENET_STD if std is None else std, alpha=alpha, image_format=image_format, size=image_size,
+                      antialias=antialias)
     trunk = enc.model
     x = trunk.relu(trunk.bn1(trunk.conv1(x)))
     levels = [x]

@@ -852,6 +852,54 @@ int diner_encoder_input_u8(const uint8_t *pixels, const uint8_t *alpha, int32_t 
                            const float *ys, float mean0, float mean1, float mean2, float std0, float std1, float std2, float *out,
                            void *stream);
 
+/* ---- the datasets' image resizes, fused with the byte decode (csrc/image_resize.hip) -------------------------------------------------
+ * New symbols only: DINER_ABI_VERSION stays 3.  Three resamplers, each defined by the library call it replaces:
+ *   nearest                    F.interpolate(mode="nearest"): src = min((int)floorf(dst * scale), in - 1), scale = (float)in / (float)out,
+ *                              the product in fp32 (Multiface's alphas, depths and stds, src/data/multiface.py:349-354)
+ *   DINER_RESIZE_BILINEAR_AA   F.interpolate(mode="bilinear", align_corners=False, antialias=True), what current torchvision's resize
+ *                              runs on a float tensor (multiface.py:347-348): per axis scale = in / out, support = max(scale, 1),
+ *                              center = scale (i + 0.5), xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support +
+ *                              0.5), in) - xmin, w_j = max(0, 1 - |(j + xmin - center + 0.5) / max(scale, 1)|) / their sum
+ *   DINER_RESIZE_BILINEAR      the same call with antialias=False (torchvision 0.12 on tensors): src = max(scale (i + 0.5) - 0.5, 0),
+ *                              i0 = (int)src, taps i0 and i0 + (i0 < in - 1) with 1 - (src - i0) and src - i0
+ *   DINER_RESIZE_BICUBIC_U8    PIL's Image.resize on 8-bit pixels (src/data/dtu.py:79-83): support = 2 max(scale, 1), the window as
+ *                              above, k_j = bicubic((j + xmin - center + 0.5) / max(scale, 1)) with a = -0.5 / their sum, then to fixed
+ *                              point with 22 fractional bits, (int)(+-0.5 + k 2^22)
+ * The filters are separable.  diner_resize_table tabulates one axis on the HOST, in double: bounds [out][2] = (xmin, n) and weights
+ * [out][taps] (fp32, or int32 for DINER_RESIZE_BICUBIC_U8; zero beyond n), taps >= diner_resize_taps(in, out, mode) = the longest
+ * window.  The caller copies the tables to the device and may keep them per (in, out, mode).  The kernels only multiply and add, in the
+ * order of the taps (fp32: one fused multiply-add per tap), so two runs give the same bits; what a table says is clamped into the
+ * source before it addresses anything; no atomics; every output element is written.
+ * Both: DINER_E_INVALID for in / out <= 0, an unknown mode, NULL pointers or taps below diner_resize_taps. */
+#define DINER_RESIZE_BILINEAR_AA 1
+#define DINER_RESIZE_BILINEAR 2
+#define DINER_RESIZE_BICUBIC_U8 3
+int diner_resize_taps(int32_t in, int32_t out, int32_t mode);
+int diner_resize_table(int32_t in, int32_t out, int32_t mode, int32_t taps, int32_t *bounds, void *weights);
+/* diner_decode_image_u8 at the size (h, w): the pixels are decoded at full size (steps 1..4 above: a filled pixel enters the filter as
+ * the fill, the reference's order), filtered along x into tmp [N,3,H,w] fp32 (the decoded values of a row segment staged in LDS once
+ * per workgroup) and along y into rgb_out [N,3,h,w]; alpha_out [N,1,h,w] (optional) is the NEAREST resample of alpha / 255.  The tables
+ * (device pointers) are those of a float mode for (W, w) and (H, h).
+ * Before any launch: diner_decode_image_u8's refusals, DINER_E_INVALID for a NULL tmp or table, taps or h / w <= 0;
+ * DINER_E_UNSUPPORTED for H W, H w or h w >= 2^31, N > 65535, N H >= 2^31 or w > 256 x 65535. */
+int diner_decode_image_u8_resized(const uint8_t *pixels, const uint8_t *alpha, int64_t N, int32_t H, int32_t W, int32_t C, int32_t bg_rule,
+                                  float bg, int32_t gamma, int32_t symmetric_range, int32_t h, int32_t w, const int32_t *bounds_x,
+                                  const float *weights_x, int32_t taps_x, const int32_t *bounds_y, const float *weights_y, int32_t taps_y,
+                                  float *tmp, float *rgb_out, float *alpha_out, void *stream);
+/* PIL's Image.resize((w, h)) with its default filter on N images [N,H,W,C] uint8, C = 1 or 3 interleaved -> out [N,h,w,C] uint8:
+ * pixel = clip((2^21 + sum byte k) >> 22, 0, 255) in integer arithmetic, the horizontal pass first into tmp [N,H,w,C] uint8, the
+ * vertical pass second; a pass whose size does not change is skipped (its table and, unless both run, tmp may be NULL).  The tables are
+ * DINER_RESIZE_BICUBIC_U8's.  Before any launch: DINER_E_INVALID for a NULL pointer, a non-positive size or taps, C not 1 or 3 (PIL
+ * premultiplies RGBA: not served); DINER_E_UNSUPPORTED as above. */
+int diner_resize_u8(const uint8_t *pixels, int64_t N, int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, const int32_t *bounds_x,
+                    const int32_t *weights_x, int32_t taps_x, const int32_t *bounds_y, const int32_t *weights_y, int32_t taps_y,
+                    uint8_t *tmp, uint8_t *out, void *stream);
+/* diner_decode_depth_u16_mf at the size (h, w): its arithmetic, the zero-depth rule included, on the texel the nearest resample
+ * selects -> depth_out, std_out (, mask_out) [N,h,w].  Its refusals, with h / w <= 0 in place of the stride's; N <= 0 is refused. */
+int diner_decode_depth_u16_mf_nearest(const uint16_t *depth, const uint16_t *conf, int64_t N, int32_t H, int32_t W, int32_t h, int32_t w,
+                                      float mul0, float std_a, float std_b, float const_std, float *depth_out, float *std_out,
+                                      float *mask_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
