@@ -255,7 +255,12 @@ __device__ __forceinline__ BicubicFoot bicubic_footprint(float u, float w, float
 
 // --------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG (perf mode: statistically equivalent to torch.rand/randn, not
-// bit-matching any torch generator -- parity tests inject explicit noise instead)
+// bit-matching any torch generator -- parity tests against the reference inject explicit noise
+// instead).  What the sampler draws from it is a fixed function of (call seed, ray, index), the
+// stream contract of DESIGN.md section 2: key = (seed_lo, seed_hi), counter = (x, stream, gray_lo,
+// gray_hi).  tests/philox_ref.py restates it on the host and tests/test_gpu_philox.py holds the
+// kernels to that restatement (uniform streams bit for bit): a change here or to a counter in
+// sampler.hip changes every frame rendered at a fixed seed.
 // --------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint4 philox4x32(uint4 ctr, uint2 key)
 {
