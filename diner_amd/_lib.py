@@ -262,6 +262,13 @@ SYMBOLS = {
                                                 _I32, _P, _P, _P, _P]),
     "diner_resize_u8": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P, _P]),
     "diner_decode_depth_u16_mf_nearest": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _F32, _F32, _F32, _F32, _P, _P, _P, _P]),
+    # nearest mesh vertex and the deformation built on it (csrc/nearest_vertex.hip; the ABI version stays 3: new entry points only)
+    "diner_nearest_vertex_workspace_floats": (_I64, [_I32, _I32]),
+    "diner_nearest_vertex_keys": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "diner_nearest_vertex_build": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
+    "diner_nearest_vertex": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
+    "diner_deform_points": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
+    "diner_deform_ray_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -18,7 +18,9 @@ and the way from a rendered frame to its files and scores: :func:`torch_cmap` (r
 :func:`frames_u8` (the quantisation of ``save_image`` and ``save_torch_video``, ``src/models/diner.py:129-133, :209-214``) and
 :func:`image_scores` (l1, l2, psnr, ssim of ``evaluate_folder``, ``src/evaluation/eval_suite.py:63-68``);
 and rendering inside a scene bounding box: :func:`ray_box` (``FacescapeDataSet.get_near_far`` + ``get_mask_at_box``,
-``src/data/facescape.py:128-185``, on the project's rays), :func:`box_rays` (the hit pixels' rays, compacted) and :func:`frame_from_hits`.
+``src/data/facescape.py:128-185``, on the project's rays), :func:`box_rays` (the hit pixels' rays, compacted) and :func:`frame_from_hits`;
+and the deformation of the fork's NOVEL renderers (``src/models/novel/nerf_novel_renderer.py:40-50``): :func:`nearest_vertex`,
+:func:`deform_points` and :func:`deform_ray_points`, which live in :mod:`diner_amd.deform`.
 """
 from __future__ import annotations
 
@@ -1027,3 +1029,7 @@ def frame_from_hits(rgb_c, depth_c, slot, H, W, white_bkgd, return_mask=False):
     if return_mask:
         return out + (mask.view(SB, 1, H, W).bool(),)
     return out
+
+
+# ---- nearest mesh vertex and the NOVEL renderers' deformation (csrc/nearest_vertex.hip) -------------------------------------------------
+from .deform import deform_points, deform_ray_points, nearest_vertex  # noqa: E402,F401

@@ -900,6 +900,47 @@ int diner_decode_depth_u16_mf_nearest(const uint16_t *depth, const uint16_t *con
                                       float mul0, float std_a, float std_b, float const_std, float *depth_out, float *std_out,
                                       float *mask_out, void *stream);
 
+/* ---- nearest mesh vertex and the deformation built on it (csrc/nearest_vertex.hip; glue.nearest_vertex, glue.deform_points,
+ * glue.deform_ray_points; diner_amd.compat.pytorch3d_knn) --------------------------------------------------------------------------------
+ * What the fork's NOVEL / NOVEL_PE renderers do to every candidate and sample (src/models/novel/nerf_novel_renderer.py:40-50):
+ * knn_points(points, target_vertices, K=1) and points + offsets[nearest].  New symbols only: DINER_ABI_VERSION stays 3.
+ * Arithmetic contract, for an fp32 point p and vertex v:
+ *   d2      = ((px - vx)^2 + (py - vy)^2) + (pz - vz)^2, every operation rounded once to fp32, nothing contracted
+ *   winner  the vertex of smallest (d2, original index), lexicographic, among those with d2 < +inf: a tie goes to the lowest index, a
+ *           NaN d2 never wins; a point without such a vertex gets idx = 0, d2 = +inf
+ * points [SB,N,3], vertices [SB,V,3] (every scene its own set, the same V), idx [SB,N] int32, d2 [SB,N], offsets [SB,V,3], all fp32 and
+ * on the device.  No array index is derived from a point's coordinates; what is derived from vertex coordinates (the Morton keys) is
+ * clamped before the conversion to int.  No atomics; every output element is written; two runs give the same bits.
+ * Two routes with the same results, bit for bit, for every input:
+ *   workspace == NULL  brute force: the vertices pass through LDS in SoA tiles, ascending, strict `<`
+ *   workspace != NULL  the cluster structure of diner_nearest_vertex_build (16-byte aligned): per cluster of 64 vertices, consecutive in
+ *                      Morton order, lb = (ex^2 + ey^2) + ez^2 with e = max(lo - p, p - hi, 0) per axis, in the operation order of d2.
+ *                      fp32 subtraction, squaring of non-negatives and addition are monotone, so lb <= d2 of every member; a cluster is
+ *                      scanned iff lb <= best (not strict: a tie with a lower index may sit in it), starting from the cluster of smallest
+ *                      lb, which is not scanned again.
+ * Envelope: 0 < V <= 2^24, 0 <= N < 2^31, 0 <= SB <= 65535.  Before any launch: DINER_E_INVALID for a NULL pointer, V <= 0 or a
+ * negative size, DINER_E_UNSUPPORTED outside the envelope; N = 0 or SB = 0: DINER_OK, nothing is launched. */
+/* floats of the cluster structure: per scene ceil(V / 64) clusters of 64 (x, y, z, original index) and 6 AABB floats; -1 for bad sizes */
+int64_t diner_nearest_vertex_workspace_floats(int32_t SB, int32_t V);
+/* keys [SB,V] int32: the 30-bit Morton key of every vertex over the bounding box of its scene's finite coordinates, 10 bits per axis,
+ * q = (int)min(max((v - lo) (1024 / extent), 0), 1023); an axis of zero extent contributes 0.  One workgroup per scene. */
+int diner_nearest_vertex_keys(const float *vertices, int32_t SB, int32_t V, int32_t *keys, void *stream);
+/* order [SB,V] int32: the vertices of each scene in the STABLE order of their keys (the sort is the caller's; entries are clamped into
+ * [0, V - 1]) -> workspace: the permuted copy with each vertex's original index, the ragged last cluster padded with NaN vertices, and
+ * one AABB [lo, hi] per cluster (NaN coordinates bound nothing).  The order decides the time of a query, never its result. */
+int diner_nearest_vertex_build(const float *vertices, const int32_t *order, int32_t SB, int32_t V, float *workspace, void *stream);
+int diner_nearest_vertex(const float *points, const float *vertices, const float *workspace, int32_t SB, int64_t N, int32_t V, int32_t *idx,
+                         float *d2, void *stream);
+/* out [SB,N,3] = points + offsets[idx], in one pass; offsets2 / out2 (optional, together): a second offset set over the same vertices,
+ * served by the same search. */
+int diner_deform_points(const float *points, const float *vertices, const float *workspace, const float *offsets, const float *offsets2,
+                        int32_t SB, int64_t N, int32_t V, float *out, float *out2, void *stream);
+/* The same with the points formed from rays [SB,B,8] and z [SB,B,K] as the reference forms them (:412): p = o + z d, a multiplication
+ * and an addition; N = B K, point b K + k.  points_out [SB,B K,3] (optional): the undeformed points. */
+int diner_deform_ray_points(const float *rays, const float *z, const float *vertices, const float *workspace, const float *offsets,
+                            const float *offsets2, int32_t SB, int64_t B, int32_t K, int32_t V, float *out, float *out2, float *points_out,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
