@@ -269,6 +269,9 @@ SYMBOLS = {
     "diner_nearest_vertex": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "diner_deform_points": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "diner_deform_ray_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    # the depth-guided sampler on given candidate points (csrc/sampler_points.hip; the ABI version stays 3: a new entry point only)
+    "diner_sample_depthguided_points": (C.c_int, [C.POINTER(DinerScene), _P, _P, _P, _I64, C.POINTER(DinerSamplerCfg), _P, _P, _U64,
+                                                  _P, _P, _P, _P]),
 }
 
 _lib = None

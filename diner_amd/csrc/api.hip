@@ -109,6 +109,8 @@ int launch_linz_maps(const float *, int64_t, const float *, float *, hipStream_t
 int launch_linz_maps_ring(const float *, int64_t, int, int, const float *, float *, hipStream_t);
 int launch_sampler(const DinerScene &, const float *, const DinerTargetCam *, float *, int64_t, const DinerSamplerCfg &, const float *,
                    const float *, const float *, const float *, uint64_t, float *, float *, float *, hipStream_t);
+int launch_sampler_points(const DinerScene &, const float *, const float *, const float *, int64_t, const DinerSamplerCfg &, const float *,
+                          const float *, uint64_t, float *, float *, float *, hipStream_t);
 int launch_sample_coarse(const float *, int64_t, int, const float *, uint64_t, float *, hipStream_t);
 int launch_fill_up(const float *, const float *, int64_t, int, const float *, uint64_t, float *, hipStream_t);
 int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, float *, hipStream_t);
@@ -330,6 +332,25 @@ int diner_sample_depthguided(const DinerScene *scene, const float *rays, int64_t
     if (NR > 0 && scene->SB > 0 && (!rays || !z_out)) return bad("sample_depthguided: NULL rays / z_out");
     return launch_sampler(*scene, rays, nullptr, nullptr, NR, *cfg, u_coarse, n_gauss, u_fill, z_cand, seed, z_out, z_dg_out, lik_out,
                           (hipStream_t)stream);
+}
+
+int diner_sample_depthguided_points(const DinerScene *scene, const float *rays, const float *z_cand, const float *xyz_cand,
+                                    int64_t NR, const DinerSamplerCfg *cfg, const float *n_gauss, const float *u_fill,
+                                    uint64_t seed, float *z_out, float *z_dg_out, float *lik_out, void *stream)
+{
+    int rc;
+    if ((rc = check_scene(scene, false)) || (rc = check_cfg(cfg))) return rc;   // (check_cfg: K < G)
+    if (NR < 0) return bad("NR < 0");
+    if (cfg->n_candidates > 4096) {
+        set_error("sample_depthguided_points: n_candidates=%d > 4096 unsupported", cfg->n_candidates);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (NR > 0 && scene->SB > 0) {
+        if (!rays || !z_out) return bad("sample_depthguided_points: NULL rays / z_out");
+        if (!z_cand || !xyz_cand) return bad("sample_depthguided_points: NULL z_cand / xyz_cand");
+    }
+    return launch_sampler_points(*scene, rays, z_cand, xyz_cand, NR, *cfg, n_gauss, u_fill, seed, z_out, z_dg_out, lik_out,
+                                 (hipStream_t)stream);
 }
 
 int64_t diner_linz_maps_floats(int64_t N, int32_t h, int32_t w, const DinerLatentIndex *index)

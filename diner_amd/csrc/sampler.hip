@@ -19,102 +19,9 @@
 // [0,1], so the bit pattern is monotonic) counting with ballots, then keeps everything above it and
 // the lowest-index ties -- no sort of the candidates at all.
 #include "common.hpp"
+#include "sampler_blocks.hpp"
 
 namespace diner {
-
-struct MapGeo {
-    int H, W;
-    float halfW, halfH, Wm1, Hm1;          // depth / normal maps
-    float sfx, sfy, halfWp, halfHp, Wpm1, Hpm1;  // sigma map extended by DINER_SIGMA_PAD
-};
-
-// Likelihood of one candidate under one source view -- nerf_renderer.py:107-128.
-// tex: the view's packed map, 2 float4 per texel = {nx,ny,nz,depth},{sigma,0,0,0}.
-__device__ __forceinline__ float view_likelihood(const float4 *__restrict__ tex, const View &vw, const MapGeo &g,
-                                                 float iw, float ih, float dcx, float dcy, float dcz,
-                                                 float x, float y, float z, float half_step, float ddmax)
-{
-    float px, py, pz, u, w;
-    project(vw, iw, ih, x, y, z, px, py, pz, u, w);
-    // depth: nearest, border (image_encoder.py:129-151)
-    const float ux = unnorm(u, g.halfW), uy = unnorm(w, g.halfH);
-    const int dx = safe_idx(__builtin_rintf(clipf(ux, g.Wm1)), g.W), dy = safe_idx(__builtin_rintf(clipf(uy, g.Hm1)), g.H);
-    const float depth = tex[((int64_t)dy * g.W + dx) * 2].w;
-    if (!(fabsf(depth - pz) < ddmax)) return 0.0f;                      // depth_dist_mask (:122)
-    // sigma: nearest in the exponentially padded map, zeros outside (image_encoder.py:153-180,
-    // torch_helpers.py:100-160): ring at Chebyshev distance d>=1 = border * exp((d-1)/12 * ln 2)
-    const float jx = __builtin_rintf(unnorm(u * g.sfx, g.halfWp)), jy = __builtin_rintf(unnorm(w * g.sfy, g.halfHp));
-    if (!(jx >= 0.0f && jx <= g.Wpm1 && jy >= 0.0f && jy <= g.Hpm1)) return 0.0f;
-    const int sx = (int)jx - DINER_SIGMA_PAD, sy = (int)jy - DINER_SIGMA_PAD;
-    const int ox = sx < 0 ? -sx : (sx > g.W - 1 ? sx - (g.W - 1) : 0);
-    const int oy = sy < 0 ? -sy : (sy > g.H - 1 ? sy - (g.H - 1) : 0);
-    const int cheb = ox > oy ? ox : oy;
-    const int cx = sx < 0 ? 0 : (sx > g.W - 1 ? g.W - 1 : sx), cy = sy < 0 ? 0 : (sy > g.H - 1 ? g.H - 1 : sy);
-    float sigma = tex[((int64_t)cy * g.W + cx) * 2 + 1].x;
-    if (cheb > 1) sigma = sigma * expf((float)(cheb - 1) / 12.0f * 0.6931471805599453f);
-    if (sigma == 0.0f) return 0.0f;                                      // bg_mask (:123)
-    // normal: nearest, zeros (image_encoder.py:182-204)
-    const float nxf = __builtin_rintf(ux), nyf = __builtin_rintf(uy);
-    float cosd = 0.0f;
-    if (nxf >= 0.0f && nxf <= g.Wm1 && nyf >= 0.0f && nyf <= g.Hm1) {
-        const float4 n = tex[((int64_t)(int)nyf * g.W + (int)nxf) * 2];
-        cosd = dcx * n.x + dcy * n.y + dcz * n.z;                        // :119
-    }
-    if (!(cosd <= 0.0f)) return 0.0f;                                    // :121
-    const float den = sigma * 1.4142135623730951f;
-    const float a = erff((pz + half_step - depth) / den), b = erff((pz - half_step - depth) / den);
-    return fabsf(0.5f * (a - b));                                        // :125-128
-}
-
-// fill_up_uniform_samples (:376-396) on the K values of one ray held in LDS (one wave):
-// after the reference's first sort the m zeros sit in columns n_neg .. n_neg+m-1 (n_neg = number of
-// negative samples, normally 0), so the i-th empty slot becomes near + (n_neg+i)*step + u_i*step;
-// then one ascending bitonic sort (:396) over n2 = pow2 >= K with +inf padding.
-__device__ __forceinline__ void fill_up_and_sort(float *zs, int K, float near, float far, const float *u_fill_row,
-                                                 int64_t gray, uint2 key, int lane)
-{
-    int m = 0, n_neg = 0;
-    for (int i0 = 0; i0 < K; i0 += 64) {
-        const int i = i0 + lane;
-        const float v = i < K ? zs[i] : 1.0f;
-        m += __popcll(__ballot(v == 0.0f));
-        n_neg += __popcll(__ballot(v < 0.0f));
-    }
-    if (m > 0) {
-        const float step = (far - near) / (float)m;                   // :388
-        int seen = 0;
-        for (int i0 = 0; i0 < K; i0 += 64) {
-            const int i = i0 + lane;
-            const bool zero = i < K && zs[i] == 0.0f;
-            const unsigned long long zm = __ballot(zero);
-            if (zero) {
-                const int rank = seen + __popcll(zm & ((1ull << lane) - 1ull));
-                float u;
-                if (u_fill_row) u = u_fill_row[rank];
-                else u = u01(philox4x32(make_uint4((uint32_t)rank, 2u, (uint32_t)gray, (uint32_t)(gray >> 32)), key).x);
-                const float zmiss = near + (float)(n_neg + rank) * step;  // :389
-                zs[i] = zmiss + u * step;                                  // :390
-            }
-            seen += __popcll(zm);
-        }
-    }
-    int n2 = 1;
-    while (n2 < K) n2 <<= 1;
-    for (int i = K + lane; i < n2; i += 64) zs[i] = __builtin_inff();
-    __syncthreads();
-    for (int kk = 2; kk <= n2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (n2 >> 1); t += 64) {
-                const int i = 2 * t - (t & (j - 1));
-                const int l = i + j;
-                const float a = zs[i], b = zs[l];
-                const bool asc = (i & kk) == 0;
-                if ((a > b) == asc) { zs[i] = b; zs[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // stratified candidate j of a ray (sample_coarse, :53-60): t_j = linspace(0, 1-1/NC, NC)[j] + u/NC,
 // z = near*(1-t) + far*t; torch.linspace in fp32 evaluates symmetrically from both ends.

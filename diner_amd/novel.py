@@ -1,0 +1,175 @@
+"""The renderer of the fork's NOVEL / NOVEL_PE configurations (reference ``src/models/novel/nerf_novel_renderer.py`` and
+``src/models/novel_pe/pe_nerf_novel_renderer.py``) on the device: ``renderer.module: diner_amd.novel.NeRFRendererDGS``.
+
+Every candidate and every sample is moved by the offset of its nearest mesh vertex before a source view or the model sees it:
+
+* ``sample_depthguided``  -- three launches: ``diner_sample_coarse`` (the stratified depths), ``diner_deform_ray_points`` (the points
+  of those depths, deformed by ``tgt_in_offsets``) and ``diner_sample_depthguided_points`` (csrc/sampler_points.hip: the depth-guided
+  sampler on given candidate points).  One seed per call: the noise is the stream contract of ``diner_sample_depthguided``.
+* ``fill_up_uniform_samples`` -- inherited.
+* ``composite``           -- ``glue.deform_ray_points`` with both offset sets from one search, the model on the deformed points in
+  the reference's chunks, then ``diner_composite`` under autograd (``diner_composite_backward``): gradient to the model's
+  rgb-sigma, hence to its parameters, and to nothing else.
+* ``forward``             -- the reference's three stages and its output object.
+
+The point model stays PyTorch: any callable ``model(in_deformed, gen_deformed[, points], viewdirs=dirs) -> [SB,B',4]`` with ``poses``,
+``focal``, ``c``, ``image_shape`` and an ``encoder`` holding ``depths``, ``depths_std``, ``normals``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from types import SimpleNamespace
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib, deform
+from ._lib import check
+from .renderer import NeRFRendererDGS as _Renderer
+from .renderer import RenderOutput, _f32c, _ptr, _stream
+
+
+class _MapsModel:
+    """what ``_scene(model, need_latent=False)`` reads, of a model that need not be a ``PixelNeRF``: the cameras and the encoder's
+    depth / std / normal maps; the fields of the latent lookup and the positional code, which no sampler reads, take defaults"""
+
+    def __init__(self, model):
+        enc = model.encoder
+        self.poses, self.focal, self.c, self.image_shape = model.poses, model.focal, model.c, model.image_shape
+        self.encoder = SimpleNamespace(depths=enc.depths, depths_std=enc.depths_std, normals=enc.normals,
+                                       feature_padding=float(getattr(enc, "feature_padding", 0.0)))
+        self.poscode = SimpleNamespace(num_freqs=0, freqs=[1.0])
+
+
+class _CompositeFn(torch.autograd.Function):
+    """rgbsigma [SB,B,K,4] -> (weights, rgb, depth) by ``diner_composite``; backward by ``diner_composite_backward`` (gradient to
+    rgbsigma only: rays and depths are data here)"""
+
+    @staticmethod
+    def forward(ctx, rgbsigma, rays, z, white, status):
+        c = _f32c(rgbsigma)
+        SB, NR, K = z.shape
+        dev = rays.device
+        weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev)
+        rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
+        depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
+        check(_lib.lib().diner_composite(_ptr(rays), _ptr(z), _ptr(c), SB * NR, K, int(white), _ptr(rgb), _ptr(depth), _ptr(weights),
+                                         _ptr(status), _stream(dev)), "diner_composite")
+        ctx.save_for_backward(rgbsigma, rays, z)   # (the inputs themselves; rays and z arrive fp32 and contiguous from composite)
+        ctx.set_materialize_grads(False)       # an output the loss does not read hands backward None, diner_composite_backward's NULL
+        ctx.white, ctx.dtype = int(white), rgbsigma.dtype
+        return weights, rgb, depth
+
+    @staticmethod
+    @once_differentiable                       # the hand-written backward has no graph of its own: a double backward raises
+    def backward(ctx, d_weights, d_rgb, d_depth):
+        rgbsigma, rays, z = ctx.saved_tensors
+        c = _f32c(rgbsigma)
+        SB, NR, K = z.shape
+        dev = rays.device
+        g = torch.zeros((SB, NR, 3), dtype=torch.float32, device=dev) if d_rgb is None else _f32c(d_rgb)
+        gd = None if d_depth is None else _f32c(d_depth)
+        gw = None if d_weights is None else _f32c(d_weights)
+        out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=dev)
+        check(_lib.lib().diner_composite_backward(_ptr(rays), _ptr(z), _ptr(c), _ptr(g), _ptr(gd), _ptr(gw), SB * NR, K, ctx.white,
+                                                  _ptr(out), _stream(dev)), "diner_composite_backward")
+        return out.to(ctx.dtype), None, None, None, None
+
+
+class NeRFRendererDGS(_Renderer):
+    """The NOVEL renderer (reference nerf_novel_renderer.py:13-38): the constructor of the reference, and ``pass_points``: True for
+    NOVEL_PE, whose model takes the undeformed points as a third argument (pe_nerf_novel_renderer.py)."""
+
+    def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000, white_bkgd=True, pass_points=False):
+        super().__init__(n_samples=n_samples, n_depth_candidates=n_depth_candidates, n_gaussian=n_gaussian,
+                         eval_batch_size=eval_batch_size, white_bkgd=white_bkgd)
+        self.pass_points = bool(pass_points)
+
+    def deform_points(self, points, target_vertices, offsets):
+        """reference :40-50"""
+        return deform.deform_points(points, target_vertices, offsets)
+
+    @torch.no_grad()
+    def sample_depthguided(self, rays, model, n_samples, n_candidates, target_vertices, tgt_in_offsets, depth_diff_max=0.05,
+                           n_gaussian=None, *, noise=None, return_internals=False):
+        """Depth-guided short-list + gaussian samples of the DEFORMED candidates (reference :79-167): returns z [SB,NR,n_samples]
+        before fill-up (0 = empty slot).  ``noise=(u_coarse, n_gauss, u_fill)``: dense tensors (any of them None) replacing the
+        Philox streams 0 / 1 / 2 of the call's one seed.  ``return_internals``: also a dict with ``z_cand`` [SB,NR,NC], ``xyz_cand``
+        [SB,NR,NC,3], ``likelihood`` [SB,NR,NC], ``z_dg`` (the return value), ``z`` (filled and sorted) and ``seed``."""
+        G = self.n_gaussian if n_gaussian is None else n_gaussian
+        out = self._sample_deformed(rays, model, int(n_samples), int(n_candidates), G, target_vertices, tgt_in_offsets, depth_diff_max,
+                                    noise, want_lik=return_internals)
+        return (out["z_dg"], out) if return_internals else out["z_dg"]
+
+    def _sample_deformed(self, rays, model, K, NC, G, target_vertices, tgt_in_offsets, depth_diff_max, noise, want_lik):
+        r = self._check_rays(rays)
+        SB, NR, _ = r.shape
+        dev = r.device
+        sc, _keep = self._scene(_MapsModel(model), need_latent=False)
+        assert SB == sc.SB
+        cfg = self._cfg(K, NC, G, depth_diff_max)
+        u_c = n_g = u_f = None
+        if noise is not None:
+            u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
+            if u_c is not None: assert u_c.numel() == SB * NR * NC
+            if n_g is not None: assert n_g.numel() == SB * NR * G
+            if u_f is not None: assert u_f.numel() == SB * NR * K
+        L, st, seed = _lib.lib(), _stream(dev), self._next_seed()
+        z_cand = torch.empty((SB, NR, NC), dtype=torch.float32, device=dev)
+        # (the global ray index sb * NR + ray is the Philox ray counter of both launches)
+        check(L.diner_sample_coarse(_ptr(r), SB * NR, NC, _ptr(u_c), seed, _ptr(z_cand), st), "diner_sample_coarse")
+        xyz = deform.deform_ray_points(r, z_cand, target_vertices, tgt_in_offsets, method="auto")      # [SB, NR*NC, 3]
+        z = torch.empty((SB, NR, K), dtype=torch.float32, device=dev)
+        z_dg = torch.empty_like(z)
+        lik = torch.empty((SB, NR, NC), dtype=torch.float32, device=dev) if want_lik else None
+        check(L.diner_sample_depthguided_points(C.byref(sc), _ptr(r), _ptr(z_cand), _ptr(xyz), NR, C.byref(cfg), _ptr(n_g), _ptr(u_f),
+                                                seed, _ptr(z), _ptr(z_dg), _ptr(lik), st), "diner_sample_depthguided_points")
+        return dict(z_cand=z_cand, xyz_cand=xyz.view(SB, NR, NC, 3), likelihood=lik, z_dg=z_dg, z=z, seed=seed)
+
+    @staticmethod
+    def _no_data_grad(**tensors):
+        """rays, depths, vertices and offsets are data here: one that requires grad is refused, never silently left without a gradient"""
+        if not torch.is_grad_enabled():
+            return
+        for name, t in tensors.items():
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise NotImplementedError(f"diner_amd.novel.NeRFRendererDGS: {name} requires grad, but the NOVEL compositing carries "
+                                          "gradient to the model's rgb-sigma only (vertices and offsets are data, as in the reference); "
+                                          "the training path with ray and camera gradients is diner_amd.NeRFRendererDGS.forward "
+                                          "(diner_amd/training.py), which serves the plain renderer")
+
+    def composite(self, model, rays, z_samp, target_vertices, tgt_in_offsets, tgt_gen_offsets, *, _sync=False):
+        """Alpha compositing of the model's rgb-sigma on the deformed sample points (reference :394-477) -> (weights, rgb, depth).
+        Differentiable to what the model's output depends on (its parameters); rays, depths, vertices or offsets that require grad raise."""
+        self._no_data_grad(rays=rays, z_samp=z_samp, target_vertices=target_vertices, tgt_in_offsets=tgt_in_offsets,
+                           tgt_gen_offsets=tgt_gen_offsets)
+        r = self._check_rays(rays)
+        z = _f32c(z_samp.detach())
+        SB, B, K = z.shape
+        with torch.no_grad():
+            sets = deform.deform_ray_points(r, z, target_vertices, tgt_in_offsets, tgt_gen_offsets, return_points=self.pass_points)
+            dirs = r[..., None, 3:6].expand(-1, -1, K, -1).reshape(SB, B * K, 3)       # :413, :432
+        chunk = (int(self.eval_batch_size) - 1) // SB + 1                               # :433
+        split = [torch.split(t, chunk, dim=1) for t in sets]
+        vals = [model(*pts, viewdirs=d) for *pts, d in zip(*split, torch.split(dirs, chunk, dim=1))]   # :440-444
+        out = torch.cat(vals, dim=1).reshape(SB, B, K, -1)                              # :450-451
+        dev = r.device
+        self._poll_status()
+        weights, rgb, depth = _CompositeFn.apply(out, r, z, bool(self.white_bkgd), self._status_word(dev))
+        self._after_launch(dev, sync=_sync)
+        return weights, rgb, depth
+
+    def forward(self, model, rays, target_vertices, tgt_in_offsets, tgt_gen_offsets, want_weights=False, *, noise=None):
+        """Reference :511-540: sample_depthguided -> fill_up_uniform_samples -> composite; ``out.fine.rgb`` [SB,B,3],
+        ``out.fine.depth`` [SB,B], ``out.fine.weights`` [SB,B,K] iff ``want_weights``.  (The sampler kernel fills and sorts in the
+        same launch, under the call's seed: that result is what the compositing gets.)"""
+        assert len(rays.shape) == 3
+        self._no_data_grad(rays=rays, target_vertices=target_vertices, tgt_in_offsets=tgt_in_offsets, tgt_gen_offsets=tgt_gen_offsets)
+        with torch.no_grad():
+            internals = self._sample_deformed(rays, model, int(self.n_samples), int(self.n_depth_candidates), self.n_gaussian,
+                                              target_vertices, tgt_in_offsets, 0.05, noise, want_lik=False)
+        big = want_weights or rays.shape[0] * rays.shape[1] > int(self.finite_sync_rays)
+        weights, rgb, depth = self.composite(model, rays, internals["z"], target_vertices, tgt_in_offsets, tgt_gen_offsets, _sync=big)
+        return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
+
+    render_rays = forward

@@ -941,6 +941,18 @@ int diner_deform_ray_points(const float *rays, const float *z, const float *vert
                             const float *offsets2, int32_t SB, int64_t B, int32_t K, int32_t V, float *out, float *out2, float *points_out,
                             void *stream);
 
+/* ---- the depth-guided sampler on given candidate points (sampler_points.hip) ------------------------------------------------------
+ * The sampler of the NOVEL / NOVEL_PE renderers (reference src/models/novel/nerf_novel_renderer.py:79-167): diner_sample_depthguided
+ * with the position of candidate j of a ray read from xyz_cand [SB,NR,NC,3] (e.g. diner_deform_ray_points of diner_sample_coarse's
+ * depths) instead of formed as o + z d.  z_cand [SB,NR,NC] are the candidates' depths: the moments, the short-list and every output
+ * are depths.  The ray's direction still gives raydirs_cam, near / far give the likelihood's half step and the fill-up.  No candidate
+ * noise is drawn; n_gauss / u_fill (optional) replace Philox streams 1 / 2 of `seed` as in diner_sample_depthguided, whose outputs
+ * z_out [SB,NR,K] (filled and sorted), z_dg_out [SB,NR,K] and lik_out [SB,NR,NC] (both optional) these are.  The likelihood is the
+ * same device function: on xyz = o + z d the two entry points return the same bits.  NC <= 4096 (DINER_E_UNSUPPORTED beyond). */
+int diner_sample_depthguided_points(const DinerScene *scene, const float *rays, const float *z_cand, const float *xyz_cand,
+                                    int64_t NR, const DinerSamplerCfg *cfg, const float *n_gauss, const float *u_fill,
+                                    uint64_t seed, float *z_out, float *z_dg_out, float *lik_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
