@@ -73,6 +73,11 @@ class DinerLatentIndex(C.Structure):
     _fields_ = [("interp", C.c_int32), ("padding", C.c_int32)]
 
 
+class DinerNovelGen(C.Structure):
+    _fields_ = [("latent", _FP), ("h", C.c_int32), ("w", C.c_int32), ("C", C.c_int32), ("_pad", C.c_int32),
+                ("poses", _FP), ("focal", _FP), ("c", _FP), ("image_w", C.c_float), ("image_h", C.c_float)]
+
+
 class DinerLatentLevel(C.Structure):
     _fields_ = [("data", _FP), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -272,6 +277,10 @@ SYMBOLS = {
     # the depth-guided sampler on given candidate points (csrc/sampler_points.hip; the ABI version stays 3: a new entry point only)
     "diner_sample_depthguided_points": (C.c_int, [C.POINTER(DinerScene), _P, _P, _P, _I64, C.POINTER(DinerSamplerCfg), _P, _P, _U64,
                                                   _P, _P, _P, _P]),
+    # the NOVEL point model on the shape-general kernels: given points, a second (general) latent lookup (csrc/points_mlp_gen_nv.hip,
+    # points_mlp_gen_f16_nv.hip; the ABI version stays 3: a new entry point only)
+    "diner_render_points_novel": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerNovelGen),
+                                            C.POINTER(DinerMlpShape), _P, _P, _P, _P, _I64, _I32, _P, _P]),
 }
 
 _lib = None

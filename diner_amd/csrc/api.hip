@@ -128,6 +128,8 @@ int launch_points_mlp_lz(const DinerScene &, const DinerLatentIndex &, const Din
                          hipStream_t, int bicubic_pad, const float *lzmaps);
 int64_t linz_maps_floats(const DinerMlpShape &, int64_t texels);
 int launch_linz_maps(const DinerMlpShape &, const float *, int64_t, const float *, float *, hipStream_t);
+int launch_points_mlp_novel(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerMlpShape &, const float *, const float *,
+                            const float *, const float *, int64_t, float *, hipStream_t);
 }
 namespace genf16 {
 int64_t packed_floats(const DinerMlpShape &);
@@ -136,6 +138,8 @@ int launch_points_mlp(const DinerScene &, const DinerLatentIndex &, const DinerM
                       int bicubic_pad = -1);
 int launch_points_mlp_lz(const DinerScene &, const DinerLatentIndex &, const DinerMlpShape &, const float *, const float *, const float *, int64_t, int, float *,
                          hipStream_t, int bicubic_pad, const float *lzmaps);
+int launch_points_mlp_novel(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerMlpShape &, const float *, const float *,
+                            const float *, const float *, int64_t, float *, hipStream_t);
 }
 
 int launch_train_point_inputs_gen_bc(const DinerScene &, int, const float *, const float *, const float *, int64_t, int, int, float *, int64_t,
@@ -1036,6 +1040,54 @@ int diner_train_bicubic_scatter(const float *dz, const float *taps, int64_t P, i
     if (!dz || !taps || !dlatent_nhwc) return bad("train_bicubic_scatter: NULL pointer");
     if (P < 0 || C <= 0 || h <= 0 || w <= 0 || NV < 1 || sb < 0) return bad("train_bicubic_scatter: bad size");
     return launch_train_bicubic_scatter(dz, taps, P, C, h, w, NV, sb, dlatent_nhwc, (hipStream_t)stream);
+}
+
+/* ---- the NOVEL point model on the shape-general kernels (points_mlp_gen_nv.hip, points_mlp_gen_f16_nv.hip) ------------------------- */
+int diner_render_points_novel(const DinerScene *scene, const DinerLatentIndex *index, const DinerNovelGen *gen, const DinerMlpShape *shape,
+                              const float *mlp_packed, const float *xyz_in, const float *xyz_gen, const float *viewdirs, int64_t P,
+                              int32_t precision, float *rgbsigma_out, void *stream)
+{
+    const char *who = "render_points_novel";
+    int rc;
+    if (!shape) return bad("render_points_novel: shape is NULL");
+    if (!gen) return bad("render_points_novel: gen is NULL");
+    if (precision != DINER_PRECISION_FP32 && precision != DINER_PRECISION_F16X3) {
+        set_error("%s: precision=%d unknown (DINER_PRECISION_FP32 0 or DINER_PRECISION_F16X3 1)", who, precision);
+        return DINER_E_INVALID;
+    }
+    const bool f16 = precision == DINER_PRECISION_F16X3;
+    if ((rc = check_index(index, who))) return rc;   /* the 4-tap modes only: DinerLatentIndex does not carry bicubic */
+    if ((rc = gen::check_shape(*shape))) return rc;
+    const bool has_lz = shape->combine_layer > 0;    /* else neither latent is read */
+    if ((rc = check_scene(scene, has_lz))) return rc;
+    if (shape->combine_layer >= shape->n_blocks && scene->NV != 1) {
+        set_error("%s: combine_layer=%d >= n_blocks=%d never averages over views, which the reference supports for NV = 1 only "
+                  "(src/models/novel/novel_pixelnerf.py:234 reshapes (SB, NV, B, 4) to (SB, B, 4)); NV=%d", who, shape->combine_layer,
+                  shape->n_blocks, scene->NV);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (scene->C != shape->d_latent) { set_error("%s: latent channels C=%d != d_latent=%d", who, scene->C, shape->d_latent); return DINER_E_INVALID; }
+    if (gen->C != shape->d_latent) { set_error("%s: general latent channels C=%d != d_latent=%d", who, gen->C, shape->d_latent); return DINER_E_INVALID; }
+    if (scene->num_freqs != shape->num_freqs) {
+        set_error("%s: scene num_freqs=%d != shape num_freqs=%d", who, scene->num_freqs, shape->num_freqs);
+        return DINER_E_INVALID;
+    }
+    if (gen->h < 1 || gen->w < 1) { set_error("%s: general latent size h=%d, w=%d (both >= 1)", who, gen->h, gen->w); return DINER_E_INVALID; }
+    if ((int64_t)gen->h * gen->w * (gen->C / 4) > 0x7fffffffLL || (int64_t)scene->h * scene->w * (scene->C / 4) > 0x7fffffffLL)
+        return bad("render_points_novel: a latent map of 2^31 or more float4 (the tap offsets are 32-bit)");
+    if (has_lz && !gen->latent) return bad("render_points_novel: general latent is NULL");
+    if (!gen->poses || !gen->focal || !gen->c) return bad("render_points_novel: NULL general camera pointer");
+    if (!(gen->image_w > 0.f) || !(gen->image_h > 0.f)) return bad("render_points_novel: bad general image shape");
+    if (P < 0) return bad("render_points_novel: bad P");
+    if ((P + 63) / 64 > 0x7fffffffLL) { set_error("%s: too many points (%lld)", who, (long long)P); return DINER_E_INVALID; }
+    if (!mlp_packed) return bad("render_points_novel: mlp_packed is NULL");
+    if (f16 && (uintptr_t)mlp_packed % 16) return bad("render_points_novel: mlp_packed not 16-byte aligned (f16x3)");
+    if (has_lz && ((uintptr_t)gen->latent % 16 || (uintptr_t)scene->latent % 16)) return bad("render_points_novel: latent not 16-byte aligned");
+    if (P == 0 || scene->SB == 0) return DINER_OK;
+    if (!xyz_in || !xyz_gen || !viewdirs || !rgbsigma_out) return bad("render_points_novel: NULL points / viewdirs / out");
+    return (f16 ? genf16::launch_points_mlp_novel : gen::launch_points_mlp_novel)(*scene, index ? *index : k_default_index, *gen, *shape,
+                                                                                 mlp_packed, xyz_in, xyz_gen, viewdirs, P, rgbsigma_out,
+                                                                                 (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -12,12 +12,18 @@ Every candidate and every sample is moved by the offset of its nearest mesh vert
   rgb-sigma, hence to its parameters, and to nothing else.
 * ``forward``             -- the reference's three stages and its output object.
 
-The point model stays PyTorch: any callable ``model(in_deformed, gen_deformed[, points], viewdirs=dirs) -> [SB,B',4]`` with ``poses``,
-``focal``, ``c``, ``image_shape`` and an ``encoder`` holding ``depths``, ``depths_std``, ``normals``.
+The point model is any callable ``model(in_deformed, gen_deformed[, points], viewdirs=dirs) -> [SB,B',4]`` with ``poses``, ``focal``,
+``c``, ``image_shape`` and an ``encoder`` holding ``depths``, ``depths_std``, ``normals``; it runs on PyTorch unless the renderer was
+constructed with ``hip_point_model=True`` and the model is the NOVEL ``PixelNeRF`` (reference src/models/novel/novel_pixelnerf.py):
+
+* ``render_points_novel`` -- that model on the shape-general point/MLP kernels' "novel" form (csrc/points_mlp_gen_nv.hip,
+  points_mlp_gen_f16_nv.hip through ``diner_render_points_novel``): given points, per-point viewdirs, and the model's learned
+  ``gen_latent`` looked up at the general camera and added to the encoder's latent.  Inference only.
 """
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from types import SimpleNamespace
 
 import torch
@@ -26,7 +32,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib, deform
 from ._lib import check
 from .renderer import NeRFRendererDGS as _Renderer
-from .renderer import RenderOutput, _f32c, _ptr, _stream
+from .renderer import RenderOutput, _f32c, _ptr, _Sources, _stream
 
 
 class _MapsModel:
@@ -80,10 +86,20 @@ class NeRFRendererDGS(_Renderer):
     """The NOVEL renderer (reference nerf_novel_renderer.py:13-38): the constructor of the reference, and ``pass_points``: True for
     NOVEL_PE, whose model takes the undeformed points as a third argument (pe_nerf_novel_renderer.py)."""
 
-    def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000, white_bkgd=True, pass_points=False):
+    def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000, white_bkgd=True, pass_points=False,
+                 hip_point_model=False, f16x3_any_shape=False):
         super().__init__(n_samples=n_samples, n_depth_candidates=n_depth_candidates, n_gaussian=n_gaussian,
-                         eval_batch_size=eval_batch_size, white_bkgd=white_bkgd)
+                         eval_batch_size=eval_batch_size, white_bkgd=white_bkgd, f16x3_any_shape=f16x3_any_shape)
         self.pass_points = bool(pass_points)
+        # composite() evaluates the NOVEL PixelNeRF with one render_points_novel call for all B K points instead of the chunked
+        # PyTorch calls, when gradients are off (or no parameter of the model requires grad), the model is recognisably that one (its
+        # gen_latent and gen_* buffers, a fusion MLP _validate accepts, no deformation_layer), pass_points is False and the encoder's
+        # lookup is a 4-tap mode.  Anything else -- training, NOVEL_PE, a bicubic encoder, another callable -- goes the PyTorch way,
+        # as with the switch off.  last_route: "novel_points_gen" / "novel_points_gen_f16" (precision == "f16x3" with f16x3_any_shape,
+        # as on the plain renderer) or "torch".  Opt-in; a plain attribute, so that a config can set it (renderer.kwargs.hip_point_model).
+        self.hip_point_model = bool(hip_point_model)
+        self._gen_latent_key = self._gen_latent_pack = None      # the model's gen_latent, NHWC
+        self._gen_cam_key = self._gen_cam_pack = None            # its general cameras, fp32 and contiguous
 
     def deform_points(self, points, target_vertices, offsets):
         """reference :40-50"""
@@ -138,6 +154,114 @@ class NeRFRendererDGS(_Renderer):
                                           "the training path with ray and camera gradients is diner_amd.NeRFRendererDGS.forward "
                                           "(diner_amd/training.py), which serves the plain renderer")
 
+    # ------------------------------------------------------------------------------------------------------------------------------
+    # the NOVEL point model on the HIP kernels
+    # ------------------------------------------------------------------------------------------------------------------------------
+    _GEN_STATE = ("gen_latent", "gen_poses", "gen_focal", "gen_c", "gen_image_shape")
+
+    def _novel_gen(self, model, dev):
+        """``model``'s general latent and cameras as a DinerNovelGen (+ the tensors it points into).  gen_latent [C,h,w] is packed to
+        NHWC by diner_pack_latent (N = 1) and cached under a _Sources key like the encoder's latent: an optimizer step re-packs it."""
+        gl = model.gen_latent
+        if gl.dim() != 3:
+            raise ValueError(f"gen_latent must be [C, h, w], not {tuple(gl.shape)}")
+        if self._gen_latent_key is None or not self._gen_latent_key.valid_for([gl]):
+            src = _f32c(gl).to(dev)
+            Cc, h, w = src.shape
+            pack = torch.empty((h, w, Cc), dtype=torch.float32, device=dev)
+            check(_lib.lib().diner_pack_latent(_ptr(src), 1, Cc, h, w, _ptr(pack), _stream(dev)), "diner_pack_latent")
+            torch.cuda.current_stream(dev).synchronize()     # `src` may be a temporary
+            self._gen_latent_pack, self._gen_latent_key = pack, _Sources([gl])
+        cams = [model.gen_poses, model.gen_focal, model.gen_c, model.gen_image_shape]
+        if self._gen_cam_key is None or not self._gen_cam_key.valid_for(cams):
+            poses = _f32c(model.gen_poses).to(dev)
+            poses = poses.reshape(-1, *poses.shape[-2:])                       # [SB,1,4,4] (encode_gen) or [SB,4,4]; 3 x 4 accepted
+            if poses.shape[-2:] != (4, 4):
+                full = torch.zeros((poses.shape[0], 4, 4), dtype=torch.float32, device=dev)
+                full[:, :3, :] = poses[:, :3, :]
+                full[:, 3, 3] = 1
+                poses = full
+            ishape = [float(v) for v in model.gen_image_shape.detach().float().cpu()]   # (W, H), novel_pixelnerf.py:80-81
+            self._gen_cam_pack = (poses.contiguous(), _f32c(model.gen_focal).to(dev).reshape(-1, 2).contiguous(),
+                                  _f32c(model.gen_c).to(dev).reshape(-1, 2).contiguous(), ishape)
+            self._gen_cam_key = _Sources(cams)
+        pack, (poses, focal, c, ishape) = self._gen_latent_pack, self._gen_cam_pack
+        g = _lib.DinerNovelGen()
+        g.latent, (g.h, g.w, g.C) = pack.data_ptr(), pack.shape
+        g.poses, g.focal, g.c = poses.data_ptr(), focal.data_ptr(), c.data_ptr()
+        g.image_w, g.image_h = ishape
+        return g, (pack, poses, focal, c)
+
+    def memory_report(self, model=None, rays_per_call=None, n_views=None):
+        """the plain renderer's report + ``cached["gen_latent_nhwc"]``: the packed copy of the NOVEL model's general latent"""
+        rep = super().memory_report(model, rays_per_call=rays_per_call, n_views=n_views)
+        pack = self._gen_latent_pack
+        rep["cached"]["gen_latent_nhwc"] = 0 if pack is None else pack.numel() * pack.element_size()
+        rep["cached"]["total"] = sum(v for k, v in rep["cached"].items() if k != "total")
+        return rep
+
+    @torch.no_grad()
+    def render_points_novel(self, model, in_points, gen_points, viewdirs):
+        """rgb-sigma of the NOVEL PixelNeRF (reference novel_pixelnerf.py:143-242) at given points, in one kernel launch:
+        ``in_points`` / ``gen_points`` / ``viewdirs`` [SB,P,3] -> [SB,P,4].  Any fusion MLP of the shape-general envelope, the standard
+        one included; every 4-tap lookup mode of the encoder, applied to both latents.  Exact fp32, or f16x3 under ``precision ==
+        "f16x3"`` with ``f16x3_any_shape``.  Raises ``NotImplementedError`` for what this form does not serve (a bicubic encoder)."""
+        missing = [k for k in self._GEN_STATE if getattr(model, k, None) is None]
+        if missing:
+            raise TypeError(f"render_points_novel: the model has no {', '.join(missing)} (not the NOVEL PixelNeRF, or encode_gen() was not called)")
+        if getattr(model.encoder, "index_interp", "bilinear") == "bicubic":
+            raise NotImplementedError("render_points_novel: index_interp='bicubic' is not served by the novel point kernels "
+                                      "(bilinear or nearest, any padding); composite() evaluates such a model with PyTorch")
+        shape = self._validate(model)
+        xi, xg, vd = _f32c(in_points), _f32c(gen_points), _f32c(viewdirs)
+        if not xi.is_cuda:
+            raise RuntimeError("diner_amd.novel.NeRFRendererDGS runs on the GPU only (points are on %s)" % xi.device)
+        assert xi.dim() == 3 and xi.shape[-1] == 3 and xg.shape == xi.shape and vd.shape == xi.shape
+        SB, P, _ = xi.shape
+        dev = xi.device
+        f16 = self.precision == "f16x3" and bool(self.f16x3_any_shape)
+        if f16:
+            self.effective_precision = "f16x3"
+        else:
+            if self.precision != "fp32" and not self._warned_precision:
+                warnings.warn(f"diner_amd.novel.NeRFRendererDGS: precision={self.precision!r} reaches the NOVEL point model only with "
+                              "f16x3_any_shape set; it runs in exact fp32 (renderer.effective_precision)", stacklevel=3)
+                self._warned_precision = True
+            self.effective_precision = "fp32"
+        packed, _gshape = self._gen_packs(model, shape, f16)
+        sc, _keep = self._scene(model, need_latent=True)
+        assert SB == sc.SB                                                      # novel_pixelnerf.py:156
+        g, _gkeep = self._novel_gen(model, dev)
+        ix = self._latent_index(model)
+        cs = shape.c_struct()
+        out = torch.empty((SB, P, 4), dtype=torch.float32, device=dev)
+        check(_lib.lib().diner_render_points_novel(C.byref(sc), C.byref(ix) if ix is not None else None, C.byref(g), C.byref(cs), _ptr(packed),
+                                                   _ptr(xi), _ptr(xg), _ptr(vd), P, _lib.PRECISIONS["f16x3" if f16 else "fp32"], _ptr(out),
+                                                   _stream(dev)), "diner_render_points_novel")
+        self.last_route, self.last_binding = ("novel_points_gen_f16" if f16 else "novel_points_gen"), "ctypes"
+        return out
+
+    def _hip_point_model_ok(self, model) -> bool:
+        """composite() may hand ``model`` to render_points_novel: see ``hip_point_model`` in the constructor"""
+        if not self.hip_point_model or self.pass_points:
+            return False
+        if any(getattr(model, k, None) is None for k in self._GEN_STATE + ("mlp_fine", "poscode", "depthcode", "encoder")):
+            return False
+        if getattr(model, "deformation_layer", None) is not None:              # NOVEL_PE
+            return False
+        enc = model.encoder
+        if getattr(enc, "latent", None) is None or getattr(enc, "index_interp", "bilinear") == "bicubic":
+            return False
+        if torch.is_grad_enabled():
+            params = list(model.parameters()) if isinstance(model, torch.nn.Module) else list(model.mlp_fine.parameters())
+            if any(p.requires_grad for p in params + [model.gen_latent, enc.latent]):
+                return False
+        try:
+            self._validate(model)
+        except (NotImplementedError, AttributeError):
+            return False
+        return True
+
     def composite(self, model, rays, z_samp, target_vertices, tgt_in_offsets, tgt_gen_offsets, *, _sync=False):
         """Alpha compositing of the model's rgb-sigma on the deformed sample points (reference :394-477) -> (weights, rgb, depth).
         Differentiable to what the model's output depends on (its parameters); rays, depths, vertices or offsets that require grad raise."""
@@ -149,10 +273,14 @@ class NeRFRendererDGS(_Renderer):
         with torch.no_grad():
             sets = deform.deform_ray_points(r, z, target_vertices, tgt_in_offsets, tgt_gen_offsets, return_points=self.pass_points)
             dirs = r[..., None, 3:6].expand(-1, -1, K, -1).reshape(SB, B * K, 3)       # :413, :432
-        chunk = (int(self.eval_batch_size) - 1) // SB + 1                               # :433
-        split = [torch.split(t, chunk, dim=1) for t in sets]
-        vals = [model(*pts, viewdirs=d) for *pts, d in zip(*split, torch.split(dirs, chunk, dim=1))]   # :440-444
-        out = torch.cat(vals, dim=1).reshape(SB, B, K, -1)                              # :450-451
+        if self._hip_point_model_ok(model):
+            out = self.render_points_novel(model, sets[0], sets[1], dirs).reshape(SB, B, K, 4)
+        else:
+            chunk = (int(self.eval_batch_size) - 1) // SB + 1                           # :433
+            split = [torch.split(t, chunk, dim=1) for t in sets]
+            vals = [model(*pts, viewdirs=d) for *pts, d in zip(*split, torch.split(dirs, chunk, dim=1))]   # :440-444
+            out = torch.cat(vals, dim=1).reshape(SB, B, K, -1)                          # :450-451
+            self.last_route = "torch"
         dev = r.device
         self._poll_status()
         weights, rgb, depth = _CompositeFn.apply(out, r, z, bool(self.white_bkgd), self._status_word(dev))

@@ -953,6 +953,32 @@ int diner_sample_depthguided_points(const DinerScene *scene, const float *rays, 
                                     int64_t NR, const DinerSamplerCfg *cfg, const float *n_gauss, const float *u_fill,
                                     uint64_t seed, float *z_out, float *z_dg_out, float *lik_out, void *stream);
 
+/* ---- the NOVEL point model on the shape-general point/MLP kernels (points_mlp_gen_nv.hip, points_mlp_gen_f16_nv.hip) ---------------
+ * The fork's NOVEL PixelNeRF (reference src/models/novel/novel_pixelnerf.py:143-242): diner_render_points_gen at points that are
+ * given instead of formed as o + z d, with a second, learned latent added to the encoder's.  New symbols only: DINER_ABI_VERSION stays 3.
+ *   xyz_in   [SB,P,3]  goes to the source cameras, the positional code, the depth feature and the encoder's latent lookup
+ *   xyz_gen  [SB,P,3]  is projected by scene sb's general camera; gen->latent is looked up there with the scene's feature_padding
+ *                      (scaled by the general latent's own size) and the lookup mode of `index`, and added to the encoder's lookup in
+ *                      every view before lin_z: final_latent = gen_latent + latent (:196)
+ *   viewdirs [SB,P,3]  replace the ray direction
+ * index: NULL = bilinear / border; every 4-tap DinerLatentIndex mode is served and applies to both lookups (bicubic and the lin_z-map
+ * forms are not).  precision: DINER_PRECISION_FP32 with mlp_packed from diner_pack_mlp_gen, DINER_PRECISION_F16X3 with mlp_packed from
+ * diner_pack_mlp_gen_f16.  Any shape of the shape-general envelope, the standard one included.  No atomics: two runs agree bit for
+ * bit.  Before any launch: DINER_E_INVALID for a NULL pointer, an unknown index or precision, P < 0, h or w < 1, C != d_latent for
+ * either latent; DINER_E_UNSUPPORTED for a shape outside the envelope; P = 0 or SB = 0: DINER_OK, nothing is launched. */
+typedef struct DinerNovelGen {
+    const float *latent;     /* [h, w, C] NHWC: diner_pack_latent of gen_latent [C,h,w] with N = 1; not read when combine_layer = 0 */
+    int32_t h, w, C;         /* its size (need not be the encoder latent's) and channels (= d_latent) */
+    int32_t _pad;
+    const float *poses;      /* [SB,4,4] world -> general camera, one per scene */
+    const float *focal;      /* [SB,2] */
+    const float *c;          /* [SB,2] */
+    float image_w, image_h;  /* gen_image_shape (W, H) */
+} DinerNovelGen;
+int diner_render_points_novel(const DinerScene *scene, const DinerLatentIndex *index, const DinerNovelGen *gen, const DinerMlpShape *shape,
+                              const float *mlp_packed, const float *xyz_in, const float *xyz_gen, const float *viewdirs, int64_t P,
+                              int32_t precision, float *rgbsigma_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
