@@ -78,6 +78,12 @@ class DinerNovelGen(C.Structure):
                 ("poses", _FP), ("focal", _FP), ("c", _FP), ("image_w", C.c_float), ("image_h", C.c_float)]
 
 
+class DinerNovelPe(C.Structure):
+    _fields_ = [("map", _FP), ("head", _FP), ("src_pe", _FP), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("tgt_pe", _FP), ("tgt_h", C.c_int32), ("tgt_w", C.c_int32),
+                ("poses", _FP), ("focal", _FP), ("c", _FP), ("image_w", C.c_float), ("image_h", C.c_float)]
+
+
 class DinerLatentLevel(C.Structure):
     _fields_ = [("data", _FP), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -281,6 +287,12 @@ SYMBOLS = {
     # points_mlp_gen_f16_nv.hip; the ABI version stays 3: a new entry point only)
     "diner_render_points_novel": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerNovelGen),
                                             C.POINTER(DinerMlpShape), _P, _P, _P, _P, _I64, _I32, _P, _P]),
+    # the NOVEL_PE point model: a third point set, two pos-encoding lookups, the deformation layer hoisted onto the latent's texels
+    # (csrc/points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip, novel_pe_map.hip; new entry points only)
+    "diner_novel_pe_map_floats": (_I64, [C.POINTER(DinerScene)]),
+    "diner_pack_novel_pe_map": (C.c_int, [C.POINTER(DinerScene), _P, _P, _P]),
+    "diner_render_points_novel_pe": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerNovelGen),
+                                               C.POINTER(DinerNovelPe), C.POINTER(DinerMlpShape), _P, _P, _P, _P, _P, _I64, _I32, _P, _P]),
 }
 
 _lib = None

@@ -130,6 +130,9 @@ int64_t linz_maps_floats(const DinerMlpShape &, int64_t texels);
 int launch_linz_maps(const DinerMlpShape &, const float *, int64_t, const float *, float *, hipStream_t);
 int launch_points_mlp_novel(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerMlpShape &, const float *, const float *,
                             const float *, const float *, int64_t, float *, hipStream_t);
+int launch_points_mlp_novel_pe(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerNovelPe &, const DinerMlpShape &,
+                               const float *, const float *, const float *, const float *, const float *, int64_t, float *, hipStream_t);
+int launch_novel_pe_map(const float *, int64_t, int, const float *, float *, hipStream_t);
 }
 namespace genf16 {
 int64_t packed_floats(const DinerMlpShape &);
@@ -140,6 +143,8 @@ int launch_points_mlp_lz(const DinerScene &, const DinerLatentIndex &, const Din
                          hipStream_t, int bicubic_pad, const float *lzmaps);
 int launch_points_mlp_novel(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerMlpShape &, const float *, const float *,
                             const float *, const float *, int64_t, float *, hipStream_t);
+int launch_points_mlp_novel_pe(const DinerScene &, const DinerLatentIndex &, const DinerNovelGen &, const DinerNovelPe &, const DinerMlpShape &,
+                               const float *, const float *, const float *, const float *, const float *, int64_t, float *, hipStream_t);
 }
 
 int launch_train_point_inputs_gen_bc(const DinerScene &, int, const float *, const float *, const float *, int64_t, int, int, float *, int64_t,
@@ -1088,6 +1093,104 @@ int diner_render_points_novel(const DinerScene *scene, const DinerLatentIndex *i
     return (f16 ? genf16::launch_points_mlp_novel : gen::launch_points_mlp_novel)(*scene, index ? *index : k_default_index, *gen, *shape,
                                                                                  mlp_packed, xyz_in, xyz_gen, viewdirs, P, rgbsigma_out,
                                                                                  (hipStream_t)stream);
+}
+
+/* ---- the NOVEL_PE point model (points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip; the deformation map: novel_pe_map.hip) --------- */
+static int check_novel_pe_map_scene(const DinerScene *scene, const char *who)
+{
+    if (!scene) { set_error("%s: scene is NULL", who); return DINER_E_INVALID; }
+    if (scene->SB < 0 || scene->NV <= 0 || scene->h <= 0 || scene->w <= 0) { set_error("%s: bad SB / NV / h / w", who); return DINER_E_INVALID; }
+    if (scene->C < 8 || scene->C % 8) { set_error("%s: latent channels C=%d (a multiple of 8, >= 8)", who, scene->C); return DINER_E_INVALID; }
+    if (scene->C + 8 > 1024) {
+        set_error("%s: latent channels C=%d unsupported (the fusion MLP's padded d_latent = C + 8 must not exceed 1024)", who, scene->C);
+        return DINER_E_UNSUPPORTED;
+    }
+    return DINER_OK;
+}
+
+int64_t diner_novel_pe_map_floats(const DinerScene *scene)
+{
+    const int rc = check_novel_pe_map_scene(scene, "novel_pe_map_floats");
+    if (rc) return rc;
+    return (int64_t)scene->SB * scene->NV * scene->h * scene->w * scene->C;
+}
+
+int diner_pack_novel_pe_map(const DinerScene *scene, const float *w_latent_part, float *map_out, void *stream)
+{
+    const int rc = check_novel_pe_map_scene(scene, "pack_novel_pe_map");
+    if (rc) return rc;
+    if (!w_latent_part || !map_out) return bad("pack_novel_pe_map: NULL pointer");
+    if (!scene->latent) return bad("pack_novel_pe_map: scene latent is NULL");
+    if ((uintptr_t)scene->latent % 16) return bad("pack_novel_pe_map: latent not 16-byte aligned");
+    return gen::launch_novel_pe_map(scene->latent, (int64_t)scene->SB * scene->NV * scene->h * scene->w, scene->C, w_latent_part, map_out,
+                                    (hipStream_t)stream);
+}
+
+int diner_render_points_novel_pe(const DinerScene *scene, const DinerLatentIndex *index, const DinerNovelGen *gen, const DinerNovelPe *pe,
+                                 const DinerMlpShape *shape, const float *mlp_packed, const float *xyz_in, const float *xyz_gen,
+                                 const float *xyz_tgt, const float *viewdirs, int64_t P, int32_t precision, float *rgbsigma_out,
+                                 void *stream)
+{
+    const char *who = "render_points_novel_pe";
+    int rc;
+    if (!shape) return bad("render_points_novel_pe: shape is NULL");
+    if (!gen) return bad("render_points_novel_pe: gen is NULL");
+    if (!pe) return bad("render_points_novel_pe: pe is NULL");
+    if (precision != DINER_PRECISION_FP32 && precision != DINER_PRECISION_F16X3) {
+        set_error("%s: precision=%d unknown (DINER_PRECISION_FP32 0 or DINER_PRECISION_F16X3 1)", who, precision);
+        return DINER_E_INVALID;
+    }
+    const bool f16 = precision == DINER_PRECISION_F16X3;
+    if ((rc = check_index(index, who))) return rc;   /* the 4-tap modes only: DinerLatentIndex does not carry bicubic */
+    if ((rc = gen::check_shape(*shape))) return rc;  /* d_latent = C + 8 <= 1024 */
+    const bool has_lz = shape->combine_layer > 0;    /* else no latent, map or pos-encoding is read */
+    if ((rc = check_scene(scene, false))) return rc;
+    if (shape->combine_layer >= shape->n_blocks && scene->NV != 1) {
+        set_error("%s: combine_layer=%d >= n_blocks=%d never averages over views, which the reference supports for NV = 1 only "
+                  "(src/models/novel_pe/pe_novel_pixelnerf.py:284 reshapes (SB, NV, B, 4) to (SB, B, 4)); NV=%d", who, shape->combine_layer,
+                  shape->n_blocks, scene->NV);
+        return DINER_E_UNSUPPORTED;
+    }
+    if (scene->C != shape->d_latent - 8) {
+        set_error("%s: latent channels C=%d != d_latent - 8 = %d (the MLP's latent input is C + 6 columns, padded to C + 8)", who, scene->C,
+                  shape->d_latent - 8);
+        return DINER_E_INVALID;
+    }
+    if (gen->C != shape->d_latent - 8) {
+        set_error("%s: general latent channels C=%d != d_latent - 8 = %d", who, gen->C, shape->d_latent - 8);
+        return DINER_E_INVALID;
+    }
+    if (scene->num_freqs != shape->num_freqs) {
+        set_error("%s: scene num_freqs=%d != shape num_freqs=%d", who, scene->num_freqs, shape->num_freqs);
+        return DINER_E_INVALID;
+    }
+    if (scene->h < 1 || scene->w < 1) { set_error("%s: deformation map size h=%d, w=%d (both >= 1)", who, scene->h, scene->w); return DINER_E_INVALID; }
+    if (gen->h < 1 || gen->w < 1) { set_error("%s: general latent size h=%d, w=%d (both >= 1)", who, gen->h, gen->w); return DINER_E_INVALID; }
+    if (pe->src_h < 1 || pe->src_w < 1) { set_error("%s: source pos-encoding size h=%d, w=%d (both >= 1)", who, pe->src_h, pe->src_w); return DINER_E_INVALID; }
+    if (pe->tgt_h < 1 || pe->tgt_w < 1) { set_error("%s: target pos-encoding size h=%d, w=%d (both >= 1)", who, pe->tgt_h, pe->tgt_w); return DINER_E_INVALID; }
+    if (scene->C < 8) { set_error("%s: d_latent=%d leaves no latent channel (C = d_latent - 8 >= 8)", who, shape->d_latent); return DINER_E_UNSUPPORTED; }
+    if ((int64_t)gen->h * gen->w * (gen->C / 4) > 0x7fffffffLL || (int64_t)scene->h * scene->w * (scene->C / 4) > 0x7fffffffLL)
+        return bad("render_points_novel_pe: a latent map of 2^31 or more float4 (the tap offsets are 32-bit)");
+    if ((int64_t)pe->src_h * pe->src_w > 0x7fffffffLL || (int64_t)pe->tgt_h * pe->tgt_w > 0x7fffffffLL)
+        return bad("render_points_novel_pe: a pos-encoding map of 2^31 or more texels (the tap offsets are 32-bit)");
+    if (has_lz && !gen->latent) return bad("render_points_novel_pe: general latent is NULL");
+    if (has_lz && (!pe->map || !pe->head || !pe->src_pe || !pe->tgt_pe)) return bad("render_points_novel_pe: NULL map / head / pos-encoding pointer");
+    if (!gen->poses || !gen->focal || !gen->c) return bad("render_points_novel_pe: NULL general camera pointer");
+    if (!pe->poses || !pe->focal || !pe->c) return bad("render_points_novel_pe: NULL target camera pointer");
+    if (!(gen->image_w > 0.f) || !(gen->image_h > 0.f)) return bad("render_points_novel_pe: bad general image shape");
+    if (!(pe->image_w > 0.f) || !(pe->image_h > 0.f)) return bad("render_points_novel_pe: bad target image shape");
+    if (P < 0) return bad("render_points_novel_pe: bad P");
+    if ((P + 63) / 64 > 0x7fffffffLL) { set_error("%s: too many points (%lld)", who, (long long)P); return DINER_E_INVALID; }
+    if (!mlp_packed) return bad("render_points_novel_pe: mlp_packed is NULL");
+    if (f16 && (uintptr_t)mlp_packed % 16) return bad("render_points_novel_pe: mlp_packed not 16-byte aligned (f16x3)");
+    if (has_lz && ((uintptr_t)gen->latent % 16 || (uintptr_t)pe->map % 16 || (uintptr_t)pe->head % 16 || (uintptr_t)pe->src_pe % 16 ||
+                   (uintptr_t)pe->tgt_pe % 16))
+        return bad("render_points_novel_pe: latent / map / head / pos-encoding not 16-byte aligned");
+    if (P == 0 || scene->SB == 0) return DINER_OK;
+    if (!xyz_in || !xyz_gen || !xyz_tgt || !viewdirs || !rgbsigma_out) return bad("render_points_novel_pe: NULL points / viewdirs / out");
+    return (f16 ? genf16::launch_points_mlp_novel_pe : gen::launch_points_mlp_novel_pe)(
+        *scene, index ? *index : k_default_index, *gen, *pe, *shape, mlp_packed, xyz_in, xyz_gen, xyz_tgt, viewdirs, P, rgbsigma_out,
+        (hipStream_t)stream);
 }
 
 }  // extern "C"

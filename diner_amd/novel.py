@@ -19,6 +19,10 @@ constructed with ``hip_point_model=True`` and the model is the NOVEL ``PixelNeRF
 * ``render_points_novel`` -- that model on the shape-general point/MLP kernels' "novel" form (csrc/points_mlp_gen_nv.hip,
   points_mlp_gen_f16_nv.hip through ``diner_render_points_novel``): given points, per-point viewdirs, and the model's learned
   ``gen_latent`` looked up at the general camera and added to the encoder's latent.  Inference only.
+* ``render_points_novel_pe`` -- with ``pass_points``, the NOVEL_PE ``PixelNeRF`` (reference src/models/novel_pe/pe_novel_pixelnerf.py)
+  on the "novel_pe" form (csrc/points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip through ``diner_render_points_novel_pe``): a
+  third point set for the target camera, two 3-channel pos-encoding lookups, and the deformation layer applied to the latent's
+  texels once per encode (csrc/novel_pe_map.hip).  Inference only.
 """
 from __future__ import annotations
 
@@ -45,6 +49,17 @@ class _MapsModel:
         self.encoder = SimpleNamespace(depths=enc.depths, depths_std=enc.depths_std, normals=enc.normals,
                                        feature_padding=float(getattr(enc, "feature_padding", 0.0)))
         self.poscode = SimpleNamespace(num_freqs=0, freqs=[1.0])
+
+
+class _PaddedMlp:
+    """the NOVEL_PE model's fusion MLP as the point kernels see it: d_latent = C + 6 padded to C + 8, ``lin_z`` the padded copies of
+    ``NeRFRendererDGS._pe_mlp_pack`` (None where only the shape is read); every other attribute is the MLP's own"""
+
+    def __init__(self, mlp, lin_z):
+        self._mlp, self.lin_z, self.d_latent = mlp, lin_z, int(mlp.d_latent) + 2
+
+    def __getattr__(self, k):
+        return getattr(self._mlp, k)
 
 
 class _CompositeFn(torch.autograd.Function):
@@ -94,12 +109,20 @@ class NeRFRendererDGS(_Renderer):
         # composite() evaluates the NOVEL PixelNeRF with one render_points_novel call for all B K points instead of the chunked
         # PyTorch calls, when gradients are off (or no parameter of the model requires grad), the model is recognisably that one (its
         # gen_latent and gen_* buffers, a fusion MLP _validate accepts, no deformation_layer), pass_points is False and the encoder's
-        # lookup is a 4-tap mode.  Anything else -- training, NOVEL_PE, a bicubic encoder, another callable -- goes the PyTorch way,
+        # lookup is a 4-tap mode.  Anything else -- training, a bicubic encoder, another callable -- goes the PyTorch way,
         # as with the switch off.  last_route: "novel_points_gen" / "novel_points_gen_f16" (precision == "f16x3" with f16x3_any_shape,
         # as on the plain renderer) or "torch".  Opt-in; a plain attribute, so that a config can set it (renderer.kwargs.hip_point_model).
         self.hip_point_model = bool(hip_point_model)
         self._gen_latent_key = self._gen_latent_pack = None      # the model's gen_latent, NHWC
         self._gen_cam_key = self._gen_cam_pack = None            # its general cameras, fp32 and contiguous
+        # With pass_points the same switch serves the NOVEL_PE PixelNeRF (a deformation_layer Linear(C + 6 -> C), the gen_* and tgt_*
+        # state, pos_encodings; a fusion MLP inside the envelope once its d_latent C + 6 is padded to C + 8) through
+        # render_points_novel_pe: last_route "novel_pe_points_gen" / "novel_pe_points_gen_f16".  Its packs, each under a _Sources key:
+        self._pe_linz_key = self._pe_linz_pad = None             # lin_z[b].weight padded with two zero columns
+        self._pe_map_key = self._pe_map_pack = None              # the deformation map W_d[:, :C] . latent (encoder.latent, deformation_layer.weight)
+        self._pe_head_key = self._pe_head_pack = None            # the [C][8] head table (deformation_layer.weight, .bias)
+        self._pe_pos_key = self._pe_pos_pack = None              # pos_encodings and tgt_pos_encoding, NHWC with 4 channels
+        self._pe_cam_key = self._pe_cam_pack = None              # the target cameras
 
     def deform_points(self, points, target_vertices, offsets):
         """reference :40-50"""
@@ -193,10 +216,14 @@ class NeRFRendererDGS(_Renderer):
         return g, (pack, poses, focal, c)
 
     def memory_report(self, model=None, rays_per_call=None, n_views=None):
-        """the plain renderer's report + ``cached["gen_latent_nhwc"]``: the packed copy of the NOVEL model's general latent"""
+        """the plain renderer's report + ``cached["gen_latent_nhwc"]``: the packed copy of the NOVEL model's general latent, and of the
+        NOVEL_PE route ``cached["novel_pe_map"]`` (the deformation map: the latent's byte size) and ``cached["novel_pe_pos_encodings"]``
+        (both packed pos-encoding maps); 0 until that route has run"""
         rep = super().memory_report(model, rays_per_call=rays_per_call, n_views=n_views)
-        pack = self._gen_latent_pack
-        rep["cached"]["gen_latent_nhwc"] = 0 if pack is None else pack.numel() * pack.element_size()
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
+        rep["cached"]["gen_latent_nhwc"] = nb(self._gen_latent_pack)
+        rep["cached"]["novel_pe_map"] = nb(self._pe_map_pack)
+        rep["cached"]["novel_pe_pos_encodings"] = sum(nb(t) for t in (self._pe_pos_pack or ()))
         rep["cached"]["total"] = sum(v for k, v in rep["cached"].items() if k != "total")
         return rep
 
@@ -241,6 +268,171 @@ class NeRFRendererDGS(_Renderer):
         self.last_route, self.last_binding = ("novel_points_gen_f16" if f16 else "novel_points_gen"), "ctypes"
         return out
 
+    # ------------------------------------------------------------------------------------------------------------------------------
+    # the NOVEL_PE point model on the HIP kernels
+    # ------------------------------------------------------------------------------------------------------------------------------
+    _PE_STATE = _GEN_STATE + ("deformation_layer", "pos_encodings", "tgt_pos_encoding", "tgt_poses", "tgt_focal", "tgt_c", "tgt_image_shape")
+
+    def _validate_pe(self, model):
+        """the shape of the NOVEL_PE model's fusion MLP as the kernels see it: d_latent = C + 6 padded to C + 8, which must lie in the
+        shape-general envelope (``_validate`` keeps refusing C + 6 for every other route)"""
+        dl = getattr(model, "deformation_layer", None)
+        Cc = int(getattr(dl, "out_features", -1))
+        if dl is None or int(dl.in_features) != Cc + 6 or int(model.mlp_fine.d_latent) != Cc + 6:
+            raise NotImplementedError("not the NOVEL_PE PixelNeRF: deformation_layer must be Linear(C + 6 -> C) and the fusion MLP's "
+                                      "d_latent C + 6 (pe_novel_pixelnerf.py:21-28)")
+        if Cc < 8 or Cc % 8:
+            raise NotImplementedError(f"encoder latent_size C={Cc} unsupported by the NOVEL_PE point kernels (a multiple of 8 in [8, 1016])")
+        shim = SimpleNamespace(encoder=model.encoder, mlp_fine=_PaddedMlp(model.mlp_fine, None), poscode=model.poscode,
+                               depthcode=model.depthcode)
+        return self._validate(shim)
+
+    def _pe_mlp_pack(self, model, shape, f16):
+        """the packed image of the fusion MLP with every lin_z[b].weight [d_hidden, C + 6] padded with two zero columns: on copies, cached
+        under the weights they were made from; the packer's own cache then sees stable tensors"""
+        mlp = model.mlp_fine
+        nlz = min(shape.combine_layer, shape.n_blocks)
+        src = [mlp.lin_z[b].weight for b in range(nlz)]
+        if self._pe_linz_key is None or not self._pe_linz_key.valid_for(src):
+            pads = [torch.nn.functional.pad(_f32c(w.detach()), (0, 2)).contiguous() for w in src]
+            self._pe_linz_pad = [SimpleNamespace(weight=p, bias=mlp.lin_z[b].bias) for b, p in enumerate(pads)]
+            self._pe_linz_key = _Sources(src)
+        shim = SimpleNamespace(mlp_fine=_PaddedMlp(mlp, self._pe_linz_pad))
+        return self._mlp_shape_general(shim, shape, f16)
+
+    @staticmethod
+    def _cams(poses, focal, c, image_shape, dev):
+        """one camera per scene, [SB,1,..] (encode_gen / encode_tgt) or [SB,..]; 3 x 4 poses accepted -> fp32, contiguous, (W, H)"""
+        poses = _f32c(poses).to(dev)
+        poses = poses.reshape(-1, *poses.shape[-2:])
+        if poses.shape[-2:] != (4, 4):
+            full = torch.zeros((poses.shape[0], 4, 4), dtype=torch.float32, device=dev)
+            full[:, :3, :] = poses[:, :3, :]
+            full[:, 3, 3] = 1
+            poses = full
+        ishape = [float(v) for v in image_shape.detach().float().cpu()]
+        return poses.contiguous(), _f32c(focal).to(dev).reshape(-1, 2).contiguous(), _f32c(c).to(dev).reshape(-1, 2).contiguous(), ishape
+
+    def _novel_pe(self, model, sc, latent, dev, need_maps):
+        """``model``'s deformation map, head table, pos-encoding maps and target cameras as a DinerNovelPe (+ the tensors it points into),
+        each cached under the tensors it was made from: an in-place update of one rebuilds its pack.  ``latent``: the NHWC pack ``sc``
+        points to.  ``need_maps`` False (combine_layer 0): nothing but the cameras is read or built."""
+        L, st = _lib.lib(), _stream(dev)
+        dl, enc = model.deformation_layer, model.encoder
+        pe = _lib.DinerNovelPe()
+        keep = []
+        if need_maps:
+            Cc = int(dl.out_features)
+            msrc = [enc.latent, dl.weight]
+            if self._pe_map_key is None or not self._pe_map_key.valid_for(msrc):
+                wl = _f32c(dl.weight.detach()[:, :Cc]).to(dev).contiguous()
+                n = int(L.diner_novel_pe_map_floats(C.byref(sc)))
+                if n < 0:
+                    check(n, "diner_novel_pe_map_floats")
+                assert n == latent.numel()
+                dmap = torch.empty(tuple(latent.shape), dtype=torch.float32, device=dev)
+                check(L.diner_pack_novel_pe_map(C.byref(sc), _ptr(wl), _ptr(dmap), st), "diner_pack_novel_pe_map")
+                torch.cuda.current_stream(dev).synchronize()     # `wl` is a temporary
+                self._pe_map_pack, self._pe_map_key = dmap, _Sources(msrc)
+            hsrc = [dl.weight, dl.bias]
+            if self._pe_head_key is None or not self._pe_head_key.valid_for(hsrc):
+                w, b = _f32c(dl.weight.detach()).to(dev), _f32c(dl.bias.detach()).to(dev)
+                self._pe_head_pack = torch.cat((w[:, Cc:Cc + 6], b[:, None], torch.zeros_like(b[:, None])), dim=1).contiguous()
+                self._pe_head_key = _Sources(hsrc)
+            psrc = [model.pos_encodings, model.tgt_pos_encoding]
+            if self._pe_pos_key is None or not self._pe_pos_key.valid_for(psrc):
+                s = _f32c(model.pos_encodings).to(dev)                          # [SB,NV,3,H,W]
+                t = _f32c(model.tgt_pos_encoding).to(dev)                       # [SB,1,3,H,W] (encode_tgt) or [SB,3,H,W]
+                t = t.reshape(-1, *t.shape[-3:])
+                if s.dim() != 5 or s.shape[2] != 3 or t.shape[1] != 3:
+                    raise ValueError(f"pos_encodings must be [SB,NV,3,H,W] and tgt_pos_encoding [SB,(1,)3,H,W], not {tuple(s.shape)} / {tuple(t.shape)}")
+                nhwc4 = lambda m: torch.nn.functional.pad(m.movedim(-3, -1), (0, 1)).contiguous()   # a zero 4th channel: 16-byte texels
+                self._pe_pos_pack, self._pe_pos_key = (nhwc4(s), nhwc4(t)), _Sources(psrc)
+            spe, tpe = self._pe_pos_pack
+            assert spe.shape[:2] == (sc.SB, sc.NV) and tpe.shape[0] == sc.SB
+            pe.map, pe.head, pe.src_pe, pe.tgt_pe = (t.data_ptr() for t in (self._pe_map_pack, self._pe_head_pack, spe, tpe))
+            (pe.src_h, pe.src_w), (pe.tgt_h, pe.tgt_w) = spe.shape[2:4], tpe.shape[1:3]
+            keep += [self._pe_map_pack, self._pe_head_pack, spe, tpe]
+        else:
+            pe.src_h = pe.src_w = pe.tgt_h = pe.tgt_w = 1
+        cams = [model.tgt_poses, model.tgt_focal, model.tgt_c, model.tgt_image_shape]
+        if self._pe_cam_key is None or not self._pe_cam_key.valid_for(cams):
+            self._pe_cam_pack, self._pe_cam_key = self._cams(*cams, dev), _Sources(cams)
+        poses, focal, c, ishape = self._pe_cam_pack
+        pe.poses, pe.focal, pe.c = poses.data_ptr(), focal.data_ptr(), c.data_ptr()
+        pe.image_w, pe.image_h = ishape
+        return pe, keep + [poses, focal, c]
+
+    @torch.no_grad()
+    def render_points_novel_pe(self, model, in_points, gen_points, tgt_points, viewdirs):
+        """rgb-sigma of the NOVEL_PE PixelNeRF (reference pe_novel_pixelnerf.py:200-292) at given points, in one kernel launch:
+        ``in_points`` / ``gen_points`` / ``tgt_points`` / ``viewdirs`` [SB,P,3] -> [SB,P,4].  The deformation layer's latent part is
+        applied to the encoder's latent once per encode (the deformation map, cached like the latent's pack).  Any fusion MLP whose
+        d_latent = C + 6, padded to C + 8, lies in the shape-general envelope (C <= 1016); every 4-tap lookup mode, applied to all
+        four lookups.  Exact fp32, or f16x3 under ``precision == "f16x3"`` with ``f16x3_any_shape``.  Raises ``NotImplementedError``
+        for what this form does not serve (a bicubic encoder, C = 1024)."""
+        missing = [k for k in self._PE_STATE if getattr(model, k, None) is None]
+        if missing:
+            raise TypeError(f"render_points_novel_pe: the model has no {', '.join(missing)} (not the NOVEL_PE PixelNeRF, or encode() / "
+                            "encode_gen() / encode_tgt() was not called)")
+        if getattr(model.encoder, "index_interp", "bilinear") == "bicubic":
+            raise NotImplementedError("render_points_novel_pe: index_interp='bicubic' is not served by the novel_pe point kernels "
+                                      "(bilinear or nearest, any padding); composite() evaluates such a model with PyTorch")
+        shape = self._validate_pe(model)
+        xi, xg, xt, vd = _f32c(in_points), _f32c(gen_points), _f32c(tgt_points), _f32c(viewdirs)
+        if not xi.is_cuda:
+            raise RuntimeError("diner_amd.novel.NeRFRendererDGS runs on the GPU only (points are on %s)" % xi.device)
+        assert xi.dim() == 3 and xi.shape[-1] == 3 and xg.shape == xi.shape and xt.shape == xi.shape and vd.shape == xi.shape
+        SB, P, _ = xi.shape
+        dev = xi.device
+        f16 = self.precision == "f16x3" and bool(self.f16x3_any_shape)
+        if f16:
+            self.effective_precision = "f16x3"
+        else:
+            if self.precision != "fp32" and not self._warned_precision:
+                warnings.warn(f"diner_amd.novel.NeRFRendererDGS: precision={self.precision!r} reaches the NOVEL_PE point model only with "
+                              "f16x3_any_shape set; it runs in exact fp32 (renderer.effective_precision)", stacklevel=3)
+                self._warned_precision = True
+            self.effective_precision = "fp32"
+        packed = self._pe_mlp_pack(model, shape, f16)
+        sc, keep = self._scene(model, need_latent=True)
+        assert SB == sc.SB                                                      # pe_novel_pixelnerf.py:213
+        if sc.C != shape.d_latent - 8:
+            raise ValueError(f"encoder latent has {sc.C} channels, deformation_layer.out_features is {shape.d_latent - 8}")
+        g, _gkeep = self._novel_gen(model, dev)
+        pe, _pkeep = self._novel_pe(model, sc, keep[4], dev, need_maps=min(shape.combine_layer, shape.n_blocks) > 0)
+        ix = self._latent_index(model)
+        cs = shape.c_struct()
+        out = torch.empty((SB, P, 4), dtype=torch.float32, device=dev)
+        check(_lib.lib().diner_render_points_novel_pe(C.byref(sc), C.byref(ix) if ix is not None else None, C.byref(g), C.byref(pe),
+                                                      C.byref(cs), _ptr(packed), _ptr(xi), _ptr(xg), _ptr(xt), _ptr(vd), P,
+                                                      _lib.PRECISIONS["f16x3" if f16 else "fp32"], _ptr(out), _stream(dev)),
+              "diner_render_points_novel_pe")
+        self.last_route, self.last_binding = ("novel_pe_points_gen_f16" if f16 else "novel_pe_points_gen"), "ctypes"
+        return out
+
+    def _hip_pe_model_ok(self, model) -> bool:
+        """composite() may hand ``model`` to render_points_novel_pe: see ``hip_point_model`` in the constructor"""
+        if not self.hip_point_model or not self.pass_points:
+            return False
+        if any(getattr(model, k, None) is None for k in self._PE_STATE + ("mlp_fine", "poscode", "depthcode", "encoder")):
+            return False
+        dl, enc = model.deformation_layer, model.encoder
+        if not hasattr(dl, "in_features") or int(dl.in_features) != int(dl.out_features) + 6 or getattr(dl, "bias", None) is None:
+            return False
+        if getattr(enc, "latent", None) is None or getattr(enc, "index_interp", "bilinear") == "bicubic":
+            return False
+        if torch.is_grad_enabled():
+            params = list(model.parameters()) if isinstance(model, torch.nn.Module) else \
+                list(model.mlp_fine.parameters()) + list(dl.parameters())
+            if any(p.requires_grad for p in params + [model.gen_latent, enc.latent]):
+                return False
+        try:
+            self._validate_pe(model)
+        except (NotImplementedError, AttributeError):
+            return False
+        return True
+
     def _hip_point_model_ok(self, model) -> bool:
         """composite() may hand ``model`` to render_points_novel: see ``hip_point_model`` in the constructor"""
         if not self.hip_point_model or self.pass_points:
@@ -275,6 +467,8 @@ class NeRFRendererDGS(_Renderer):
             dirs = r[..., None, 3:6].expand(-1, -1, K, -1).reshape(SB, B * K, 3)       # :413, :432
         if self._hip_point_model_ok(model):
             out = self.render_points_novel(model, sets[0], sets[1], dirs).reshape(SB, B, K, 4)
+        elif self._hip_pe_model_ok(model):
+            out = self.render_points_novel_pe(model, sets[0], sets[1], sets[2], dirs).reshape(SB, B, K, 4)
         else:
             chunk = (int(self.eval_batch_size) - 1) // SB + 1                           # :433
             split = [torch.split(t, chunk, dim=1) for t in sets]

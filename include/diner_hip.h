@@ -979,6 +979,42 @@ int diner_render_points_novel(const DinerScene *scene, const DinerLatentIndex *i
                               const float *mlp_packed, const float *xyz_in, const float *xyz_gen, const float *viewdirs, int64_t P,
                               int32_t precision, float *rgbsigma_out, void *stream);
 
+/* ---- the NOVEL_PE point model on the shape-general point/MLP kernels (points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip) --------
+ * The fork's NOVEL_PE PixelNeRF (reference src/models/novel_pe/pe_novel_pixelnerf.py:200-292): diner_render_points_novel with
+ * C = encoder.latent_size, a fusion MLP of d_latent = C + 6, and
+ *   xyz_tgt [SB,P,3]   the undeformed points, projected by scene sb's target camera (pe->poses / focal / c / image_w, image_h)
+ *   src_pe = lookup(pe->src_pe[sb, v], uv) per view, tgt_pe = lookup(pe->tgt_pe[sb], tgt_uv) per point: 3 channels each, with the
+ *            scene's feature_padding (scaled by that map's own size) and the lookup mode of `index`
+ *   conditioned = deformation_layer(cat(latent(uv), src_pe, tgt_pe)); final_latent = gen_latent(gen_uv) + conditioned (:265-268)
+ *   the MLP's latent input is cat(final_latent, src_pe, tgt_pe) (:275)
+ * deformation_layer is linear and every 4-tap lookup a weighted sum of texels, so its latent part is applied to the texels once per
+ * encode: diner_pack_novel_pe_map writes D[sb,v,y,x,:] = W_d[:, :C] . latent[sb,v,y,x,:] (exact fp32 MFMA, no bias; the layout and
+ * size of scene->latent, diner_novel_pe_map_floats floats), and the kernel adds b_d[c] + sum_j W_d[c, C + j] pe6[j] from the head table.
+ * `shape` is the fusion MLP with d_latent = C + 8: lin_z[b].weight [d_hidden, C + 6] padded with two zero columns before
+ * diner_pack_mlp_gen / diner_pack_mlp_gen_f16 (mlp_packed).  scene->latent is not read; scene->C, h, w describe D.
+ * New symbols only: DINER_ABI_VERSION stays 3.  No atomics: two runs agree bit for bit.  Before any launch: DINER_E_INVALID for a NULL
+ * pointer, an unknown index or precision, P < 0, a map size < 1, scene->C or gen->C != shape->d_latent - 8; DINER_E_UNSUPPORTED for a
+ * shape outside the envelope (C + 8 > 1024 included); P = 0 or SB = 0: DINER_OK, nothing is launched.  With combine_layer = 0 no
+ * latent, map or pos-encoding is read. */
+typedef struct DinerNovelPe {
+    const float *map;        /* [SB,NV,h,w,C]: diner_pack_novel_pe_map */
+    const float *head;       /* [C][8]: W_d[c, C:C+6] | b_d[c] | 0 */
+    const float *src_pe;     /* [SB,NV,src_h,src_w,4]: pos_encodings, NHWC, the 4th channel padding */
+    int32_t src_h, src_w;
+    const float *tgt_pe;     /* [SB,tgt_h,tgt_w,4]: tgt_pos_encoding, likewise */
+    int32_t tgt_h, tgt_w;
+    const float *poses;      /* [SB,4,4] world -> target camera, one per scene */
+    const float *focal;      /* [SB,2] */
+    const float *c;          /* [SB,2] */
+    float image_w, image_h;  /* tgt_image_shape (W, H) */
+} DinerNovelPe;
+int64_t diner_novel_pe_map_floats(const DinerScene *scene);
+int diner_pack_novel_pe_map(const DinerScene *scene, const float *w_latent_part, float *map_out, void *stream);
+int diner_render_points_novel_pe(const DinerScene *scene, const DinerLatentIndex *index, const DinerNovelGen *gen, const DinerNovelPe *pe,
+                                 const DinerMlpShape *shape, const float *mlp_packed, const float *xyz_in, const float *xyz_gen,
+                                 const float *xyz_tgt, const float *viewdirs, int64_t P, int32_t precision, float *rgbsigma_out,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
