@@ -293,6 +293,11 @@ SYMBOLS = {
     "diner_pack_novel_pe_map": (C.c_int, [C.POINTER(DinerScene), _P, _P, _P]),
     "diner_render_points_novel_pe": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), C.POINTER(DinerNovelGen),
                                                C.POINTER(DinerNovelPe), C.POINTER(DinerMlpShape), _P, _P, _P, _P, _P, _I64, _I32, _P, _P]),
+    # the NOVEL point model's training path: the point inputs at given points with the general lookup added, and the general latent's
+    # scatter (csrc/train_novel.hip; the ABI version stays 3: new entry points only)
+    "diner_train_point_inputs_novel": (C.c_int, [C.POINTER(DinerScene), C.POINTER(DinerLatentIndex), _P, C.POINTER(DinerNovelGen), _P, _P, _P,
+                                                 _I64, _I32, _P, _I64, _P, _P, _P, _P]),
+    "diner_train_novel_gen_scatter": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 _lib = None

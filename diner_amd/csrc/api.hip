@@ -153,6 +153,9 @@ int launch_train_point_inputs_bwd_gen_bc(const DinerScene &, int, const float *,
                                          int64_t, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
                                          hipStream_t);
 int launch_train_bicubic_scatter(const float *, const float *, int64_t, int, int, int, int, int, float *, hipStream_t);
+int launch_train_point_inputs_novel(const DinerScene &, const DinerLatentIndex &, const float *, const DinerNovelGen &, const float *, const float *,
+                                    const float *, int64_t, int, float *, int64_t, float *, float *, float *, hipStream_t);
+int launch_train_novel_gen_scatter(const float *, const float *, int64_t, int, int, float *, hipStream_t);
 int launch_train_gemm_act(const float *, const float *, const float *, const float *, float *, int64_t, int, int, int64_t, int64_t, int64_t,
                           int64_t, int64_t, int64_t, int, int, int, float, int, int, int64_t, hipStream_t);
 int launch_train_point_inputs_gen(const DinerScene &, const DinerLatentIndex &, const float *, const float *, const float *, int64_t, int, int,
@@ -1191,6 +1194,44 @@ int diner_render_points_novel_pe(const DinerScene *scene, const DinerLatentIndex
     return (f16 ? genf16::launch_points_mlp_novel_pe : gen::launch_points_mlp_novel_pe)(
         *scene, index ? *index : k_default_index, *gen, *pe, *shape, mlp_packed, xyz_in, xyz_gen, xyz_tgt, viewdirs, P, rgbsigma_out,
         (hipStream_t)stream);
+}
+
+/* ---- the NOVEL point model's training path (train_novel.hip; diner_amd/training_novel.py) ------------------------------------------ */
+int diner_train_point_inputs_novel(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const DinerNovelGen *gen,
+                                   const float *xyz_in, const float *xyz_gen, const float *viewdirs, int64_t P, int32_t sb, float *in_out,
+                                   int64_t ld_in, float *zlat, float *taps, float *gen_taps, void *stream)
+{
+    const char *who = "train_point_inputs_novel";
+    int rc;
+    if (!gen) return bad("train_point_inputs_novel: gen is NULL");
+    if (index && index->interp == 2) {   /* SpatialEncoder's third index_interp: DinerLatentIndex does not carry the 16-tap lookup */
+        set_error("%s: latent index interp=2 (bicubic) is not served: the 4-tap modes only (DINER_INDEX_BILINEAR 0 or DINER_INDEX_NEAREST 1)", who);
+        return DINER_E_UNSUPPORTED;
+    }
+    if ((rc = check_train_gen_inputs(scene, index, 0, 1, sb, ld_in, who))) return rc;
+    if (P < 0) return bad("train_point_inputs_novel: bad P");
+    if (gen->C != scene->C) { set_error("%s: general latent channels C=%d != latent channels C=%d", who, gen->C, scene->C); return DINER_E_INVALID; }
+    if (gen->h < 1 || gen->w < 1) { set_error("%s: general latent size h=%d, w=%d (both >= 1)", who, gen->h, gen->w); return DINER_E_INVALID; }
+    if ((int64_t)gen->h * gen->w > 0x7fffffffLL || (int64_t)scene->h * scene->w > 0x7fffffffLL)
+        return bad("train_point_inputs_novel: a latent map of 2^31 or more texels (the tap indices are 32-bit)");
+    if (!gen->poses || !gen->focal || !gen->c) return bad("train_point_inputs_novel: NULL general camera pointer");
+    if (!(gen->image_w > 0.f) || !(gen->image_h > 0.f)) return bad("train_point_inputs_novel: bad general image shape");
+    if (!xyz_in || !xyz_gen || !viewdirs || !in_out) return bad("train_point_inputs_novel: NULL pointer");
+    if (zlat && (!latent_nhwc || !gen->latent || !taps || !gen_taps)) return bad("train_point_inputs_novel: NULL latent / taps pointer");
+    if (P * (int64_t)scene->NV > 0x7fffffffLL) { set_error("%s: too many rows (%lld points, %d views)", who, (long long)P, scene->NV); return DINER_E_INVALID; }
+    if (P == 0) return DINER_OK;
+    return launch_train_point_inputs_novel(*scene, index ? *index : k_default_index, latent_nhwc, *gen, xyz_in, xyz_gen, viewdirs, P, sb, in_out,
+                                           ld_in, zlat, taps, gen_taps, (hipStream_t)stream);
+}
+
+int diner_train_novel_gen_scatter(const float *d_zlat, const float *gen_taps, int64_t P, int32_t C, int32_t h, int32_t w, int32_t NV,
+                                  float *d_gen_nhwc, void *stream)
+{
+    if (!d_zlat || !gen_taps || !d_gen_nhwc) return bad("train_novel_gen_scatter: NULL pointer");
+    if (P < 0 || C <= 0 || h < 1 || w < 1 || NV < 1) return bad("train_novel_gen_scatter: bad size");
+    if ((P + 15) / 16 > 0x7fffffffLL) return bad("train_novel_gen_scatter: too many points");
+    if (P == 0) return DINER_OK;
+    return launch_train_novel_gen_scatter(d_zlat, gen_taps, P, C, NV, d_gen_nhwc, (hipStream_t)stream);
 }
 
 }  // extern "C"

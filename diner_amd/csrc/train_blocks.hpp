@@ -1,5 +1,5 @@
 // The building blocks the training translation units share (train.hip, train_core.hip, train_gen.hip, train_gen_bc.hip,
-// train_gen_f16.hip, train_gen_points.hpp): the operand tile loads of the fp32 and the f16x3 GEMMs, the XCD-aware block -> tile map, the
+// train_gen_f16.hip, train_novel.hip, train_gen_points.hpp): the operand tile loads of the fp32 and the f16x3 GEMMs, the XCD-aware block -> tile map, the
 // fp16 hi / lo split and its LDS layout, the power-of-two operand scale, the activations and their derivatives, the GEMM epilogue, and
 // the constants of the camera-gradient records.  One definition each: the kernels, their argument structs and the Softplus-aware tile
 // stores stay in their units and namespaces.  Everything here is __forceinline__ device code or a constant, so a unit's code object

@@ -18,11 +18,18 @@ constructed with ``hip_point_model=True`` and the model is the NOVEL ``PixelNeRF
 
 * ``render_points_novel`` -- that model on the shape-general point/MLP kernels' "novel" form (csrc/points_mlp_gen_nv.hip,
   points_mlp_gen_f16_nv.hip through ``diner_render_points_novel``): given points, per-point viewdirs, and the model's learned
-  ``gen_latent`` looked up at the general camera and added to the encoder's latent.  Inference only.
+  ``gen_latent`` looked up at the general camera and added to the encoder's latent.  Inference: grad mode off, or no parameter of
+  the model requiring grad.
+* ``_train_points_novel`` -- with ``train_hip_point_model=True`` as well, the same model under autograd (an MLP parameter,
+  ``encoder.latent`` or ``gen_latent`` requires grad): ``diner_amd/training_novel.py`` on the shape-general training path --
+  ``diner_train_point_inputs_novel`` and ``diner_train_novel_gen_scatter`` (csrc/train_novel.hip) around the layer schedule of
+  ``diner_amd/training_gen.py``, in exact fp32 or (``precision == "f16x3"`` with ``train_f16x3_any_shape``) in f16x3: gradients to the
+  MLP's parameters, ``encoder.latent`` and ``gen_latent``; ``last_route`` "novel_train_gen" / "novel_train_gen_f16".  Without that
+  switch training stays on PyTorch (``last_route == "torch"``).
 * ``render_points_novel_pe`` -- with ``pass_points``, the NOVEL_PE ``PixelNeRF`` (reference src/models/novel_pe/pe_novel_pixelnerf.py)
   on the "novel_pe" form (csrc/points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip through ``diner_render_points_novel_pe``): a
   third point set for the target camera, two 3-channel pos-encoding lookups, and the deformation layer applied to the latent's
-  texels once per encode (csrc/novel_pe_map.hip).  Inference only.
+  texels once per encode (csrc/novel_pe_map.hip).  Inference only: NOVEL_PE trains on PyTorch.
 """
 from __future__ import annotations
 
@@ -102,17 +109,26 @@ class NeRFRendererDGS(_Renderer):
     NOVEL_PE, whose model takes the undeformed points as a third argument (pe_nerf_novel_renderer.py)."""
 
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000, white_bkgd=True, pass_points=False,
-                 hip_point_model=False, f16x3_any_shape=False):
+                 hip_point_model=False, f16x3_any_shape=False, train_hip_point_model=False, train_f16x3_any_shape=False):
         super().__init__(n_samples=n_samples, n_depth_candidates=n_depth_candidates, n_gaussian=n_gaussian,
-                         eval_batch_size=eval_batch_size, white_bkgd=white_bkgd, f16x3_any_shape=f16x3_any_shape)
+                         eval_batch_size=eval_batch_size, white_bkgd=white_bkgd, f16x3_any_shape=f16x3_any_shape,
+                         train_f16x3_any_shape=train_f16x3_any_shape)
         self.pass_points = bool(pass_points)
         # composite() evaluates the NOVEL PixelNeRF with one render_points_novel call for all B K points instead of the chunked
         # PyTorch calls, when gradients are off (or no parameter of the model requires grad), the model is recognisably that one (its
         # gen_latent and gen_* buffers, a fusion MLP _validate accepts, no deformation_layer), pass_points is False and the encoder's
-        # lookup is a 4-tap mode.  Anything else -- training, a bicubic encoder, another callable -- goes the PyTorch way,
-        # as with the switch off.  last_route: "novel_points_gen" / "novel_points_gen_f16" (precision == "f16x3" with f16x3_any_shape,
+        # lookup is a 4-tap mode.  Anything else -- training (without train_hip_point_model, below), a bicubic encoder, another
+        # callable -- goes the PyTorch way, as with the switch off.  last_route: "novel_points_gen" / "novel_points_gen_f16" (precision == "f16x3" with f16x3_any_shape,
         # as on the plain renderer) or "torch".  Opt-in; a plain attribute, so that a config can set it (renderer.kwargs.hip_point_model).
         self.hip_point_model = bool(hip_point_model)
+        # Training of that model on the HIP path: with hip_point_model AND train_hip_point_model, grad mode on, and an MLP parameter,
+        # encoder.latent or gen_latent requiring grad, composite() evaluates the NOVEL PixelNeRF by diner_amd/training_novel.py
+        # (csrc/train_novel.hip + the shape-general training GEMMs; any shape of the envelope, the standard one included) instead of
+        # the chunked PyTorch model: gradients to those three, last_route "novel_train_gen", or "novel_train_gen_f16" when precision ==
+        # "f16x3" and train_f16x3_any_shape is set (the plain renderer's switch: the GEMMs in f16x3).  Off: such a call stays on
+        # PyTorch, as before.  NOVEL_PE (pass_points) and a bicubic encoder always do.  Opt-in; plain attributes, so that a config can
+        # set them (renderer.kwargs.train_hip_point_model, renderer.kwargs.train_f16x3_any_shape).
+        self.train_hip_point_model = bool(train_hip_point_model)
         self._gen_latent_key = self._gen_latent_pack = None      # the model's gen_latent, NHWC
         self._gen_cam_key = self._gen_cam_pack = None            # its general cameras, fp32 and contiguous
         # With pass_points the same switch serves the NOVEL_PE PixelNeRF (a deformation_layer Linear(C + 6 -> C), the gen_* and tgt_*
@@ -433,8 +449,9 @@ class NeRFRendererDGS(_Renderer):
             return False
         return True
 
-    def _hip_point_model_ok(self, model) -> bool:
-        """composite() may hand ``model`` to render_points_novel: see ``hip_point_model`` in the constructor"""
+    def _novel_model_ok(self, model) -> bool:
+        """``model`` is recognisably the NOVEL PixelNeRF with a fusion MLP and a lookup the novel kernels serve (everything
+        ``hip_point_model`` asks for but the gradient state)"""
         if not self.hip_point_model or self.pass_points:
             return False
         if any(getattr(model, k, None) is None for k in self._GEN_STATE + ("mlp_fine", "poscode", "depthcode", "encoder")):
@@ -444,15 +461,46 @@ class NeRFRendererDGS(_Renderer):
         enc = model.encoder
         if getattr(enc, "latent", None) is None or getattr(enc, "index_interp", "bilinear") == "bicubic":
             return False
-        if torch.is_grad_enabled():
-            params = list(model.parameters()) if isinstance(model, torch.nn.Module) else list(model.mlp_fine.parameters())
-            if any(p.requires_grad for p in params + [model.gen_latent, enc.latent]):
-                return False
         try:
             self._validate(model)
         except (NotImplementedError, AttributeError):
             return False
         return True
+
+    @staticmethod
+    def _any_requires_grad(model) -> bool:
+        if not torch.is_grad_enabled():
+            return False
+        params = list(model.parameters()) if isinstance(model, torch.nn.Module) else list(model.mlp_fine.parameters())
+        return any(p.requires_grad for p in params + [model.gen_latent, model.encoder.latent])
+
+    def _hip_point_model_ok(self, model) -> bool:
+        """composite() may hand ``model`` to render_points_novel: see ``hip_point_model`` in the constructor"""
+        return self._novel_model_ok(model) and not self._any_requires_grad(model)
+
+    def _hip_point_model_trains(self, model) -> bool:
+        """composite() may hand ``model`` to training_novel.render_points_with_grad: see ``train_hip_point_model`` in the constructor"""
+        if not self.train_hip_point_model or not torch.is_grad_enabled() or not self._novel_model_ok(model):
+            return False
+        from .training_gen import mlp_params
+        return any(p.requires_grad for p in mlp_params(model.mlp_fine) + [model.encoder.latent, model.gen_latent])
+
+    def _train_points_novel(self, model, in_points, gen_points, viewdirs):
+        """rgb-sigma [SB,P,4] of the NOVEL PixelNeRF under autograd (diner_amd/training_novel.py)"""
+        from . import training_novel
+        shape = self._validate(model)
+        f16 = self.precision == "f16x3" and bool(self.train_f16x3_any_shape)
+        if f16:
+            self.effective_precision = "f16x3"
+        else:
+            if self.precision != "fp32" and not self._warned_precision:
+                warnings.warn(f"diner_amd.novel.NeRFRendererDGS: precision={self.precision!r} reaches the NOVEL point model's training "
+                              "path only with train_f16x3_any_shape set; it runs in exact fp32 (renderer.effective_precision)", stacklevel=4)
+                self._warned_precision = True
+            self.effective_precision = "fp32"
+        out = training_novel.render_points_with_grad(self, model, in_points, gen_points, viewdirs, shape, f16=f16)
+        self.last_route, self.last_binding = ("novel_train_gen_f16" if f16 else "novel_train_gen"), "ctypes"
+        return out
 
     def composite(self, model, rays, z_samp, target_vertices, tgt_in_offsets, tgt_gen_offsets, *, _sync=False):
         """Alpha compositing of the model's rgb-sigma on the deformed sample points (reference :394-477) -> (weights, rgb, depth).
@@ -467,6 +515,8 @@ class NeRFRendererDGS(_Renderer):
             dirs = r[..., None, 3:6].expand(-1, -1, K, -1).reshape(SB, B * K, 3)       # :413, :432
         if self._hip_point_model_ok(model):
             out = self.render_points_novel(model, sets[0], sets[1], dirs).reshape(SB, B, K, 4)
+        elif self._hip_point_model_trains(model):
+            out = self._train_points_novel(model, sets[0], sets[1], dirs).reshape(SB, B, K, 4)
         elif self._hip_pe_model_ok(model):
             out = self.render_points_novel_pe(model, sets[0], sets[1], sets[2], dirs).reshape(SB, B, K, 4)
         else:

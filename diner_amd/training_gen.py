@@ -171,6 +171,81 @@ class _Layout:
         return 2 + 2 * self.nlz + 4 * self.nb
 
 
+# ---- the layer schedule of ResnetFC.forward and its transpose, for one scene's rows: what both autograd functions (_RenderGenFn here,
+# training_novel._RenderNovelFn) run between their own point-input and latent-scatter stages
+
+def schedule_forward(L, inp, zl, prm, w_in, lay, act, sw, NV, P, st):
+    """in [R, ld_in], zlat [R, C] (None: no lin_z) -> blocks [(x, net) per block], the last block's output x, lin_out's output [P or R, 4].
+    ``prm``: the fp32 parameters in ``mlp_params`` order, ``w_in``: lin_in's zero-padded weight, ``sw(i)``: weight i's SplitWeight (f16x3)
+    or None."""
+    dev = inp.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    H = w_in.shape[0]
+    x = f(NV * P, H)
+    linear_fwd(inp, w_in, prm[1], x, sw=sw(0))                                                # resnetfc.py:139
+    blocks = []
+    for b in range(lay.nb):
+        if b == lay.cl:                                                                # :146-149 (mean over views)
+            xbar = f(P, H)
+            check(L.diner_train_view_mean(_p(x), P * H, NV, _p(xbar), 0, st), "diner_train_view_mean")
+            x = xbar
+        if b < lay.cl:                                                                 # :151-153, x += lin_z[b](z) in place
+            linear_fwd(zl, prm[lay.lz(b)], prm[lay.lz(b) + 1], x, accumulate=True, sw=sw(lay.lz(b)))
+        i = lay.blk(b)
+        net = torch.empty_like(x)
+        linear_fwd(x, prm[i], prm[i + 1], net, act=act, sw=sw(i))                             # :62
+        y = x.clone()
+        linear_fwd(net, prm[i + 2], prm[i + 3], y, act=act, accumulate=True, sw=sw(i + 2))         # :63, :69
+        blocks.append((x, net))
+        x = y
+    out = f(x.shape[0], 4)
+    linear_fwd(x, prm[lay.out], prm[lay.out + 1], out, act=act, sw=sw(lay.out))                    # :158
+    return blocks, x, out
+
+
+def schedule_backward(L, inp, zl, blocks, x_last, d_out, prm, g, g_in, lay, act, swt, f16, NV, P, Cl, st, zero_d_zl=False):
+    """The transpose of ``schedule_forward`` from d_out (the head's backward) down to lin_in's weight gradient: adds every parameter's
+    gradient into ``g`` (``g_in``: lin_in's padded weight) and returns d_x [R, H] (lin_in's output gradient), its amax word (f16x3, else
+    None) and d_zlat [R, Cl] (None without lin_z, zeros under ``zero_d_zl``).  ``swt(i)``: weight i's transposed SplitWeight or None."""
+    dev = inp.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    H, R = x_last.shape[1], NV * P
+    a_out = grad_reduce(d_out, g[lay.out + 1], f16)
+    linear_bwd_w(d_out, x_last, g[lay.out], g[lay.out + 1], act=act, amax=a_out)  # lin_out
+    d_x = f(x_last.shape[0], H)
+    linear_bwd_x(d_out, prm[lay.out], x_last, d_x, act=act, sw=swt(lay.out), amax=a_out)
+    d_zl = torch.zeros((R, Cl), dtype=torch.float32, device=dev) if zero_d_zl else None
+    for b in reversed(range(lay.nb)):
+        xb, net = blocks[b]
+        i = lay.blk(b)
+        d_y = d_x                                                                      # gradient of the block's output
+        a_y = grad_reduce(d_y, g[i + 3], f16)
+        linear_bwd_w(d_y, net, g[i + 2], g[i + 3], act=act, amax=a_y)             # fc_1
+        d_net = torch.empty_like(net)
+        linear_bwd_x(d_y, prm[i + 2], net, d_net, act=act, sw=swt(i + 2), amax=a_y)
+        a_net = grad_reduce(d_net, g[i + 1], f16)
+        linear_bwd_w(d_net, xb, g[i], g[i + 1], act=act, amax=a_net)              # fc_0
+        linear_bwd_x(d_net, prm[i], xb, d_y, act=act, accumulate=True, sw=swt(i), amax=a_net)  # d_xb = d_y + (d_net W0) act'(xb), in place
+        d_xb = d_y
+        if b < lay.cl:                                                                 # lin_z[b]: its own dY is d_xb
+            j = lay.lz(b)
+            a_xb = grad_reduce(d_xb, g[j + 1], f16)
+            linear_bwd_w(d_xb, zl, g[j], g[j + 1], amax=a_xb)
+            if d_zl is None:
+                d_zl = f(R, Cl)
+                linear_bwd_x(d_xb, prm[j], None, d_zl, sw=swt(j), amax=a_xb)
+            else:
+                linear_bwd_x(d_xb, prm[j], None, d_zl, accumulate=True, sw=swt(j), amax=a_xb)
+        if b == lay.cl:                                                                # the mean's transpose: rows P -> R
+            d_x = f(R, H)
+            check(L.diner_train_view_mean(_p(d_xb), P * H, NV, _p(d_x), 1, st), "diner_train_view_mean(bwd)")
+        else:
+            d_x = d_xb
+    a_x = grad_reduce(d_x, g[1], f16)
+    linear_bwd_w(d_x, inp, g_in, g[1], amax=a_x)                                  # lin_in
+    return d_x, a_x, d_zl
+
+
 class _RenderGenFn(torch.autograd.Function):
     """(rays, latent, poses, focal, c, image_shape, depths, *mlp_params) -> (rgb, depth, weights) for fixed samples, any shape of the
     envelope.  Same contract as ``training._RenderFn`` (``cams``: the caller's leaves, whose versions backward() checks).
@@ -211,25 +286,7 @@ class _RenderGenFn(torch.autograd.Function):
             else:
                 check(L.diner_train_point_inputs_gen(C.byref(scene), ixp, _p(lat_nhwc), _p(rays), _p(z), NR, K, sb, _p(inp), ld_in, _p(zl),
                                                      _p(taps), st), "diner_train_point_inputs_gen")
-            x = f(R, H)
-            linear_fwd(inp, w_in, prm[1], x, sw=sw(0))                                                # resnetfc.py:139
-            blocks = []
-            for b in range(lay.nb):
-                if b == lay.cl:                                                                # :146-149 (mean over views)
-                    xbar = f(P, H)
-                    check(L.diner_train_view_mean(_p(x), P * H, NV, _p(xbar), 0, st), "diner_train_view_mean")
-                    x = xbar
-                if b < lay.cl:                                                                 # :151-153, x += lin_z[b](z) in place
-                    linear_fwd(zl, prm[lay.lz(b)], prm[lay.lz(b) + 1], x, accumulate=True, sw=sw(lay.lz(b)))
-                i = lay.blk(b)
-                net = torch.empty_like(x)
-                linear_fwd(x, prm[i], prm[i + 1], net, act=act, sw=sw(i))                             # :62
-                y = x.clone()
-                linear_fwd(net, prm[i + 2], prm[i + 3], y, act=act, accumulate=True, sw=sw(i + 2))         # :63, :69
-                blocks.append((x, net))
-                x = y
-            out = f(x.shape[0], 4)
-            linear_fwd(x, prm[lay.out], prm[lay.out + 1], out, act=act, sw=sw(lay.out))                    # :158
+            blocks, x, out = schedule_forward(L, inp, zl, prm, w_in, lay, act, sw, NV, P, st)
             check(L.diner_train_head(_p(out), None, None, P * 4, _p(rgbsigma[sb]), 0, st), "diner_train_head")  # pixelnerf.py:139-143
             saved.append((inp, zl, taps, blocks, x, out))
         N = SB * NR
@@ -278,42 +335,10 @@ class _RenderGenFn(torch.autograd.Function):
 
         for sb in range(SB):
             inp, zl, taps, blocks, x_last, out = ctx.saved_acts[sb]
-            out_rows = x_last.shape[0]
-            d_out = f(out_rows, 4)
+            d_out = f(x_last.shape[0], 4)
             check(L.diner_train_head(_p(out), _p(rgbsigma[sb]), _p(d_rgbsigma[sb]), P * 4, _p(d_out), 1, st), "diner_train_head(bwd)")
-            a_out = grad_reduce(d_out, g[lay.out + 1], f16)
-            linear_bwd_w(d_out, x_last, g[lay.out], g[lay.out + 1], act=act, amax=a_out)  # lin_out
-            d_x = f(out_rows, H)
-            linear_bwd_x(d_out, prm[lay.out], x_last, d_x, act=act, sw=swt(lay.out), amax=a_out)
-            d_zl = torch.zeros((R, scene.C), dtype=torch.float32, device=dev) if (lay.nlz == 0 and cam_any) else None
-            for b in reversed(range(lay.nb)):
-                xb, net = blocks[b]
-                i = lay.blk(b)
-                d_y = d_x                                                                      # gradient of the block's output
-                a_y = grad_reduce(d_y, g[i + 3], f16)
-                linear_bwd_w(d_y, net, g[i + 2], g[i + 3], act=act, amax=a_y)             # fc_1
-                d_net = torch.empty_like(net)
-                linear_bwd_x(d_y, prm[i + 2], net, d_net, act=act, sw=swt(i + 2), amax=a_y)
-                a_net = grad_reduce(d_net, g[i + 1], f16)
-                linear_bwd_w(d_net, xb, g[i], g[i + 1], act=act, amax=a_net)              # fc_0
-                linear_bwd_x(d_net, prm[i], xb, d_y, act=act, accumulate=True, sw=swt(i), amax=a_net)  # d_xb = d_y + (d_net W0) act'(xb), in place
-                d_xb = d_y
-                if b < lay.cl:                                                                 # lin_z[b]: its own dY is d_xb
-                    j = lay.lz(b)
-                    a_xb = grad_reduce(d_xb, g[j + 1], f16)
-                    linear_bwd_w(d_xb, zl, g[j], g[j + 1], amax=a_xb)
-                    if d_zl is None:
-                        d_zl = f(R, scene.C)
-                        linear_bwd_x(d_xb, prm[j], None, d_zl, sw=swt(j), amax=a_xb)
-                    else:
-                        linear_bwd_x(d_xb, prm[j], None, d_zl, accumulate=True, sw=swt(j), amax=a_xb)
-                if b == lay.cl:                                                                # the mean's transpose: rows P -> R
-                    d_x = f(R, H)
-                    check(L.diner_train_view_mean(_p(d_xb), P * H, NV, _p(d_x), 1, st), "diner_train_view_mean(bwd)")
-                else:
-                    d_x = d_xb
-            a_x = grad_reduce(d_x, g[1], f16)
-            linear_bwd_w(d_x, inp, g_in, g[1], amax=a_x)                                  # lin_in
+            d_x, a_x, d_zl = schedule_backward(L, inp, zl, blocks, x_last, d_out, prm, g, g_in, lay, act, swt, f16, NV, P, scene.C, st,
+                                               zero_d_zl=lay.nlz == 0 and cam_any)
             if cam_any:   # lin_in's input gradient, then the transpose of the point inputs to the geometric leaves
                 d_in = f(R, ld_in)
                 linear_bwd_x(d_x, ctx.w_in, None, d_in, sw=swt(0), amax=a_x)

@@ -1015,6 +1015,34 @@ int diner_render_points_novel_pe(const DinerScene *scene, const DinerLatentIndex
                                  const float *xyz_tgt, const float *viewdirs, int64_t P, int32_t precision, float *rgbsigma_out,
                                  void *stream);
 
+/* ---- the NOVEL point model's training path (train_novel.hip; diner_amd/training_novel.py) ------------------------------------------
+ * Training the fork's NOVEL PixelNeRF (reference src/models/novel/novel_pixelnerf.py:143-242) on the shape-general training path's
+ * staged schedule (diner_train_gemm_act and its f16x3 forms, view mean, head): only the first and the last stage differ from the plain
+ * model's.  New symbols only: DINER_ABI_VERSION stays 3.  Both: before any launch DINER_E_INVALID for a NULL pointer, an unknown index
+ * mode, P < 0, gen->C != scene->C, gen->h or gen->w < 1; P = 0: DINER_OK, nothing is launched.
+ *
+ * diner_train_point_inputs_novel replaces :159-200 (projection of xyz into the source views, viewdirs rotated, the encoder's lookup
+ * and PixelNeRF.index :108-141 of gen_latent at the general camera, final_latent = gen_latent + latent :196, the depth feature) and the
+ * positional code of :225: diner_train_point_inputs_gen at GIVEN points.  Same rows (row = v*P + p), same in_out [R, ld_in] columns
+ * with the same sinf expressions, same taps [R,8] record of the encoder's lookup; the world point is xyz_in[sb][p], the direction
+ * viewdirs[sb][p] ([SB,P,3] each).  zlat [R, C] = lookup(latent[sb, v], uv) + lookup(gen->latent, gen_uv), with gen_uv from
+ * xyz_gen[sb][p] through scene sb's general camera, the scene's feature_padding scaled by the general map's own size and the lookup
+ * mode of `index` (NULL = bilinear / border; every 4-tap mode is served; interp = 2, bicubic: DINER_E_UNSUPPORTED).  gen_taps [P,8]:
+ * the general footprint in the taps format (4 texel indices as int bits, 4 weights), written once per point.  With gen->latent = 0,
+ * xyz_gen = xyz_in = o + z d and viewdirs = d the three outputs equal diner_train_point_inputs_gen's bit for bit.  zlat = NULL
+ * (combine_layer = 0): neither latent is read, taps and gen_taps are not written and may be NULL. */
+int diner_train_point_inputs_novel(const DinerScene *scene, const DinerLatentIndex *index, const float *latent_nhwc, const DinerNovelGen *gen,
+                                   const float *xyz_in, const float *xyz_gen, const float *viewdirs, int64_t P, int32_t sb, float *in_out,
+                                   int64_t ld_in, float *zlat, float *taps, float *gen_taps, void *stream);
+/* grid_sample's input gradient for the general lookup (autograd of :126-137, where index() repeats the one map over SB * NV):
+ * d_gen_nhwc[texel][ch] += (sum_v d_zlat[v*P + p][ch]) * weight, the view sum formed in registers in the order v = 0 .. NV-1, then
+ * diner_train_bilinear_scatter's scheme (runs of consecutive points merged while the footprint stays, one float atomic per used tap on
+ * 256-byte contiguous rows, a tap of weight 0 never flushed).  The caller zeroes d_gen_nhwc [h,w,C] once per backward; every scene
+ * accumulates into it; diner_train_nhwc_to_nchw with N = 1 then gives gen_latent's [C,h,w] layout.  The encoder latent's gradient
+ * goes through diner_train_bilinear_scatter unchanged (taps has its format). */
+int diner_train_novel_gen_scatter(const float *d_zlat, const float *gen_taps, int64_t P, int32_t C, int32_t h, int32_t w, int32_t NV,
+                                  float *d_gen_nhwc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
