@@ -447,6 +447,12 @@ int diner_train_gemm(const float *A, const float *B, const float *bias, const fl
     if (precision != DINER_PRECISION_FP32 && precision != DINER_PRECISION_F16X3) return bad("train_gemm: unknown precision");
     if (M < 0 || N <= 0 || K <= 0 || (N & 3) || (k_chunk & 31)) return bad("train_gemm: bad size (N % 4, k_chunk % 32 must be 0)");
     if (exp_a < -60 || exp_a > 60 || exp_b < -60 || exp_b > 60) return bad("train_gemm: scale exponent out of range");
+    // the tile loads read float4 pieces along an operand's contiguous index (a piece is valid when its first element is): what
+    // diner_train_gemm_act refuses is refused here
+    if (sak != 1 && sam != 1) return bad("train_gemm: A must be contiguous along m or k");
+    if (sbn != 1 && sbk != 1) return bad("train_gemm: B must be contiguous along k or n");
+    if ((sak == 1 ? (K & 3) || (sam & 3) : (M & 3) || (sak & 3)) || (sbn == 1 ? (sbk & 3) : (K & 3) || (sbn & 3)))
+        return bad("train_gemm: the contiguous extent and the other stride of each operand must be multiples of 4");
     return launch_train_gemm(A, B, bias, S, C, M, N, K, sam, sak, sbk, sbn, ldc, lds, relu_a, relu_b, accumulate, atomic, k_chunk,
                              precision, (const unsigned int *)amax_a, (const unsigned int *)amax_b, exp_a, exp_b, (hipStream_t)stream);
 }

@@ -549,7 +549,8 @@ int diner_render_image_gen_lz(const DinerScene *scene, const DinerLatentIndex *i
  * diner_amd/training.py exactly like autograd orchestrates the reference's ATen ops.  Gradients: MLP
  * parameters and encoder.latent (NCHW); the sampler is @torch.no_grad in the reference. ------------------ */
 /* C[m][n] (+)= sum_k opA(A[m*sam + k*sak]) * opB(B[k*sbk + n*sbn]) (+ bias[n]) (* [S[m*lds + n] > 0]).
- * Each operand must be contiguous along one of its two indices; N % 4 == 0; k_chunk (0 = no split, else a
+ * Each operand must be contiguous along one of its two indices, with that index's extent and the other
+ * index's stride multiples of 4 (as diner_train_gemm_act); N % 4 == 0; k_chunk (0 = no split, else a
  * multiple of 32) splits the contraction over blockIdx.z (use with atomic = 1).
  * precision DINER_PRECISION_FP32: exact fp32 MFMA (amax / exp arguments ignored).
  * precision DINER_PRECISION_F16X3: each operand element is multiplied by a power of two, split into fp16
