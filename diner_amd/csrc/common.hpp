@@ -51,6 +51,20 @@ __device__ __forceinline__ View load_view(const DinerScene &s, int sb, int v)
     return o;
 }
 
+// the one camera per scene of the NOVEL models (general, target): poses [SB,4,4], focal [SB,2], c [SB,2]
+__device__ __forceinline__ View view_of(const float *poses, const float *focal, const float *c, int sb)
+{
+    View v;
+    const float *Pm = poses + (int64_t)sb * 16;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        v.r[i * 3 + 0] = Pm[i * 4 + 0]; v.r[i * 3 + 1] = Pm[i * 4 + 1]; v.r[i * 3 + 2] = Pm[i * 4 + 2];
+        v.t[i] = Pm[i * 4 + 3];
+    }
+    v.fx = focal[sb * 2]; v.fy = focal[sb * 2 + 1]; v.cx = c[sb * 2]; v.cy = c[sb * 2 + 1];
+    return v;
+}
+
 // R*x as torch.matmul evaluates it (BLAS: k-ordered FMA chain) -- nerf_renderer.py:100,103
 __device__ __forceinline__ void rotate(const View &v, float x, float y, float z, float &ox, float &oy, float &oz)
 {
@@ -128,6 +142,83 @@ __device__ __forceinline__ int safe_idx(float f, int size)
 }
 
 // --------------------------------------------------------------------------------------------
+// the input stage of the shape-general point models (render: points_mlp_gen*; training: train_gen_points.hpp, train_novel.hip)
+// --------------------------------------------------------------------------------------------
+// depth of view (sb, v) at the texel (ddx, ddy) nearest to uv (pixelnerf.py:114)
+__device__ __forceinline__ float nearest_depth(const DinerScene &s, int sb, int v, float u, float w, int &ddx, int &ddy)
+{
+    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
+    ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
+    ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
+    return tex[((int64_t)ddy * s.W + ddx) * 2].w;
+}
+
+// world point (wx, wy, wz) and direction (dwx, dwy, dwz) in source view (sb, v): camera point, NDC uv, camera direction and
+// delta = depth - z (pixelnerf.py:91-115).  Scalars in and out: a record selected from by index would live in scratch memory.
+__device__ __forceinline__ void view_geometry(const DinerScene &s, int sb, int v, float wx, float wy, float wz, float dwx, float dwy,
+                                              float dwz, float &px, float &py, float &pz, float &u, float &w, float &dcx, float &dcy,
+                                              float &dcz, float &delta)
+{
+    const View vw = load_view(s, sb, v);
+    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);
+    rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);
+    int ddx, ddy;
+    delta = nearest_depth(s, sb, v, u, w, ddx, ddy) - pz;
+}
+
+// column e of the MLP's 7 + 8F inputs (pixelnerf.py:128; positional_encoding.py:45-49), 0 past them:
+//   [x_cam 3 | sin(f_j x_cam + phi_j) 6F | R d_w 3 | depth_dist 1 | sin(f_j depth_dist + phi_j) 2F]
+// The one place that states the layout and the sinf expressions for the render and the training kernels alike.
+__device__ __forceinline__ float input_element(int e, float px, float py, float pz, float dcx, float dcy, float dcz, float delta, int F,
+                                               float freq_factor)
+{
+    const int e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
+    const float half_pi = 1.5707963267948966f;
+    float val;
+    if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
+    else if (e < e_pe3) {
+        const int j = (e - 3) / 3, i = (e - 3) % 3;
+        val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f));
+    } else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
+    else if (e == e_dir) val = delta;
+    else if (e < e_pe1 + 2 * F) {
+        const int j = e - e_pe1;
+        val = sinf(__builtin_fmaf(delta, ldexpf(freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f));
+    } else val = 0.0f;
+    return val;
+}
+
+// XCD-aware order of the point tiles (workgroups go round-robin to the 8 XCDs): consecutive tiles -- neighbouring samples of a ray,
+// then neighbouring rays, so neighbouring latent texels -- stay on one XCD's L2.  Bijective for any grid size.  (train_blocks.hpp's
+// tile_of is another function: it deals the column blocks of a 2-D GEMM tile grid, not a 1-D run of tiles.)
+__device__ __forceinline__ int64_t xcd_tile(int64_t nwg, int64_t b)
+{
+    const int64_t q = nwg / 8, r = nwg % 8, xcd = b % 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+}
+
+// a wave's [RB][CT] block of 16-float MFMA accumulators (V = f32x16 of either family): cleared, and summed over the views
+template <class V, int RB, int CT>
+__device__ __forceinline__ void acc_zero(V (&acc)[RB][CT])
+{
+#pragma unroll
+    for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[tm][tn][i] = 0.0f;
+}
+
+template <class V, int RB, int CT>
+__device__ __forceinline__ void acc_add(V (&acc)[RB][CT], const V (&x)[RB][CT])
+{
+#pragma unroll
+    for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn) acc[tm][tn] += x[tm][tn];
+}
+
+// --------------------------------------------------------------------------------------------
 // latent lookup: SpatialEncoder.index (image_encoder.py:97-127) = grid_sample(align_corners=False, mode=index_interp,
 // padding_mode=index_padding) of the latent map at the feature_padding-rescaled uv.  Every mode is a footprint of at most 4 texels
 // (x0|x1) x (y0|y1) with the weights nw ne sw se, consumed in ATen's accumulation order by the gathers and by the training path's
@@ -202,6 +293,27 @@ __device__ __forceinline__ LatentFoot latent_footprint(float u, float w, float s
     };
     f.x0 = idx(xa, lw); f.x1 = idx(xb, lw); f.y0 = idx(ya, lh); f.y1 = idx(yb, lh);
     return f;
+}
+
+// uv scale of feature_padding along an axis of `size` texels (image_encoder.py:113-114): every map scales it by its own size
+__device__ __forceinline__ float pad_scale(int size, float feature_padding) { return ((float)size - feature_padding * 2.0f) / (float)size; }
+
+// footprint, in a [mh, mw] map, of world point x seen by the scene's one camera `cam` of image shape (iw, ih): the NOVEL models'
+// index() of gen_latent
+__device__ __forceinline__ LatentFoot camera_footprint(const View &cam, float iw, float ih, const float *x, int mh, int mw,
+                                                       float feature_padding, int interp, int padding)
+{
+    float px, py, pz, u, w;
+    project(cam, iw, ih, x[0], x[1], x[2], px, py, pz, u, w);
+    return latent_footprint<true>(u, w, pad_scale(mw, feature_padding), pad_scale(mh, feature_padding), mw, mh, interp, padding);
+}
+
+// one channel of a 4-tap lookup: the texel values a b c d under the weights nw ne sw se of t (a LatentFoot or a kernel's tap record),
+// in ATen's accumulation order nw, ne, sw, se with contracted FMAs
+template <class TapRec>
+__device__ __forceinline__ float tap_sum(float a, float b, float c, float d, const TapRec &t)
+{
+    return __builtin_fmaf(d, t.se, __builtin_fmaf(c, t.sw, __builtin_fmaf(b, t.ne, a * t.nw)));
 }
 
 // --------------------------------------------------------------------------------------------

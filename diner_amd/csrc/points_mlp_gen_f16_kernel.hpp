@@ -1,5 +1,8 @@
 // Device code of the shape-general f16x3 point/MLP kernels (points_mlp_gen_f16.hip has the description): the packed weight layout, the
-// LDS A image, the split-fp16 MFMA GEMM, the tap records, the kernel template and its launcher.  One lookup mode = one instantiation of
+// LDS A image, the split-fp16 MFMA GEMM, the tap records, the building blocks every kernel of the family is made of (tap_of,
+// store_input_plane, resnet_block, finish; the view geometry, the input columns and the tile order are common.hpp's), the kernel
+// template and its launcher.  Each kernel shows its inputs, its per-point records, the view loop (input stage, lin_in, gather,
+// resnet_block) and the finish; the gathers stay in the kernels.  One lookup mode = one instantiation of
 // the template, each in a translation unit of its own (points_mlp_gen_f16.hip and points_mlp_gen_f16_{ix,bc,lz,lz_bc}.hip).
 #pragma once
 #include <type_traits>
@@ -196,6 +199,126 @@ struct TapBc {      // bicubic footprint of one (point, view) in the latent map 
     float cx[4], cy[4];      // weights per axis, cy * 2^-4; zeros padding: 0 for a column / row outside the map
 };
 
+// ---- building blocks of the kernels: points_mlp_gen_f16_kernel below and the forms of it that units of their own define ----
+// the Tap of a 4-tap footprint in a map lw texels wide, c4 float4 per texel; the weights * 2^-4
+__device__ __forceinline__ Tap tap_of(const LatentFoot &f, int lw, int c4)
+{
+    Tap t;
+    t.o00 = (f.y0 * lw + f.x0) * c4; t.o01 = (f.y0 * lw + f.x1) * c4;
+    t.o10 = (f.y1 * lw + f.x0) * c4; t.o11 = (f.y1 * lw + f.x1) * c4;
+    t.nw = f.nw * ACT_SCALE; t.ne = f.ne * ACT_SCALE; t.sw = f.sw * ACT_SCALE; t.se = f.se * ACT_SCALE;
+    return t;
+}
+
+// the 8 values of one point in one plane -> the plane's hi and lo 16-byte slots
+__device__ __forceinline__ void split8(const float (&v)[8], u32x4 &vh, u32x4 &vl)
+{
+    unsigned ph[4], plo[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        _Float16 hi[2], lo[2];
+        split(v[2 * jj], hi[0], lo[0]); split(v[2 * jj + 1], hi[1], lo[1]);
+        ph[jj] = pack2(hi[0], hi[1]); plo[jj] = pack2(lo[0], lo[1]);
+    }
+    vh = u32x4{ph[0], ph[1], ph[2], ph[3]}; vl = u32x4{plo[0], plo[1], plo[2], plo[3]};
+}
+
+// plane pl of a point's MLP inputs (columns 8 pl .. 8 pl + 7 of the layout pixelnerf.py:128, * 2^-4, split hi / lo) -> A
+__device__ __forceinline__ void store_input_plane(u32x4 *A, int pl, int row, float px, float py, float pz, float dcx, float dcy, float dcz,
+                                                  float delta, int F, float freq_factor)
+{
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = input_element(pl * 8 + j, px, py, pz, dcx, dcy, dcz, delta, F, freq_factor) * ACT_SCALE;
+    u32x4 vh, vl;
+    split8(v, vh, vl);
+    A[a_slot(pl, 0, row)] = vh;
+    A[a_slot(pl, 1, row)] = vl;
+}
+
+// ResNet block b on the hidden state x (resnetfc.py:62-69): x = x + fc_1(act(fc_0(act(x)))).  The A image must be free on entry and
+// is free on return (four barriers).
+template <int RB, int CT>
+__device__ __forceinline__ void resnet_block(f32x16 (&x)[RB][CT], u32x4 *A, const float *__restrict__ Wp, const Layout &L, int b, int rb0,
+                                             int ct0, int lane)
+{
+    const h8 *A8 = (const h8 *)A, *Wh = (const h8 *)Wp;
+    const float *bias = Wp + L.off_bias;
+    const int NT = L.NT, H = L.H;
+    f32x16 net[RB][CT];
+    store_act(x, A, L.beta, rb0, ct0, NT, lane);                                                    // :62 fc_0(act(x))
+    __syncthreads();
+    acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
+    gemm(net, A8, Wh + (L.off_fc0 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
+    __syncthreads();
+    store_act(net, A, L.beta, rb0, ct0, NT, lane);                                                  // :63 fc_1(act(net))
+    __syncthreads();
+    acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                         // :69 x + dx
+    gemm(x, A8, Wh + (L.off_fc1 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
+    __syncthreads();
+}
+
+// what follows the view loop: combine() = the mean of the per-view states xsum over NV views (resnetfc.py:146-149), the blocks after
+// combine_layer, lin_out (:158) and the head (pixelnerf.py:139-143: sigmoid rgb, ReLU sigma) -> rgbsigma [SB,P,4], points of the tail
+// tile past P masked
+template <int RB, int CT>
+__device__ __forceinline__ void finish(f32x16 (&xsum)[RB][CT], u32x4 *A, const float *__restrict__ Wp, const Layout &L, int NV, int rb0,
+                                       int ct0, int tid, int sb, int64_t tile, int64_t P, float *__restrict__ rgbsigma)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    const float *bias = Wp + L.off_bias;
+    const int NT = L.NT, H = L.H;
+    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
+        const float nv = (float)NV;
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
+    }
+    for (int b = L.nvb; b < L.nb; ++b) resnet_block(xsum, A, Wp, L, b, rb0, ct0, lane);
+    // ---- lin_out(act(x)) (:158) in fp32 on the VALU: every lane's partial dot products over its own features -> LDS (the A image is
+    // free: the barrier above), [slot = 2 (tile group) + h][point][4]; a tile group past NT contributes zeros ----------------------
+    float *red = (float *)A;
+    const float *wout = Wp + L.off_wout;
+    const int h = lane >> 5, grp = RB == 2 ? wave : (wave >> 1);
+#pragma unroll
+    for (int tm = 0; tm < RB; ++tm) {
+        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int tn = 0; tn < CT; ++tn) {
+            if (ct0 + tn >= NT) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float a[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = act(xsum[tm][tn][4 * g + j], L.beta);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const f32x4 wq = *(const f32x4 *)(wout + c * H + (ct0 + tn) * 32 + 8 * g + 4 * h);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[c] = __builtin_fmaf(a[j], wq[j], o[c]);
+                }
+            }
+        }
+        const f32x4 ov = {o[0], o[1], o[2], o[3]};
+        ((f32x4 *)red)[(grp * 2 + h) * TILE_P + (rb0 + tm) * 32 + (lane & 31)] = ov;
+    }
+    __syncthreads();
+    if (tid < TILE_P * 4) {
+        const int r = tid >> 2, c = tid & 3;
+        const int ngrp = RB == 2 ? NWAVES : NWAVES / 2;   // <1,1>: the point block of r was written by the waves of its parity only
+        float sum = 0.0f;
+        for (int g = 0; g < 2 * ngrp; ++g) sum += red[(g * TILE_P + r) * 4 + c];
+        const int64_t pp = tile * TILE_P + r;
+        if (pp < P) {
+            const float val = (sum + bias[L.bias_lin_out() + c]) * (1.0f / ACT_SCALE);
+            rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
+        }
+    }
+}
+
 // ---- lookup modes -------------------------------------------------------------------------------------------------------------------
 // The kernel's first template parameter, as in points_mlp_gen_kernel.hpp.  ix: the footprint of any 4-tap lookup (ix_interp / ix_padding,
 // DINER_INDEX_*; common.hpp latent_footprint) instead of bilinear / border; bc: the 16-tap bicubic lookup (common.hpp bicubic_footprint)
@@ -234,14 +357,11 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
     const int NT = L.NT, H = L.H;
     const int sb = blockIdx.y;
     const int64_t P = NR * (int64_t)K;
-    int64_t tile;   // XCD-aware tile order (points_mlp.hip)
-    {
-        const int64_t nwg = gridDim.x, b = blockIdx.x, q = nwg / 8, r = nwg % 8, xcd = b % 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
+    const int64_t tile = xcd_tile(gridDim.x, blockIdx.x);
     const h8 *Wh = (const h8 *)Wp;
     const float *bias = Wp + L.off_bias;
 
+    // ---- this thread's point: sample p of the scene, at o + z d on its ray ----------
     const int row = tid & 63;
     int64_t p = tile * TILE_P + row;
     if (p > P - 1) p = P - 1;  // tail tile: duplicate the last point, masked at the store
@@ -251,16 +371,10 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
     const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
     const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
 
-    f32x16 x[RB][CT], net[RB][CT], xsum[RB][CT];
-#pragma unroll
-    for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = 0.0f;
+    f32x16 x[RB][CT], xsum[RB][CT];
+    acc_zero(xsum);
 
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
-    const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+    const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
     const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
     // float4 per texel the taps address.  lz: of a lin_z map, the latent itself is never read; else of the latent
     const int c4 = Mode::lz ? H / 4 : L.dlat / 4;
@@ -268,40 +382,47 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
     for (int v = 0; v < s.NV; ++v) {
         // ---- geometry + positional encodings -> planes 0 .. 2 nkb_in of A (a wave writes whole planes); footprint -> taps ----------
         {
-            const View vw = load_view(s, sb, v);
             float px, py, pz, u, w;
-            project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // pixelnerf.py:91-93,105-108
-            float dcx, dcy, dcz;
-            rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :99-101
-            const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-            const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-            const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-            const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :114-115
-            const float half_pi = 1.5707963267948966f;
-            for (int pl = wave; pl < 2 * L.nkb_in; pl += NWAVES) {              // input layout :128
-                unsigned ph[4], plo[4];
+            if constexpr (Mode::lz) {   // view_geometry + store_input_plane, written out: through input_element Lz<2,2> spills 123 VGPRs, not 122
+                const View vw = load_view(s, sb, v);
+                project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // pixelnerf.py:91-93,105-108
+                float dcx, dcy, dcz;
+                rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :99-101
+                const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
+                const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
+                const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
+                const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :114-115
+                const float half_pi = 1.5707963267948966f;
+                for (int pl = wave; pl < 2 * L.nkb_in; pl += NWAVES) {              // input layout :128
+                    unsigned ph[4], plo[4];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    _Float16 hi[2], lo[2];
+                    for (int jj = 0; jj < 4; ++jj) {
+                        _Float16 hi[2], lo[2];
 #pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int e = pl * 8 + jj * 2 + j2;
-                        float val;
-                        if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-                        else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-                            val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                        else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-                        else if (e == e_dir) val = delta;
-                        else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-                            val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                        else val = 0.0f;
-                        split(val * ACT_SCALE, hi[j2], lo[j2]);
+                        for (int j2 = 0; j2 < 2; ++j2) {
+                            const int e = pl * 8 + jj * 2 + j2;
+                            float val;
+                            if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
+                            else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
+                                val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
+                            else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
+                            else if (e == e_dir) val = delta;
+                            else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
+                                val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
+                            else val = 0.0f;
+                            split(val * ACT_SCALE, hi[j2], lo[j2]);
+                        }
+                        ph[jj] = pack2(hi[0], hi[1]); plo[jj] = pack2(lo[0], lo[1]);
                     }
-                    ph[jj] = pack2(hi[0], hi[1]); plo[jj] = pack2(lo[0], lo[1]);
+                    const u32x4 vh = {ph[0], ph[1], ph[2], ph[3]}, vl = {plo[0], plo[1], plo[2], plo[3]};
+                    A[a_slot(pl, 0, row)] = vh;
+                    A[a_slot(pl, 1, row)] = vl;
                 }
-                const u32x4 vh = {ph[0], ph[1], ph[2], ph[3]}, vl = {plo[0], plo[1], plo[2], plo[3]};
-                A[a_slot(pl, 0, row)] = vh;
-                A[a_slot(pl, 1, row)] = vl;
+            } else {
+                float dcx, dcy, dcz, delta;
+                view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);   // pixelnerf.py:91-115
+                for (int pl = wave; pl < 2 * L.nkb_in; pl += NWAVES)                                          // input layout :128
+                    store_input_plane(A, pl, row, px, py, pz, dcx, dcy, dcz, delta, F, s.freq_factor);
             }
             if constexpr (Mode::bc) {
                 if (wave == 0) {  // the 4 x 4 bicubic footprint in the latent map (image_encoder.py:97-127; common.hpp); the scale rides on cy
@@ -315,14 +436,8 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
                     taps[row] = t;
                 }
             } else {
-                if (wave == 0) {  // footprint of the lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
-                    const LatentFoot f = latent_footprint<Mode::ix>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
-                    Tap t;
-                    t.o00 = (f.y0 * s.w + f.x0) * c4; t.o01 = (f.y0 * s.w + f.x1) * c4;
-                    t.o10 = (f.y1 * s.w + f.x0) * c4; t.o11 = (f.y1 * s.w + f.x1) * c4;
-                    t.nw = f.nw * ACT_SCALE; t.ne = f.ne * ACT_SCALE; t.sw = f.sw * ACT_SCALE; t.se = f.se * ACT_SCALE;
-                    taps[row] = t;
-                }
+                if (wave == 0)   // footprint of the lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
+                    taps[row] = tap_of(latent_footprint<Mode::ix>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding), s.w, c4);
             }
         }
         __syncthreads();
@@ -366,8 +481,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
                         const Tap t = taps[r];
                         const f32x4 a = mp[t.o00 + q], bb = mp[t.o01 + q], c = mp[t.o10 + q], d = mp[t.o11 + q];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
-                            val[i] = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+                        for (int i = 0; i < 4; ++i) val[i] = tap_sum(a[i], bb[i], c[i], d[i], t);
                     }
                     S4[r * c4 + (q ^ (r & msk))] = val;
                 }
@@ -444,9 +558,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
                                     const f32x4 a = lat[t.o00 + qq], bb = lat[t.o01 + qq], c = lat[t.o10 + qq], d = lat[t.o11 + qq];
                                     _Float16 hi[4], lo[4];
 #pragma unroll
-                                    for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
-                                        split(__builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw))),
-                                              hi[i], lo[i]);
+                                    for (int i = 0; i < 4; ++i) split(tap_sum(a[i], bb[i], c[i], d[i], t), hi[i], lo[i]);
                                     ph[2 * half] = pack2(hi[0], hi[1]); ph[2 * half + 1] = pack2(hi[2], hi[3]);
                                     plo[2 * half] = pack2(lo[0], lo[1]); plo[2 * half + 1] = pack2(lo[2], lo[3]);
                                 }
@@ -461,84 +573,11 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_kernel(DinerSc
                     __syncthreads();
                 }
             }
-            store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
-            __syncthreads();
-            acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-            gemm(net, A8, Wh + (L.off_fc0 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
-            __syncthreads();
-            store_act(net, A, L.beta, rb0, ct0, NT, lane);                                          // :63 fc_1(act(net))
-            __syncthreads();
-            acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                 // :69 x + dx
-            gemm(x, A8, Wh + (L.off_fc1 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
-            __syncthreads();
+            resnet_block(x, A, Wp, L, b, rb0, ct0, lane);
         }
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn) xsum[tm][tn] += x[tm][tn];                              // :146-149
+        acc_add(xsum, x);                                                                           // :146-149
     }
-    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
-        const float nv = (float)s.NV;
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
-    }
-    for (int b = L.nvb; b < L.nb; ++b) {
-        store_act(xsum, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-        gemm(net, A8, Wh + (L.off_fc0 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
-        __syncthreads();
-        store_act(net, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(xsum, bias + L.bias_fc1(b), true, ct0, NT, lane);
-        gemm(xsum, A8, Wh + (L.off_fc1 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
-        __syncthreads();
-    }
-    // ---- lin_out(act(x)) (:158) in fp32 on the VALU: every lane's partial dot products over its own features -> LDS (the A image is
-    // free: the barrier above), [slot = 2 (tile group) + h][point][4]; a tile group past NT contributes zeros ----------------------
-    {
-        float *red = (float *)lds;
-        const float *wout = Wp + L.off_wout;
-        const int h = lane >> 5, grp = RB == 2 ? wave : (wave >> 1);
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm) {
-            float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn) {
-                if (ct0 + tn >= NT) continue;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float a[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) a[j] = act(xsum[tm][tn][4 * g + j], L.beta);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const f32x4 wq = *(const f32x4 *)(wout + c * H + (ct0 + tn) * 32 + 8 * g + 4 * h);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) o[c] = __builtin_fmaf(a[j], wq[j], o[c]);
-                    }
-                }
-            }
-            const f32x4 ov = {o[0], o[1], o[2], o[3]};
-            ((f32x4 *)red)[(grp * 2 + h) * TILE_P + (rb0 + tm) * 32 + (lane & 31)] = ov;
-        }
-        __syncthreads();
-        if (tid < TILE_P * 4) {
-            const int r = tid >> 2, c = tid & 3;
-            const int ngrp = RB == 2 ? NWAVES : NWAVES / 2;   // <1,1>: the point block of r was written by the waves of its parity only
-            float sum = 0.0f;
-            for (int g = 0; g < 2 * ngrp; ++g) sum += red[(g * TILE_P + r) * 4 + c];
-            const int64_t pp = tile * TILE_P + r;
-            if (pp < P) {
-                const float val = (sum + bias[L.bias_lin_out() + c]) * (1.0f / ACT_SCALE);          // pixelnerf.py:139-143
-                rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
-            }
-        }
-    }
+    finish(xsum, A, Wp, L, s.NV, rb0, ct0, tid, sb, tile, P, rgbsigma);
 }
 // ---- launch ---------------------------------------------------------------------------------------------------------------------------
 struct Launch {   // what a validated call passes to a mode's launcher (points_mlp_gen_f16.hip validate())

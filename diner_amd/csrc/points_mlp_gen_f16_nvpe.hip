@@ -7,22 +7,14 @@
 // scaled where it enters; the sum is formed in fp32 and split hi / lo once.  The GEMM's K is d_latent = C + 8, the texel stride of D
 // and gen_latent C / 4 float4.
 //
-// Layout, gemm(), acc_bias(), act(), store_act(), the Tap record and the packed weight image (diner_pack_mlp_gen_f16) are those of
-// points_mlp_gen_f16_kernel.hpp, unchanged.  LDS: the 128-KiB A image + two Taps per point + 8 floats per point.  No atomics.
+// The packed weight image (diner_pack_mlp_gen_f16), the tap records and the input stage are points_mlp_gen_f16_kernel.hpp's and
+// common.hpp's building blocks.  The ResNet blocks and the finish are written out here, not taken from that header's resnet_block() /
+// finish(): through either one alone <2,1> spills 104 to 105 VGPRs instead of 80.  LDS: the 128-KiB A image + two Taps per point + 8 floats per point.  No atomics.
 #include "points_mlp_gen_f16_kernel.hpp"
 #include "points_mlp_gen_nvpe.hpp"
 
 namespace diner {
 namespace genf16 {
-
-__device__ __forceinline__ Tap pe_tap_of(const LatentFoot &f, int lw, int c4)   // the weights * 2^-4
-{
-    Tap t;
-    t.o00 = (f.y0 * lw + f.x0) * c4; t.o01 = (f.y0 * lw + f.x1) * c4;
-    t.o10 = (f.y1 * lw + f.x0) * c4; t.o11 = (f.y1 * lw + f.x1) * c4;
-    t.nw = f.nw * ACT_SCALE; t.ne = f.ne * ACT_SCALE; t.sw = f.sw * ACT_SCALE; t.se = f.se * ACT_SCALE;
-    return t;
-}
 
 constexpr int NVPE_LDS_SLOTS = A_H8 + 2 * TILE_P * (int)(sizeof(Tap) / sizeof(u32x4)) + 2 * TILE_P;
 
@@ -42,11 +34,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_nvpe_kernel(Di
     const int NT = L.NT, H = L.H;
     const int sb = blockIdx.y;
     const int64_t P = n.P;
-    int64_t tile;   // XCD-aware tile order (points_mlp.hip)
-    {
-        const int64_t nwg = gridDim.x, b = blockIdx.x, q = nwg / 8, r = nwg % 8, xcd = b % 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
+    const int64_t tile = xcd_tile(gridDim.x, blockIdx.x);
     const h8 *Wh = (const h8 *)Wp;
     const float *bias = Wp + L.off_bias;
 
@@ -58,38 +46,22 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_nvpe_kernel(Di
     const float dwx = dp[0], dwy = dp[1], dwz = dp[2];     // :232-234
 
     f32x16 x[RB][CT], net[RB][CT], xsum[RB][CT];
-#pragma unroll
-    for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = 0.0f;
+    acc_zero(xsum);
 
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
-    const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-    const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
+    const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
+    const int F = L.F;
     const int Cl = L.dlat - 8, c4 = Cl / 4;   // the latents' channels; float4 per texel of D and gen_latent: C / 4, NOT the GEMM's K / 4
 
-    if (L.nvb > 0 && wave == 0) {
+    if (L.nvb > 0 && wave == 0)
         // ---- the general footprint, once per point (:220-222, :243-246, index() :117-128).  The first barrier of the view loop
         // publishes it.
-        const float *gx = n.xyz_gen + ((int64_t)sb * P + p) * 3;
-        const View gv = view_of(n.gposes, n.gfocal, n.gc, sb);
-        float px, py, pz, u, w;
-        project(gv, n.giw, n.gih, gx[0], gx[1], gx[2], px, py, pz, u, w);
-        const float sxg = ((float)n.gw - s.feature_padding * 2.0f) / (float)n.gw;
-        const float syg = ((float)n.gh - s.feature_padding * 2.0f) / (float)n.gh;
-        gtaps[row] = pe_tap_of(latent_footprint<true>(u, w, sxg, syg, n.gw, n.gh, n.ix_interp, n.ix_padding), n.gw, c4);
-    }
+        gtaps[row] = tap_of(camera_footprint(view_of(n.gposes, n.gfocal, n.gc, sb), n.giw, n.gih, n.xyz_gen + ((int64_t)sb * P + p) * 3,
+                                             n.gh, n.gw, s.feature_padding, n.ix_interp, n.ix_padding), n.gw, c4);
     float tpx = 0.0f, tpy = 0.0f, tpz = 0.0f;   // wave 1: this point's tgt_pe
     if (L.nvb > 0 && wave == 1) {
         // ---- tgt_pe, once per point (:224-226, :248-251, :262): the same in every view
-        const float *tx = n.xyz_tgt + ((int64_t)sb * P + p) * 3;
-        const View tv = view_of(n.tposes, n.tfocal, n.tc, sb);
-        float px, py, pz, u, w;
-        project(tv, n.tiw, n.tih, tx[0], tx[1], tx[2], px, py, pz, u, w);
-        const float4 t = pe_lookup((const float4 *)n.tpe + (int64_t)sb * n.tph * n.tpw, n.tph, n.tpw, u, w, s.feature_padding, n.ix_interp,
-                                   n.ix_padding);
+        const float4 t = pe_lookup_at((const float4 *)n.tpe + (int64_t)sb * n.tph * n.tpw, n.tph, n.tpw, view_of(n.tposes, n.tfocal, n.tc, sb),
+                                      n.tiw, n.tih, n.xyz_tgt + ((int64_t)sb * P + p) * 3, s.feature_padding, n.ix_interp, n.ix_padding);
         tpx = t.x * ACT_SCALE; tpy = t.y * ACT_SCALE; tpz = t.z * ACT_SCALE;
     }
     const f32x4 *glat = (const f32x4 *)n.glat;
@@ -98,43 +70,12 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_nvpe_kernel(Di
     for (int v = 0; v < s.NV; ++v) {
         // ---- geometry + positional encodings -> planes 0 .. 2 nkb_in of A (a wave writes whole planes); footprint -> taps ----------
         {
-            const View vw = load_view(s, sb, v);
-            float px, py, pz, u, w;
-            project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // :216-218, :238-241
-            float dcx, dcy, dcz;
-            rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :233-234
-            const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-            const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-            const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-            const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :271-272
-            const float half_pi = 1.5707963267948966f;
-            for (int pl = wave; pl < 2 * L.nkb_in; pl += NWAVES) {              // input layout :275 (after the latent and the pe)
-                unsigned ph[4], plo[4];
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    _Float16 hi[2], lo[2];
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int e = pl * 8 + jj * 2 + j2;
-                        float val;
-                        if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-                        else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-                            val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                        else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-                        else if (e == e_dir) val = delta;
-                        else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-                            val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                        else val = 0.0f;
-                        split(val * ACT_SCALE, hi[j2], lo[j2]);
-                    }
-                    ph[jj] = pack2(hi[0], hi[1]); plo[jj] = pack2(lo[0], lo[1]);
-                }
-                const u32x4 vh = {ph[0], ph[1], ph[2], ph[3]}, vl = {plo[0], plo[1], plo[2], plo[3]};
-                A[a_slot(pl, 0, row)] = vh;
-                A[a_slot(pl, 1, row)] = vl;
-            }
+            float px, py, pz, u, w, dcx, dcy, dcz, delta;
+            view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);
+            for (int pl = wave; pl < 2 * L.nkb_in; pl += NWAVES)
+                store_input_plane(A, pl, row, px, py, pz, dcx, dcy, dcz, delta, F, s.freq_factor);
             if (wave == 0)   // footprint of the lookup mode in the encoder's latent map = in D (image_encoder.py:97-127; common.hpp)
-                taps[row] = pe_tap_of(latent_footprint<true>(u, w, sxl, syl, s.w, s.h, n.ix_interp, n.ix_padding), s.w, c4);
+                taps[row] = tap_of(latent_footprint<true>(u, w, sxl, syl, s.w, s.h, n.ix_interp, n.ix_padding), s.w, c4);
             if (L.nvb > 0 && wave == 1) {   // src_pe at the encoder lookup's uv, in this view's own map (:134-165, :260)
                 const float4 sp = pe_lookup((const float4 *)n.spe + ((int64_t)sb * s.NV + v) * n.sph * n.spw, n.sph, n.spw, u, w,
                                             s.feature_padding, n.ix_interp, n.ix_padding);
@@ -177,8 +118,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_nvpe_kernel(Di
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) {  // each lookup in ATen's accumulation order nw,ne,sw,se with contracted FMAs
                                     const f32x4 h0 = head[(4 * qq + i) * 2], h1 = head[(4 * qq + i) * 2 + 1];
-                                    const float zd = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
-                                    const float zg = __builtin_fmaf(gd[i], g.se, __builtin_fmaf(gc[i], g.sw, __builtin_fmaf(gb[i], g.ne, ga[i] * g.nw)));
+                                    const float zd = tap_sum(a[i], bb[i], c[i], d[i], t), zg = tap_sum(ga[i], gb[i], gc[i], gd[i], g);
                                     float hd = h1[2] * ACT_SCALE;                                   // b_d[c], then the six pe terms
                                     hd = __builtin_fmaf(h0[0], p0[0], hd); hd = __builtin_fmaf(h0[1], p0[1], hd);
                                     hd = __builtin_fmaf(h0[2], p0[2], hd); hd = __builtin_fmaf(h0[3], p0[3], hd);
@@ -209,10 +149,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_f16_nvpe_kernel(Di
             gemm(x, A8, Wh + (L.off_fc1 + b * L.w_h) / 8, H / 16, 0, H / 16, rb0, ct0, NT, lane);
             __syncthreads();
         }
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn) xsum[tm][tn] += x[tm][tn];                              // :146-149
+        acc_add(xsum, x);                                                                           // :146-149
     }
     {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
         const float nv = (float)s.NV;

@@ -1,5 +1,8 @@
 // Device code of the shape-general fp32 point/MLP kernels (points_mlp_gen.hip has the description): the packed weight layout, the LDS A
-// image, the MFMA GEMM, the tap records, the kernel template and its launcher.  One lookup mode = one instantiation of the template,
+// image, the MFMA GEMM, the tap records, the building blocks every kernel of the family is made of (tap_of, resnet_block, finish; the
+// view geometry, the input columns and the tile order are common.hpp's), the kernel template and its launcher.  Each kernel shows its
+// inputs, its per-point records, the view loop (input stage, lin_in, gather, resnet_block) and the finish; the gathers stay in the
+// kernels.  One lookup mode = one instantiation of the template,
 // each in a translation unit of its own (points_mlp_gen.hip and points_mlp_gen_{ix,bc,lz,lz_bc}.hip); linz_maps_gen.hip takes the
 // layout and gemm() only.
 #pragma once
@@ -157,6 +160,90 @@ struct TapBc {      // bicubic footprint of one (point, view) in the latent map 
     float cx[4], cy[4];      // weights per axis; zeros padding: 0 for a column / row outside the map
 };
 
+// ---- building blocks of the kernels: points_mlp_gen_kernel below and the forms of it that units of their own define ----
+// the Tap of a 4-tap footprint in a map lw texels wide, c4 float4 per texel
+__device__ __forceinline__ Tap tap_of(const LatentFoot &f, int lw, int c4)
+{
+    Tap t;
+    t.o00 = (f.y0 * lw + f.x0) * c4; t.o01 = (f.y0 * lw + f.x1) * c4;
+    t.o10 = (f.y1 * lw + f.x0) * c4; t.o11 = (f.y1 * lw + f.x1) * c4;
+    t.nw = f.nw; t.ne = f.ne; t.sw = f.sw; t.se = f.se;
+    return t;
+}
+
+// ResNet block b on the hidden state x (resnetfc.py:62-69): x = x + fc_1(act(fc_0(act(x)))).  The A
+// image must be free on entry and is free on return (four barriers).
+template <int RB, int CT>
+__device__ __forceinline__ void resnet_block(f32x16 (&x)[RB][CT], float *A, const float *__restrict__ Wp, const Layout &L, int b,
+                                             int rb0, int ct0, int lane)
+{
+    const f32x4 *A4 = (const f32x4 *)A;
+    const float *bias = Wp + L.off_bias;
+    const int NT = L.NT, H = L.H;
+    f32x16 net[RB][CT];
+    store_act(x, A, L.beta, rb0, ct0, NT, lane);                                                    // :62 fc_0(act(x))
+    __syncthreads();
+    acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
+    gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+    __syncthreads();
+    store_act(net, A, L.beta, rb0, ct0, NT, lane);                                                  // :63 fc_1(act(net))
+    __syncthreads();
+    acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                         // :69 x + dx
+    gemm(x, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+    __syncthreads();
+}
+
+// what follows the view loop: combine() = the mean of the per-view states xsum over NV views (resnetfc.py:146-149), the blocks after
+// combine_layer, lin_out (:158) and the head (pixelnerf.py:139-143: sigmoid rgb, ReLU sigma) -> rgbsigma [SB,P,4], rows of the tail
+// tile past P masked
+template <int RB, int CT>
+__device__ __forceinline__ void finish(f32x16 (&xsum)[RB][CT], float *A, const float *__restrict__ Wp, const Layout &L,
+                                       int NV, int rb0, int ct0, int lane, int wave, int sb, int64_t tile,
+                                       int64_t P, float *__restrict__ rgbsigma)
+{
+    const f32x4 *A4 = (const f32x4 *)A;
+    const float *bias = Wp + L.off_bias;
+    const int H = L.H;
+    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
+        const float nv = (float)NV;
+#pragma unroll
+        for (int tm = 0; tm < RB; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < CT; ++tn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
+    }
+    for (int b = L.nvb; b < L.nb; ++b) resnet_block(xsum, A, Wp, L, b, rb0, ct0, lane);
+    store_act(xsum, A, L.beta, rb0, ct0, L.NT, lane);                                               // :158 lin_out(act(x))
+    __syncthreads();
+    if (wave < 2) {  // lin_out: one 32-column tile (4 real outputs), wave w = rows 32w..32w+31
+        f32x16 o;
+        const float bo = bias[L.bias_lin_out() + (lane & 31)];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = bo;
+        const f32x4 *ap = A4 + (lane >> 5) * TILE_P + wave * 32 + (lane & 31);
+        const f32x4 *bp = (const f32x4 *)(Wp + L.off_out) + lane;
+#pragma unroll 4
+        for (int jb = 0; jb < H / 8; ++jb) {
+            const f32x4 a = ap[jb * 2 * TILE_P], bq = bp[jb * 64];
+#pragma unroll
+            for (int ji = 0; ji < 4; ++ji) o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ji], bq[ji], o, 0, 0, 0);
+        }
+        const int c = lane & 31, h = lane >> 5;
+        if (c < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int r = wave * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
+                const int64_t pp = tile * TILE_P + r;
+                if (pp < P) {
+                    const float val = o[i];
+                    rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
+                }
+            }
+        }
+    }
+}
+
 // ---- lookup modes -------------------------------------------------------------------------------------------------------------------
 // The kernel's first template parameter.  ix: the footprint of any 4-tap lookup (ix_interp / ix_padding, DINER_INDEX_*; common.hpp
 // latent_footprint) instead of the written-out bilinear / border one; bc: the 16-tap bicubic lookup (common.hpp bicubic_footprint)
@@ -196,13 +283,10 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
     const int NT = L.NT, H = L.H;
     const int sb = blockIdx.y;
     const int64_t P = NR * (int64_t)K;
-    int64_t tile;   // XCD-aware tile order (points_mlp.hip)
-    {
-        const int64_t nwg = gridDim.x, b = blockIdx.x, q = nwg / 8, r = nwg % 8, xcd = b % 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
+    const int64_t tile = xcd_tile(gridDim.x, blockIdx.x);
     const float *bias = Wp + L.off_bias;
 
+    // ---- this thread's point: sample p of the scene, at o + z d on its ray ----------
     const int row = tid & 63;
     int64_t p = tile * TILE_P + row;
     if (p > P - 1) p = P - 1;  // tail tile: duplicate the last point, masked at the store
@@ -212,45 +296,22 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
     const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
     const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
 
-    f32x16 x[RB][CT], net[RB][CT], xsum[RB][CT];
-#pragma unroll
-    for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = 0.0f;
+    f32x16 x[RB][CT], xsum[RB][CT];
+    acc_zero(xsum);
 
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
-    const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-    const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1, din_pad = 8 * L.njb_in;
+    const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
+    const int F = L.F, din_pad = 8 * L.njb_in;
     // float4 per texel the taps address.  lz: of a lin_z map, the latent itself is never read; else of the latent
     const int c4 = Mode::lz ? H / 4 : L.dlat / 4;
 
     for (int v = 0; v < s.NV; ++v) {
-        // ---- geometry + positional encodings -> A[:, 0:din_pad]; bilinear footprint -> taps ----------
+        // ---- geometry + positional encodings -> A[:, 0:din_pad]; bilinear footprint -> taps.  (The column loop is written in each
+        // kernel: inside a helper of its own the <2,2> kernels spill 4 to 7 VGPRs more.) ----------
         {
-            const View vw = load_view(s, sb, v);
-            float px, py, pz, u, w;
-            project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // pixelnerf.py:91-93,105-108
-            float dcx, dcy, dcz;
-            rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :99-101
-            const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-            const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-            const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-            const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :114-115
-            const float half_pi = 1.5707963267948966f;
-            for (int e = wave; e < din_pad; e += NWAVES) {                      // input layout :128
-                float val;
-                if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-                else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-                    val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-                else if (e == e_dir) val = delta;
-                else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-                    val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                else val = 0.0f;
-                A[a_off(row, e)] = val;
-            }
+            float px, py, pz, u, w, dcx, dcy, dcz, delta;
+            view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);   // pixelnerf.py:91-115
+            for (int e = wave; e < din_pad; e += NWAVES)                                                  // input layout :128
+                A[a_off(row, e)] = input_element(e, px, py, pz, dcx, dcy, dcz, delta, F, s.freq_factor);
             if constexpr (Mode::bc) {
                 if (wave == 0) {  // the 4 x 4 bicubic footprint in the latent map (image_encoder.py:97-127; common.hpp)
                     const BicubicFoot f = bicubic_footprint(u, w, sxl, syl, s.w, s.h, ix_padding);
@@ -260,14 +321,8 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
                     taps[row] = t;
                 }
             } else if constexpr (Mode::ix) {
-                if (wave == 0) {  // footprint of any lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
-                    const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
-                    Tap t;
-                    t.o00 = (f.y0 * s.w + f.x0) * c4; t.o01 = (f.y0 * s.w + f.x1) * c4;
-                    t.o10 = (f.y1 * s.w + f.x0) * c4; t.o11 = (f.y1 * s.w + f.x1) * c4;
-                    t.nw = f.nw; t.ne = f.ne; t.sw = f.sw; t.se = f.se;
-                    taps[row] = t;
-                }
+                if (wave == 0)   // footprint of any lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
+                    taps[row] = tap_of(latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding), s.w, c4);
             } else if (wave == 0) {  // bilinear / border footprint in the latent map (image_encoder.py:97-127; = latent_footprint<false>,
                                      // written out: through the helper the compiler schedules this kernel differently)
                 const float ix = clipf(unnorm(u * sxl, (float)s.w / 2.0f), (float)(s.w - 1));
@@ -325,8 +380,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
                         const Tap t = taps[r];
                         const f32x4 a = mp[t.o00 + q], bb = mp[t.o01 + q], c = mp[t.o10 + q], d = mp[t.o11 + q];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
-                            val[i] = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+                        for (int i = 0; i < 4; ++i) val[i] = tap_sum(a[i], bb[i], c[i], d[i], t);
                     }
                     *(f32x4 *)(S + r * LD + ((4 * q) ^ (((r >> 2) & 1) << 5))) = val;
                 }
@@ -383,9 +437,7 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
                                 const int qq = k0 / 4 + q;
                                 const f32x4 a = lat[t.o00 + qq], bb = lat[t.o01 + qq], c = lat[t.o10 + qq], d = lat[t.o11 + qq];
 #pragma unroll
-                                for (int i = 0; i < 4; ++i)  // ATen's accumulation order nw,ne,sw,se with contracted FMAs
-                                    A[a_off(r, 4 * q + i)] =
-                                        __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
+                                for (int i = 0; i < 4; ++i) A[a_off(r, 4 * q + i)] = tap_sum(a[i], bb[i], c[i], d[i], t);
                             }
                         }
                     }
@@ -394,71 +446,25 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_kernel(DinerScene 
                     __syncthreads();
                 }
             }
-            store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
-            __syncthreads();
-            acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-            gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-            __syncthreads();
-            store_act(net, A, L.beta, rb0, ct0, NT, lane);                                          // :63 fc_1(act(net))
-            __syncthreads();
-            acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                 // :69 x + dx
-            gemm(x, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn) xsum[tm][tn] += x[tm][tn];                              // :146-149
-    }
-    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
-        const float nv = (float)s.NV;
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
-    }
-    for (int b = L.nvb; b < L.nb; ++b) {
-        store_act(xsum, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-        gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-        __syncthreads();
-        store_act(net, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(xsum, bias + L.bias_fc1(b), true, ct0, NT, lane);
-        gemm(xsum, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-        __syncthreads();
-    }
-    store_act(xsum, A, L.beta, rb0, ct0, NT, lane);                                                 // :158 lin_out(act(x))
-    __syncthreads();
-    if (wave < 2) {  // lin_out: one 32-column tile (4 real outputs), wave w = rows 32w..32w+31
-        f32x16 o;
-        const float bo = bias[L.bias_lin_out() + (lane & 31)];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = bo;
-        const f32x4 *ap = A4 + (lane >> 5) * TILE_P + wave * 32 + (lane & 31);
-        const f32x4 *bp = (const f32x4 *)(Wp + L.off_out) + lane;
-#pragma unroll 4
-        for (int jb = 0; jb < H / 8; ++jb) {
-            const f32x4 a = ap[jb * 2 * TILE_P], bq = bp[jb * 64];
-#pragma unroll
-            for (int ji = 0; ji < 4; ++ji) o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ji], bq[ji], o, 0, 0, 0);
-        }
-        const int c = lane & 31, h = lane >> 5;
-        if (c < 4) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int r = wave * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
-                const int64_t pp = tile * TILE_P + r;
-                if (pp < P) {
-                    const float val = o[i];                                                         // pixelnerf.py:139-143
-                    rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
-                }
+            if constexpr (Mode::bc && !Mode::lz) {   // resnet_block(), written out: through the helper Bc<2,1> spills 36 SGPRs, not 33
+                f32x16 net[RB][CT];
+                store_act(x, A, L.beta, rb0, ct0, NT, lane);
+                __syncthreads();
+                acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
+                gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+                __syncthreads();
+                store_act(net, A, L.beta, rb0, ct0, NT, lane);
+                __syncthreads();
+                acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);
+                gemm(x, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
+                __syncthreads();
+            } else {
+                resnet_block(x, A, Wp, L, b, rb0, ct0, lane);
             }
         }
+        acc_add(xsum, x);                                                                           // :146-149
     }
+    finish(xsum, A, Wp, L, s.NV, rb0, ct0, lane, wave, sb, tile, P, rgbsigma);
 }
 // ---- launch ---------------------------------------------------------------------------------------------------------------------------
 struct Launch {   // what a validated call passes to a mode's launcher (points_mlp_gen.hip validate())

@@ -10,10 +10,11 @@
 // and stores lookup(latent) + lookup(gen_latent): the sum is formed BEFORE lin_z, as in the reference.  The two lookups are fma chains
 // in ATen's order nw, ne, sw, se; with gen_latent = 0 the sum is the encoder's lookup bit for bit.
 //
-// Layout, gemm(), acc_bias(), store_act(), the Tap record and the packed weight image (diner_pack_mlp_gen) are those of
-// points_mlp_gen_kernel.hpp, unchanged; the kernel below is that header's template without its mode parameter: the footprint is always
-// common.hpp's latent_footprint<true> (any 4-tap lookup, bilinear / border included: the same taps and weights as the written-out
-// form for every finite coordinate).  Bicubic and the lin_z-map forms are not served.  LDS: the 128-KiB A image + two Taps per row.
+// This unit holds what is the NOVEL model's own: the given points, the general tap record and the gather of the sum.  The packed weight
+// image (diner_pack_mlp_gen), the input stage, lin_in, the ResNet blocks and the finish are points_mlp_gen_kernel.hpp's building blocks.
+// The footprint is always common.hpp's latent_footprint<true> (any 4-tap lookup, bilinear / border included: the same taps and weights
+// as the written-out form for every finite coordinate).  Bicubic and the lin_z-map forms are not served.  LDS: the 128-KiB A image +
+// two Taps per row.
 #include "points_mlp_gen_kernel.hpp"
 
 namespace diner {
@@ -29,15 +30,6 @@ struct NovelIn {            // what a validated diner_render_points_novel call h
     int ix_interp, ix_padding;                  // DINER_INDEX_* of both lookups
 };
 
-__device__ __forceinline__ Tap tap_of(const LatentFoot &f, int lw, int c4)
-{
-    Tap t;
-    t.o00 = (f.y0 * lw + f.x0) * c4; t.o01 = (f.y0 * lw + f.x1) * c4;
-    t.o10 = (f.y1 * lw + f.x0) * c4; t.o11 = (f.y1 * lw + f.x1) * c4;
-    t.nw = f.nw; t.ne = f.ne; t.sw = f.sw; t.se = f.se;
-    return t;
-}
-
 template <int RB, int CT>
 __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_nv_kernel(DinerScene s, Layout L, const float *__restrict__ Wp, NovelIn n,
                                                                         float *__restrict__ rgbsigma)
@@ -50,16 +42,13 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_nv_kernel(DinerSce
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rb0 = RB == 2 ? 0 : (wave & 1), ct0 = RB == 2 ? wave * CT : (wave >> 1) * CT;
-    const int NT = L.NT, H = L.H;
+    const int NT = L.NT;
     const int sb = blockIdx.y;
     const int64_t P = n.P;
-    int64_t tile;   // XCD-aware tile order (points_mlp.hip)
-    {
-        const int64_t nwg = gridDim.x, b = blockIdx.x, q = nwg / 8, r = nwg % 8, xcd = b % 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
+    const int64_t tile = xcd_tile(gridDim.x, blockIdx.x);
     const float *bias = Wp + L.off_bias;
 
+    // ---- this thread's point: given ----------
     const int row = tid & 63;
     int64_t p = tile * TILE_P + row;
     if (p > P - 1) p = P - 1;  // tail tile: duplicate the last point, masked at the store
@@ -67,64 +56,28 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_nv_kernel(DinerSce
     const float wx = xp[0], wy = xp[1], wz = xp[2];        // novel_pixelnerf.py:159
     const float dwx = dp[0], dwy = dp[1], dwz = dp[2];     // :171
 
-    f32x16 x[RB][CT], net[RB][CT], xsum[RB][CT];
-#pragma unroll
-    for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = 0.0f;
+    f32x16 x[RB][CT], xsum[RB][CT];
+    acc_zero(xsum);
 
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w;  // image_encoder.py:113-114
-    const float syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-    const int F = L.F, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1, din_pad = 8 * L.njb_in;
+    const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
+    const int F = L.F, din_pad = 8 * L.njb_in;
     const int c4 = L.dlat / 4;   // float4 per texel of either latent
 
-    if (L.nvb > 0 && wave == 0) {
+    if (L.nvb > 0 && wave == 0)
         // ---- the general footprint, once per point (:163-165, :183-186, index() :126-137): its own map size in the footprint and in
         // the feature-padding scale.  The first barrier of the view loop publishes it.
-        const float *gx = n.xyz_gen + ((int64_t)sb * P + p) * 3;
-        View gv;
-        const float *Pm = n.gposes + (int64_t)sb * 16;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            gv.r[i * 3 + 0] = Pm[i * 4 + 0]; gv.r[i * 3 + 1] = Pm[i * 4 + 1]; gv.r[i * 3 + 2] = Pm[i * 4 + 2];
-            gv.t[i] = Pm[i * 4 + 3];
-        }
-        gv.fx = n.gfocal[sb * 2]; gv.fy = n.gfocal[sb * 2 + 1]; gv.cx = n.gc[sb * 2]; gv.cy = n.gc[sb * 2 + 1];
-        float px, py, pz, u, w;
-        project(gv, n.giw, n.gih, gx[0], gx[1], gx[2], px, py, pz, u, w);
-        const float sxg = ((float)n.gw - s.feature_padding * 2.0f) / (float)n.gw;
-        const float syg = ((float)n.gh - s.feature_padding * 2.0f) / (float)n.gh;
-        gtaps[row] = tap_of(latent_footprint<true>(u, w, sxg, syg, n.gw, n.gh, n.ix_interp, n.ix_padding), n.gw, c4);
-    }
+        gtaps[row] = tap_of(camera_footprint(view_of(n.gposes, n.gfocal, n.gc, sb), n.giw, n.gih, n.xyz_gen + ((int64_t)sb * P + p) * 3,
+                                             n.gh, n.gw, s.feature_padding, n.ix_interp, n.ix_padding), n.gw, c4);
     const f32x4 *glat = (const f32x4 *)n.glat;
 
     for (int v = 0; v < s.NV; ++v) {
-        // ---- geometry + positional encodings -> A[:, 0:din_pad]; the encoder's footprint -> taps ----------
+        // ---- geometry + positional encodings -> A[:, 0:din_pad] (:160-161, :172-180, :199-200; input layout :225, after the latent);
+        // the encoder's footprint -> taps ----------
         {
-            const View vw = load_view(s, sb, v);
-            float px, py, pz, u, w;
-            project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);   // :160-161, :177-180
-            float dcx, dcy, dcz;
-            rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                            // :172-173
-            const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-            const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-            const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-            const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;     // :199-200
-            const float half_pi = 1.5707963267948966f;
-            for (int e = wave; e < din_pad; e += NWAVES) {                      // input layout :225 (after the latent)
-                float val;
-                if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-                else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-                    val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-                else if (e == e_dir) val = delta;
-                else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-                    val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-                else val = 0.0f;
-                A[a_off(row, e)] = val;
-            }
+            float px, py, pz, u, w, dcx, dcy, dcz, delta;
+            view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);
+            for (int e = wave; e < din_pad; e += NWAVES)
+                A[a_off(row, e)] = input_element(e, px, py, pz, dcx, dcy, dcz, delta, F, s.freq_factor);
             if (wave == 0)   // footprint of the lookup mode in the encoder's latent map (image_encoder.py:97-127; common.hpp)
                 taps[row] = tap_of(latent_footprint<true>(u, w, sxl, syl, s.w, s.h, n.ix_interp, n.ix_padding), s.w, c4);
         }
@@ -147,82 +100,19 @@ __global__ __launch_bounds__(NWAVES * 64) void points_mlp_gen_nv_kernel(DinerSce
                         const f32x4 a = lat[t.o00 + qq], bb = lat[t.o01 + qq], c = lat[t.o10 + qq], d = lat[t.o11 + qq];
                         const f32x4 ga = glat[g.o00 + qq], gb = glat[g.o01 + qq], gc = glat[g.o10 + qq], gd = glat[g.o11 + qq];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {  // each lookup in ATen's accumulation order nw,ne,sw,se with contracted FMAs
-                            const float zl = __builtin_fmaf(d[i], t.se, __builtin_fmaf(c[i], t.sw, __builtin_fmaf(bb[i], t.ne, a[i] * t.nw)));
-                            const float zg = __builtin_fmaf(gd[i], g.se, __builtin_fmaf(gc[i], g.sw, __builtin_fmaf(gb[i], g.ne, ga[i] * g.nw)));
-                            A[a_off(r, 4 * q + i)] = zg + zl;                                       // novel_pixelnerf.py:196
-                        }
+                        for (int i = 0; i < 4; ++i)                                                 // novel_pixelnerf.py:196
+                            A[a_off(r, 4 * q + i)] = tap_sum(ga[i], gb[i], gc[i], gd[i], g) + tap_sum(a[i], bb[i], c[i], d[i], t);
                     }
                 }
                 __syncthreads();
                 gemm(x, A4, (const f32x4 *)(Wp + L.off_z + b * L.w_z), L.njb_lat, k0 / 8, kc4 / 2, rb0, ct0, NT, lane);
                 __syncthreads();
             }
-            store_act(x, A, L.beta, rb0, ct0, NT, lane);                                            // :62 fc_0(act(x))
-            __syncthreads();
-            acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-            gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-            __syncthreads();
-            store_act(net, A, L.beta, rb0, ct0, NT, lane);                                          // :63 fc_1(act(net))
-            __syncthreads();
-            acc_bias(x, bias + L.bias_fc1(b), true, ct0, NT, lane);                                 // :69 x + dx
-            gemm(x, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-            __syncthreads();
+            resnet_block(x, A, Wp, L, b, rb0, ct0, lane);
         }
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn) xsum[tm][tn] += x[tm][tn];                              // :146-149
+        acc_add(xsum, x);                                                                           // :146-149
     }
-    {   // combine(): mean over views (combine_layer >= n_blocks: NV = 1 and this divides by 1, i.e. is exact)
-        const float nv = (float)s.NV;
-#pragma unroll
-        for (int tm = 0; tm < RB; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < CT; ++tn)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) xsum[tm][tn][i] = xsum[tm][tn][i] / nv;
-    }
-    for (int b = L.nvb; b < L.nb; ++b) {
-        store_act(xsum, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(net, bias + L.bias_fc0(b), false, ct0, NT, lane);
-        gemm(net, A4, (const f32x4 *)(Wp + L.off_fc0 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-        __syncthreads();
-        store_act(net, A, L.beta, rb0, ct0, NT, lane);
-        __syncthreads();
-        acc_bias(xsum, bias + L.bias_fc1(b), true, ct0, NT, lane);
-        gemm(xsum, A4, (const f32x4 *)(Wp + L.off_fc1 + b * L.w_h), H / 8, 0, H / 8, rb0, ct0, NT, lane);
-        __syncthreads();
-    }
-    store_act(xsum, A, L.beta, rb0, ct0, NT, lane);                                                 // :158 lin_out(act(x))
-    __syncthreads();
-    if (wave < 2) {  // lin_out: one 32-column tile (4 real outputs), wave w = rows 32w..32w+31
-        f32x16 o;
-        const float bo = bias[L.bias_lin_out() + (lane & 31)];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = bo;
-        const f32x4 *ap = A4 + (lane >> 5) * TILE_P + wave * 32 + (lane & 31);
-        const f32x4 *bp = (const f32x4 *)(Wp + L.off_out) + lane;
-#pragma unroll 4
-        for (int jb = 0; jb < H / 8; ++jb) {
-            const f32x4 a = ap[jb * 2 * TILE_P], bq = bp[jb * 64];
-#pragma unroll
-            for (int ji = 0; ji < 4; ++ji) o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ji], bq[ji], o, 0, 0, 0);
-        }
-        const int c = lane & 31, h = lane >> 5;
-        if (c < 4) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int r = wave * 32 + 8 * (i >> 2) + 4 * h + (i & 3);
-                const int64_t pp = tile * TILE_P + r;
-                if (pp < P) {
-                    const float val = o[i];                                                         // novel_pixelnerf.py:236-240
-                    rgbsigma[((int64_t)sb * P + pp) * 4 + c] = c < 3 ? 1.0f / (1.0f + expf(-val)) : (val < 0.0f ? 0.0f : val);
-                }
-            }
-        }
-    }
+    finish(xsum, A, Wp, L, s.NV, rb0, ct0, lane, wave, sb, tile, P, rgbsigma);                 // head: novel_pixelnerf.py:236-240
 }
 
 // a call api.hip has validated (diner_render_points_novel): P > 0, SB > 0, the tile count fits a grid

@@ -1,5 +1,6 @@
 // What both precisions of the NOVEL_PE point kernels share (points_mlp_gen_nvpe.hip, points_mlp_gen_f16_nvpe.hip): the argument record
-// a validated diner_render_points_novel_pe call hands to the kernel, and the 3-channel lookup of a positional-encoding map.
+// a validated diner_render_points_novel_pe call hands to the kernel, and the 3-channel lookup of a positional-encoding map (the camera
+// record of a [SB,4,4] pose, view_of, is common.hpp's).
 #pragma once
 #include "common.hpp"
 
@@ -23,33 +24,23 @@ struct NovelPeIn {
     int ix_interp, ix_padding;                  // DINER_INDEX_* of all four lookups
 };
 
-__device__ __forceinline__ View view_of(const float *poses, const float *focal, const float *c, int sb)
-{
-    View v;
-    const float *Pm = poses + (int64_t)sb * 16;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        v.r[i * 3 + 0] = Pm[i * 4 + 0]; v.r[i * 3 + 1] = Pm[i * 4 + 1]; v.r[i * 3 + 2] = Pm[i * 4 + 2];
-        v.t[i] = Pm[i * 4 + 3];
-    }
-    v.fx = focal[sb * 2]; v.fy = focal[sb * 2 + 1]; v.cx = c[sb * 2]; v.cy = c[sb * 2 + 1];
-    return v;
-}
-
 // lookup of one [mh, mw, 4] map at uv with the encoder's feature_padding (scaled by the map's own size, as index() scales gen_latent's)
-// and lookup mode: ATen's accumulation order nw, ne, sw, se with contracted FMAs; .w is the padding channel
+// and lookup mode; .w is the padding channel
 __device__ __forceinline__ float4 pe_lookup(const float4 *__restrict__ map, int mh, int mw, float u, float w, float feature_padding,
                                             int interp, int padding)
 {
-    const float sx = ((float)mw - feature_padding * 2.0f) / (float)mw, sy = ((float)mh - feature_padding * 2.0f) / (float)mh;
-    const LatentFoot f = latent_footprint<true>(u, w, sx, sy, mw, mh, interp, padding);
+    const LatentFoot f = latent_footprint<true>(u, w, pad_scale(mw, feature_padding), pad_scale(mh, feature_padding), mw, mh, interp, padding);
     const float4 a = map[f.y0 * mw + f.x0], b = map[f.y0 * mw + f.x1], c = map[f.y1 * mw + f.x0], d = map[f.y1 * mw + f.x1];
-    float4 o;
-    o.x = __builtin_fmaf(d.x, f.se, __builtin_fmaf(c.x, f.sw, __builtin_fmaf(b.x, f.ne, a.x * f.nw)));
-    o.y = __builtin_fmaf(d.y, f.se, __builtin_fmaf(c.y, f.sw, __builtin_fmaf(b.y, f.ne, a.y * f.nw)));
-    o.z = __builtin_fmaf(d.z, f.se, __builtin_fmaf(c.z, f.sw, __builtin_fmaf(b.z, f.ne, a.z * f.nw)));
-    o.w = 0.0f;
-    return o;
+    return make_float4(tap_sum(a.x, b.x, c.x, d.x, f), tap_sum(a.y, b.y, c.y, d.y, f), tap_sum(a.z, b.z, c.z, d.z, f), 0.0f);
+}
+
+// the same lookup at a world point x seen by the scene's one camera `cam` of image shape (iw, ih): NOVEL_PE's tgt_pe
+__device__ __forceinline__ float4 pe_lookup_at(const float4 *__restrict__ map, int mh, int mw, const View &cam, float iw, float ih,
+                                               const float *x, float feature_padding, int interp, int padding)
+{
+    float px, py, pz, u, w;
+    project(cam, iw, ih, x[0], x[1], x[2], px, py, pz, u, w);
+    return pe_lookup(map, mh, mw, u, w, feature_padding, interp, padding);
 }
 
 }  // namespace diner

@@ -14,7 +14,7 @@ using namespace train_blocks;
 // ---- per-(view, point) MLP inputs of any num_freqs F and latent width C ---------------------------------------------------------
 // rows are view-major: row = v*P + p.  in [R, ld_in]: pixelnerf.py:128's 7 + 8F inputs in point_inputs_kernel's column order
 //   [x_cam 3 | sin(f_j x_cam + phi_j) 6F | R d_w 3 | depth_dist 1 | sin(f_j depth_dist + phi_j) 2F | 0 ...]
-// with sinf and the expression of the shape-general inference kernel (points_mlp_gen.hip); zlat [R, C]: the latent lookup of the
+// from common.hpp's input_element, the shape-general inference kernels' (points_mlp_gen.hip); zlat [R, C]: the latent lookup of the
 // scene's DINER_INDEX_* mode from the NHWC latent; taps [R, 8]: its 4 texel indices (int bits) and weights.
 // BC: taps [R, 16] = the 4 columns and 4 rows of the footprint (int bits), then cx[4], cy[4].
 template <bool BC>
@@ -32,30 +32,11 @@ __global__ __launch_bounds__(64) void point_inputs_gen_kernel(DinerScene s, cons
     const float zz = zsamp[(int64_t)sb * P + p];
     const float dwx = rp[3], dwy = rp[4], dwz = rp[5];
     const float wx = rp[0] + zz * dwx, wy = rp[1] + zz * dwy, wz = rp[2] + zz * dwz;  // nerf_renderer.py:304
-    const View vw = load_view(s, sb, v);
-    float px, py, pz, u, w, dcx, dcy, dcz;
-    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // pixelnerf.py:91-93,105-108
-    rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                                           // :99-101
-    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;                    // :114-115
-    const int F = s.num_freqs, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
-    const float half_pi = 1.5707963267948966f;
-    for (int e = lane; e < ld_in; e += 64) {
-        float val;
-        if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-        else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-            val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-        else if (e == e_dir) val = delta;
-        else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-            val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else val = 0.0f;
-        in[row * ld_in + e] = val;
-    }
+    float px, py, pz, u, w, dcx, dcy, dcz, delta;
+    view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);   // pixelnerf.py:91-115
+    for (int e = lane; e < ld_in; e += 64) in[row * ld_in + e] = input_element(e, px, py, pz, dcx, dcy, dcz, delta, s.num_freqs, s.freq_factor);
     // footprint of the lookup mode in the latent map (image_encoder.py:97-127; common.hpp)
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+    const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
     if constexpr (BC) {
         const BicubicFoot f = bicubic_footprint(u, w, sxl, syl, s.w, s.h, ix_padding);
         if (lane == 0) {
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(64) void point_inputs_gen_kernel(DinerScene s, cons
             float t[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) t[i] = lat[(int64_t)o[i] * s.C + ch];
-            zlat[row * s.C + ch] = __builtin_fmaf(t[3], wt[3], __builtin_fmaf(t[2], wt[2], __builtin_fmaf(t[1], wt[1], t[0] * wt[0])));
+            zlat[row * s.C + ch] = tap_sum(t[0], t[1], t[2], t[3], f);
         }
     }
 }
@@ -117,10 +98,8 @@ __global__ __launch_bounds__(64) void point_inputs_bwd_gen_kernel(DinerScene s, 
     const View vw = load_view(s, sb, v);
     float px, py, pz, u, w;
     project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // pixelnerf.py:91-93,105-108
-    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;
+    int ddx, ddy;   // view_geometry's pieces: the camera and the depth texel are needed below
+    const float delta = nearest_depth(s, sb, v, u, w, ddx, ddy) - pz;
 
     // positional encodings: d sin(f a + phi) / d a = f cos(f a + phi) (positional_encoding.py:45-49); lanes stride the inputs,
     // each lane sums its own in a fixed order before the wave sums
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(64) void point_inputs_bwd_gen_kernel(DinerScene s, 
     if constexpr (BC) {
         // bicubic: d/d ix = sum_ij dcx[i] cy[j] texel_ij, d/d iy = sum_ij cx[i] dcy[j] texel_ij; the padding acts on the integer tap
         // positions and puts no factor on the gradient (zeros: a tap outside the map has weight and derivative 0)
-        const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+        const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
         int xi[4], yi[4];
         float cx[4], cy[4], dcx[4], dcy[4];
         bicubic_axis(unnorm(u * sxl, (float)s.w / 2.0f), s.w, ix_padding, xi, cx, dcx);
@@ -172,7 +151,7 @@ __global__ __launch_bounds__(64) void point_inputs_bwd_gen_kernel(DinerScene s, 
             }
         }
     } else if (ix_interp == DINER_INDEX_BILINEAR) {
-        const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
+        const float sxl = pad_scale(s.w, s.feature_padding), syl = pad_scale(s.h, s.feature_padding);
         float gx, gy;
         const float ix = pad_coord_grad(unnorm(u * sxl, (float)s.w / 2.0f), s.w, ix_padding, gx);
         const float iy = pad_coord_grad(unnorm(w * syl, (float)s.h / 2.0f), s.h, ix_padding, gy);

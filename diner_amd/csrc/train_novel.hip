@@ -4,7 +4,7 @@
 // general camera per scene and added to the encoder's lookup in every view before lin_z (:196).  Under autograd d(final_latent) goes to
 // both maps, and index() (:108-141) repeats the one general map over the views, so its gradient sums over them.
 //   point_inputs_novel   point_inputs_gen_kernel<false> (train_gen_points.hpp) at given points: the same rows (row = v*P + p), the same
-//                        in [R, ld_in] columns with the same sinf expressions, the same taps [R,8] record of the encoder's lookup;
+//                        in [R, ld_in] columns (common.hpp's input_element), the same taps [R,8] record of the encoder's lookup;
 //                        zlat [R, C] = lookup(latent[sb, v], uv) + lookup(gen_latent, gen_uv), each an fma chain in ATen's order
 //                        nw, ne, sw, se and the sum formed last, as points_mlp_gen_nv.hip forms it (gen_latent = 0: the encoder's
 //                        lookup bit for bit); gen_taps [P,8]: the general footprint, which no view changes, written by view 0's rows.
@@ -14,7 +14,7 @@
 //                        and flushes one float atomicAdd per used tap on 256-byte contiguous NHWC rows; a tap of weight 0 is never
 //                        flushed.  All scenes accumulate into the one map.
 // The encoder latent's gradient needs nothing new: taps has bilinear_scatter_kernel's format.
-// latent_footprint, project, rotate, load_view: common.hpp's, shared with every other kernel.
+// view_geometry, input_element, latent_footprint, camera_footprint: common.hpp's, shared with the render kernels.
 #include "train_blocks.hpp"
 
 namespace diner {
@@ -43,49 +43,19 @@ __global__ __launch_bounds__(64) void point_inputs_novel_kernel(DinerScene s, co
     const float *xp = xyz_in + ((int64_t)sb * P + p) * 3, *dp = viewdirs + ((int64_t)sb * P + p) * 3;
     const float wx = xp[0], wy = xp[1], wz = xp[2];        // novel_pixelnerf.py:159
     const float dwx = dp[0], dwy = dp[1], dwz = dp[2];     // :171
-    const View vw = load_view(s, sb, v);
-    float px, py, pz, u, w, dcx, dcy, dcz;
-    project(vw, s.image_w, s.image_h, wx, wy, wz, px, py, pz, u, w);                  // :160-161, :177-180
-    rotate(vw, dwx, dwy, dwz, dcx, dcy, dcz);                                           // :172-173
-    const float4 *tex = (const float4 *)s.maps + ((int64_t)sb * s.NV + v) * s.H * s.W * 2;
-    const int ddx = safe_idx(__builtin_rintf(clipf(unnorm(u, (float)s.W / 2.0f), (float)(s.W - 1))), s.W);
-    const int ddy = safe_idx(__builtin_rintf(clipf(unnorm(w, (float)s.H / 2.0f), (float)(s.H - 1))), s.H);
-    const float delta = tex[((int64_t)ddy * s.W + ddx) * 2].w - pz;                    // :199-200
-    const int F = s.num_freqs, e_pe3 = 3 + 6 * F, e_dir = e_pe3 + 3, e_pe1 = e_dir + 1;
-    const float half_pi = 1.5707963267948966f;
-    for (int e = lane; e < ld_in; e += 64) {               // point_inputs_gen_kernel's columns and expressions
-        float val;
-        if (e < 3) val = e == 0 ? px : e == 1 ? py : pz;
-        else if (e < e_pe3) { const int j = (e - 3) / 3, i = (e - 3) % 3;    // positional_encoding.py:45-49
-            val = sinf(__builtin_fmaf(i == 0 ? px : i == 1 ? py : pz, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else if (e < e_dir) val = e == e_pe3 ? dcx : e == e_pe3 + 1 ? dcy : dcz;
-        else if (e == e_dir) val = delta;
-        else if (e < e_pe1 + 2 * F) { const int j = e - e_pe1;
-            val = sinf(__builtin_fmaf(delta, ldexpf(s.freq_factor, j >> 1), (j & 1) ? half_pi : 0.0f)); }
-        else val = 0.0f;
-        in[row * ld_in + e] = val;
-    }
+    float px, py, pz, u, w, dcx, dcy, dcz, delta;
+    view_geometry(s, sb, v, wx, wy, wz, dwx, dwy, dwz, px, py, pz, u, w, dcx, dcy, dcz, delta);   // :160-161, :172-180, :199-200
+    for (int e = lane; e < ld_in; e += 64) in[row * ld_in + e] = input_element(e, px, py, pz, dcx, dcy, dcz, delta, s.num_freqs, s.freq_factor);
     if (!zlat) return;   // combine_layer 0: no lin_z, neither latent is read (wave-uniform)
 
     // the encoder's footprint (image_encoder.py:97-127) and the general one (novel_pixelnerf.py:163-165, :183-186, index() :126-137):
     // the scene's feature_padding scaled by each map's own size, one lookup mode for both
-    const float sxl = ((float)s.w - s.feature_padding * 2.0f) / (float)s.w, syl = ((float)s.h - s.feature_padding * 2.0f) / (float)s.h;
-    const LatentFoot f = latent_footprint<true>(u, w, sxl, syl, s.w, s.h, ix_interp, ix_padding);
+    const LatentFoot f = latent_footprint<true>(u, w, pad_scale(s.w, s.feature_padding), pad_scale(s.h, s.feature_padding), s.w, s.h,
+                                                ix_interp, ix_padding);
     const int o[4] = {f.y0 * s.w + f.x0, f.y0 * s.w + f.x1, f.y1 * s.w + f.x0, f.y1 * s.w + f.x1};
     const float wt[4] = {f.nw, f.ne, f.sw, f.se};
-    const float *gx = xyz_gen + ((int64_t)sb * P + p) * 3;
-    View gv;
-    const float *Pm = n.gposes + (int64_t)sb * 16;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        gv.r[i * 3 + 0] = Pm[i * 4 + 0]; gv.r[i * 3 + 1] = Pm[i * 4 + 1]; gv.r[i * 3 + 2] = Pm[i * 4 + 2];
-        gv.t[i] = Pm[i * 4 + 3];
-    }
-    gv.fx = n.gfocal[sb * 2]; gv.fy = n.gfocal[sb * 2 + 1]; gv.cx = n.gc[sb * 2]; gv.cy = n.gc[sb * 2 + 1];
-    float gpx, gpy, gpz, gu, gw;
-    project(gv, n.giw, n.gih, gx[0], gx[1], gx[2], gpx, gpy, gpz, gu, gw);
-    const float sxg = ((float)n.gw - s.feature_padding * 2.0f) / (float)n.gw, syg = ((float)n.gh - s.feature_padding * 2.0f) / (float)n.gh;
-    const LatentFoot fg = latent_footprint<true>(gu, gw, sxg, syg, n.gw, n.gh, ix_interp, ix_padding);
+    const LatentFoot fg = camera_footprint(view_of(n.gposes, n.gfocal, n.gc, sb), n.giw, n.gih, xyz_gen + ((int64_t)sb * P + p) * 3, n.gh,
+                                           n.gw, s.feature_padding, ix_interp, ix_padding);
     const int og[4] = {fg.y0 * n.gw + fg.x0, fg.y0 * n.gw + fg.x1, fg.y1 * n.gw + fg.x0, fg.y1 * n.gw + fg.x1};
     const float wg[4] = {fg.nw, fg.ne, fg.sw, fg.se};
     if (lane == 0) {
@@ -101,9 +71,7 @@ __global__ __launch_bounds__(64) void point_inputs_novel_kernel(DinerScene s, co
         float t[4], g[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { t[i] = lat[(int64_t)o[i] * s.C + ch]; g[i] = n.glat[(int64_t)og[i] * s.C + ch]; }
-        const float zl = __builtin_fmaf(t[3], wt[3], __builtin_fmaf(t[2], wt[2], __builtin_fmaf(t[1], wt[1], t[0] * wt[0])));
-        const float zg = __builtin_fmaf(g[3], wg[3], __builtin_fmaf(g[2], wg[2], __builtin_fmaf(g[1], wg[1], g[0] * wg[0])));
-        zlat[row * s.C + ch] = zg + zl;                                                 // novel_pixelnerf.py:196
+        zlat[row * s.C + ch] = tap_sum(g[0], g[1], g[2], g[3], fg) + tap_sum(t[0], t[1], t[2], t[3], f);   // novel_pixelnerf.py:196
     }
 }
 
