@@ -57,6 +57,32 @@ class MlpShape(NamedTuple):
 STANDARD_SHAPE = MlpShape(55, 512, 512, 5, 3, 6, 0.0)
 
 
+class _Route(NamedTuple):
+    """What one inference call runs, settled once per call from (model, f16_ok) by ``NeRFRendererDGS._resolve``."""
+    shape: MlpShape
+    gen: bool                      # a shape-general kernel (the *_gen entry points), else the 512-wide ones
+    f16: bool                      # ... its split-fp16 form
+    lookup: object                 # the latent lookup: None (bilinear / border), a DinerLatentIndex, or the int padding of a bicubic one
+    effective_precision: str
+    stem: str                      # last_route, short of the "_lz" of a call that read lin_z maps
+
+    @property
+    def op_ok(self) -> bool:
+        """the torch_ops binding serves this route (the standard model with the default lookup)"""
+        return not self.gen and self.lookup is None
+
+
+class _Keep(NamedTuple):
+    """The tensors a ``DinerScene`` points into (``NeRFRendererDGS._scene``); unused ones are None."""
+    maps: torch.Tensor
+    poses: torch.Tensor
+    focal: torch.Tensor
+    c: torch.Tensor
+    latent: Optional[torch.Tensor]
+    linz: Optional[torch.Tensor]
+    linz_gen: Optional[torch.Tensor] = None    # the lin_z maps of a shape-general route
+
+
 class RenderOutput(dict):
     """Attribute dict standing in for ``dotmap.DotMap`` (reference nerf_renderer.py:421-430)."""
 
@@ -317,7 +343,7 @@ class NeRFRendererDGS(torch.nn.Module):
     @staticmethod
     def _validate_shape(model) -> MlpShape:
         """_validate_model without the latent lookup's check"""
-        enc, mlp = model.encoder, model.mlp_fine
+        mlp = model.mlp_fine
         if getattr(mlp, "combine_type", "average") != "average":
             raise NotImplementedError(f"only combine_type='average' (resnetfc.py:9-14), not {mlp.combine_type!r}")
         act = getattr(mlp, "activation", torch.nn.ReLU())
@@ -333,11 +359,12 @@ class NeRFRendererDGS(torch.nn.Module):
                 raise NotImplementedError("every ResnetBlockFC must use the ResnetFC's activation (resnetfc.py:49-52, 117-119)")
         if mlp.d_out != 4:
             raise NotImplementedError(f"fusion MLP d_out={mlp.d_out} unsupported (PixelNeRF's head is rgb + sigma: 4)")
-        for pe in (model.poscode, model.depthcode):
+        poscode, depthcode = model.poscode, model.depthcode
+        for pe in (poscode, depthcode):
             if not pe.include_input:
                 raise NotImplementedError("positional encoding must have include_input=True")
-        F = int(model.poscode.num_freqs)
-        if int(model.depthcode.num_freqs) != F or float(model.depthcode.freqs[0]) != float(model.poscode.freqs[0]):
+        F = int(poscode.num_freqs)
+        if int(depthcode.num_freqs) != F or float(depthcode.freqs[0]) != float(poscode.freqs[0]):
             raise NotImplementedError("poscode and depthcode must share num_freqs and freq_factor (pixelnerf.py:14-15)")
         shape = MlpShape(int(mlp.d_in), int(mlp.d_latent), int(mlp.d_hidden), int(mlp.n_blocks), int(mlp.combine_layer), F, beta)
         if shape.standard:
@@ -366,8 +393,9 @@ class NeRFRendererDGS(torch.nn.Module):
         default bilinear / border (the entry points and torch ops without _ix), else the DinerLatentIndex of the _ix entry points.
         Raises ``NotImplementedError`` for a mode these entry points do not serve; bicubic is one: it has entry points of its own,
         behind the renderer's ``bicubic_index`` switch (``_validate``)."""
-        interp = getattr(model.encoder, "index_interp", "bilinear")
-        padding = getattr(model.encoder, "index_padding", "border")
+        enc = model.encoder              # (one attribute lookup on the module: this runs several times per call)
+        interp = getattr(enc, "index_interp", "bilinear")
+        padding = getattr(enc, "index_padding", "border")
         if interp not in _lib.INDEX_INTERP or padding not in _lib.INDEX_PADDING:
             raise NotImplementedError(f"latent lookup index_interp={interp!r}, index_padding={padding!r} unsupported: index_interp in "
                                       f"{sorted(_lib.INDEX_INTERP)}, index_padding in {sorted(_lib.INDEX_PADDING)} (image_encoder.py:24-25); "
@@ -399,17 +427,27 @@ class NeRFRendererDGS(torch.nn.Module):
         """``model`` has no 512-wide kernel: another shape than the standard one, or the bicubic lookup"""
         return not shape.standard or self._bicubic_pad(model) is not None
 
-    def _route(self, model, f16_ok=True) -> MlpShape:
-        """validate ``model``; for a shape that takes a shape-general kernel, settle the precision (fp32 is what runs, unless
-        f16x3_any_shape sends this inference call -- ``f16_ok`` -- to the split-fp16 kernel)"""
+    def _resolve(self, model, f16_ok=True, stacklevel=4) -> _Route:
+        """validate ``model`` and settle what an inference call on it runs (``_Route``): the kernel family, the precision (a shape-general
+        route is exact fp32, said once, unless f16x3_any_shape sends this call -- ``f16_ok`` -- to the split-fp16 kernel) and the latent
+        lookup.  Every predicate is asked through ``self``, once.  ``stacklevel``: the precision warning's, as ``_settle_fp32`` takes it
+        (4: the line that called this method's caller, i.e. the user's line behind a public door)"""
         shape = self._validate(model)
-        if f16_ok and self._use_gen_f16(shape, model):
-            self.effective_precision = "f16x3"
-        elif self._use_gen(shape, model):
-            self._settle_fp32(shape, stacklevel=4)
-        else:
-            self.effective_precision = self.precision
-        return shape
+        pad = self._bicubic_pad(model)
+        lookup = int(pad) if pad is not None else self._latent_index(model)
+        gen = self._use_gen(shape, model)
+        f16 = bool(gen and f16_ok and self._use_gen_f16(shape, model))
+        if gen and not f16:
+            self._settle_fp32(shape, stacklevel=stacklevel)
+        prec = "f16x3" if f16 else "fp32" if gen else self.precision
+        stem = self._gen_route(f16, None) if gen else "points_mlp_f16" if prec == "f16x3" else "points_mlp"
+        return _Route(shape, gen, f16, lookup, prec, stem)
+
+    def _route(self, model, f16_ok=True) -> MlpShape:
+        """``_resolve`` for the callers that want the shape alone: ``effective_precision`` is set, the shape returned"""
+        route = self._resolve(model, f16_ok, stacklevel=5)
+        self.effective_precision = route.effective_precision
+        return route.shape
 
     def _settle_fp32(self, shape: MlpShape, stacklevel=3):
         """the shape-general paths run in exact fp32: say so once when another precision was asked for"""
@@ -431,37 +469,56 @@ class NeRFRendererDGS(torch.nn.Module):
         full = "diner_" + (name.replace("_gen", "_gen_f16") if f16 else name)
         return getattr(_lib.lib(), full), full
 
-    def _gen_lookup(self, name: str, f16: bool, model):
-        """the entry point of ``_gen_entry`` for ``model``'s latent lookup and the arguments that follow the scene in its list:
-        ``diner_<name>`` (bilinear / border), ``.._ix`` + the DinerLatentIndex, or ``.._bc`` + the padding (bicubic)"""
-        pad = self._bicubic_pad(model)
-        if pad is not None:
-            return (*self._gen_entry(name + "_bc", f16), (int(pad),))
-        ix = self._latent_index(model)
-        if ix is not None:
-            return (*self._gen_entry(name + "_ix", f16), (C.byref(ix),))
-        return (*self._gen_entry(name, f16), ())
+    def _entry(self, route: _Route, stem: str, lz, sc: DinerScene, packed, a: tuple, b: tuple, scratch=None):
+        """The C entry point of ``stem`` ("render_points", "render" or "render_image") on ``route`` -> (function, its name for check(),
+        its argument list).  ``a`` and ``b`` are the stem's own arguments; what depends on the route goes around them:
 
-    def _gen_call(self, name: str, f16: bool, model, lz):
-        """``_gen_lookup`` and the arguments that end the list: with the lin_z maps ``lz`` the one entry point ``diner_<name>_lz`` of both
-        precisions and every lookup (DinerLatentIndex pointer or NULL after the scene; precision, bicubic padding or -1, maps at the end)"""
-        if lz is None:
-            return (*self._gen_lookup(name, f16, model), ())
+            standard                  diner_<stem>[_ix]                 (sc, [&index,] packed, *a, precision, [scratch,] *b)
+            shape-general             diner_<stem>_gen[_f16][_ix|_bc]   (sc, [&index | padding,] &shape, packed, *a, *b)
+            ... with lin_z maps lz    diner_<stem>_gen_lz               (sc, &index | NULL, &shape, packed, *a, *b, precision, padding | -1, lz)
+
+        (``scratch`` is the point stage's, of the standard kernels only.)"""
+        look = route.lookup
+        bicubic = isinstance(look, int)
+        prec = _lib.PRECISIONS[route.effective_precision]
+        if not route.gen:
+            full = "diner_" + stem + ("_ix" if look is not None else "")
+            head = () if look is None else (C.byref(look),)
+            mid, tail = ((prec, _ptr(scratch)) if stem == "render_points" else (prec,)), ()
+        else:
+            if lz is not None:    # one entry point for both precisions and every lookup
+                full = "diner_" + stem + "_gen_lz"
+                head = (None if bicubic or look is None else C.byref(look),)
+                tail = (prec, look if bicubic else -1, _ptr(lz))
+            else:
+                full = "diner_" + stem + ("_gen_f16" if route.f16 else "_gen") + ("" if look is None else "_bc" if bicubic else "_ix")
+                head = () if look is None else (look if bicubic else C.byref(look),)
+                tail = ()
+            head, mid = (*head, C.byref(route.shape.c_struct())), ()
+        return getattr(_lib.lib(), full), full, (C.byref(sc), *head, _ptr(packed), *a, *mid, *b, *tail)
+
+    def _gen_lookup(self, name: str, f16: bool, model):
+        """a view of ``_entry`` kept for the host tests that predate it: the shape-general entry point ``diner_<name>`` (``name`` ends
+        in "_gen") for ``model``'s lookup -> (function, its name, the arguments between the scene and the shape)"""
         pad = self._bicubic_pad(model)
-        ix = None if pad is not None else self._latent_index(model)
-        full = "diner_" + name + "_lz"
-        return (getattr(_lib.lib(), full), full, (C.byref(ix) if ix is not None else None,),
-                (_lib.PRECISIONS["f16x3" if f16 else "fp32"], -1 if pad is None else int(pad), _ptr(lz)))
+        route = _Route(STANDARD_SHAPE, True, f16, int(pad) if pad is not None else self._latent_index(model), "fp32", "")
+        fn, full, args = self._entry(route, name[:-len("_gen")], None, DinerScene(), None, (), ())
+        return fn, full, args[1:-2]
 
     @staticmethod
     def _gen_route(f16: bool, lz) -> str:
         return ("points_mlp_gen_f16" if f16 else "points_mlp_gen") + ("_lz" if lz is not None else "")
 
+    def _linz_gen_wanted(self, shape: MlpShape) -> bool:
+        """this call reads lin_z maps of a shape-general route, if they fit: the switch is on, grad mode is off (even when nothing
+        requires grad) and the shape has a lin_z layer"""
+        return bool(self.linz_maps_any_shape) and not torch.is_grad_enabled() and min(shape.combine_layer, shape.n_blocks) > 0
+
     def _linz_maps_gen(self, shape: MlpShape, sc: DinerScene, latent: torch.Tensor) -> Optional[torch.Tensor]:
         """the lin_z maps of a shape-general inference route (``linz_maps_any_shape``): a single cached entry, rebuilt when the latent
         pack or an MLP pack was rebuilt; None (the route without maps) when the switch is off, grad mode is involved, the shape has no
         lin_z layer or the maps exceed ``linz_maps_max_bytes``"""
-        if not self.linz_maps_any_shape or torch.is_grad_enabled() or min(shape.combine_layer, shape.n_blocks) == 0:
+        if not self._linz_gen_wanted(shape):
             return None
         cs = shape.c_struct()
         n = int(_lib.lib().diner_linz_maps_gen_floats(C.byref(sc), C.byref(cs)))
@@ -493,9 +550,9 @@ class NeRFRendererDGS(torch.nn.Module):
                                   "torch.no_grad() or with parameters that do not require grad, or construct the renderer with "
                                   "train_any_shape=True (renderer.train_any_shape: the shape-general fp32 training path)")
 
-    def _scene(self, model, need_latent=True, packed_mlp=None, gen_shape: Optional[MlpShape] = None) -> Tuple[DinerScene, tuple]:
-        """``gen_shape``: the call is a shape-general inference route's (its fp32 MLP image is packed): the tuple then ends with that
-        route's lin_z maps, or None (``_linz_maps_gen``)"""
+    def _scene(self, model, need_latent=True, packed_mlp=None, gen_shape: Optional[MlpShape] = None) -> Tuple[DinerScene, _Keep]:
+        """``gen_shape``: the call is a shape-general inference route's (its fp32 MLP image is packed): ``linz_gen`` of the tensors
+        returned is then that route's lin_z maps, or None (``_linz_maps_gen``)"""
         enc = model.encoder
         dev = enc.depths.device
         msrc = [model.poses, model.focal, model.c, model.image_shape, enc.depths, enc.depths_std, enc.normals]
@@ -566,9 +623,7 @@ class NeRFRendererDGS(torch.nn.Module):
         sc.maps = maps.data_ptr()
         sc.latent = latent.data_ptr() if latent is not None else None
         sc.linz_maps = linz.data_ptr() if linz is not None else None
-        if gen_shape is not None:
-            return sc, (maps, poses, focal, c, latent, linz, self._linz_maps_gen(gen_shape, sc, latent))
-        return sc, (maps, poses, focal, c, latent, linz)
+        return sc, _Keep(maps, poses, focal, c, latent, linz, None if gen_shape is None else self._linz_maps_gen(gen_shape, sc, latent))
 
     def memory_report(self, model=None, rays_per_call=None, n_views=None):
         """Bytes of device memory this renderer holds / will take, so that the appetite is a number and not a surprise:
@@ -630,7 +685,7 @@ class NeRFRendererDGS(torch.nn.Module):
     def _gen_packs(self, model, shape: MlpShape, f16: bool) -> Tuple[torch.Tensor, Optional[MlpShape]]:
         """the packed MLP image of a shape-general inference call and the ``gen_shape`` argument of its ``_scene``: with
         ``linz_maps_any_shape`` (outside grad mode, a shape with lin_z layers) the fp32 image is packed as well, for the map builder"""
-        lz = self.linz_maps_any_shape and not torch.is_grad_enabled() and min(shape.combine_layer, shape.n_blocks) > 0
+        lz = self._linz_gen_wanted(shape)
         if lz and f16:
             self._mlp_shape_general(model, shape, False)
         return self._mlp_shape_general(model, shape, f16), (shape if lz else None)
@@ -749,12 +804,10 @@ class NeRFRendererDGS(torch.nn.Module):
         assert SB == sc.SB
         cfg = self._cfg(K, NC, G, depth_diff_max)
         dev = r.device
-        u_c = n_g = u_f = None
-        if noise is not None:
-            u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
-            if u_c is not None: assert u_c.numel() == SB * NR * NC
-            if n_g is not None: assert n_g.numel() == SB * NR * G
-            if u_f is not None: assert u_f.numel() == SB * NR * K
+        u_c, n_g, u_f = self._noise(noise, dev)
+        if u_c is not None: assert u_c.numel() == SB * NR * NC
+        if n_g is not None: assert n_g.numel() == SB * NR * G
+        if u_f is not None: assert u_f.numel() == SB * NR * K
         zc = None if z_cand is None else _f32c(z_cand).to(dev)
         z = torch.empty((SB, NR, K), dtype=torch.float32, device=dev)
         z_dg = torch.empty_like(z) if want_dg else None
@@ -784,36 +837,47 @@ class NeRFRendererDGS(torch.nn.Module):
         r = self._check_rays(rays)
         z = _f32c(z_samp)
         SB, NR, K = z.shape
-        shape = self._route(model)
-        if self._use_gen(shape, model):
-            f16 = self._use_gen_f16(shape, model)
-            packed, gshape = self._gen_packs(model, shape, f16)
-            sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
-            lz = _keep[6] if gshape is not None else None
-            assert SB == sc.SB
-            out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
-            cs = shape.c_struct()
-            fn, name, look, tail = self._gen_call("render_points_gen", f16, model, lz)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(out), _stream(r.device), *tail), name)
-            self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
-            return out
-        packed = self._mlp(model)
-        sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
+        route = self._resolve(model)
+        packed, sc, _keep, lz = self._prepare(model, route)
         assert SB == sc.SB  # pixelnerf.py:68
         out = torch.empty((SB, NR, K, 4), dtype=torch.float32, device=r.device)
-        prec = _lib.PRECISIONS[self.precision]
-        n_scr = int(_lib.lib().diner_render_points_scratch_floats(SB, sc.NV, prec))
+        # (the standard kernels' scratch; a shape-general one takes none)
+        n_scr = 0 if route.gen else int(_lib.lib().diner_render_points_scratch_floats(SB, sc.NV, _lib.PRECISIONS[route.effective_precision]))
         scr = torch.empty(n_scr, dtype=torch.float32, device=r.device) if n_scr else None
-        ix = self._latent_index(model)
-        if ix is None:
-            check(_lib.lib().diner_render_points(C.byref(sc), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
-                                                 _ptr(out), _stream(r.device)),
-                  "diner_render_points")
-        else:
-            check(_lib.lib().diner_render_points_ix(C.byref(sc), C.byref(ix), _ptr(packed), _ptr(r), _ptr(z), NR, K, prec, _ptr(scr),
-                                                    _ptr(out), _stream(r.device)), "diner_render_points_ix")
-        self.last_route, self.last_binding = ("points_mlp_f16" if self.precision == "f16x3" else "points_mlp"), "ctypes"
+        self._points(route, lz, sc, packed, r, z, NR, K, scr, out, _stream(r.device))
+        self._ran(route, lz, "ctypes")
         return out
+
+    def _prepare(self, model, route: _Route, saved=False):
+        """The device state of a call on ``route`` -> (packed MLP image, DinerScene, the tensors it points into, the route's lin_z maps
+        or None).  ``saved``: the forward of an autograd frame (render_image), which is the training path's: no maps."""
+        if not route.gen:
+            packed = self._mlp(model)
+            sc, keep = self._scene(model, need_latent=True, packed_mlp=packed)
+        elif saved:
+            packed = self._mlp_shape_general(model, route.shape, route.f16)
+            sc, keep = self._scene(model, need_latent=True)
+        else:
+            packed, gshape = self._gen_packs(model, route.shape, route.f16)
+            sc, keep = self._scene(model, need_latent=True, gen_shape=gshape)
+        return packed, sc, keep, keep.linz_gen
+
+    def _points(self, route: _Route, lz, sc, packed, r, z, NR, K, scratch, out, st):
+        """the point stage: rgb-sigma ``out`` [SB*NR*K*4] of the samples ``z`` (render_points(), and the staged form of _launch)"""
+        fn, name, args = self._entry(route, "render_points", lz, sc, packed, (_ptr(r), _ptr(z), NR, K), (_ptr(out), st), scratch)
+        check(fn(*args), name)
+
+    def _ran(self, route: _Route, lz, binding: str):
+        """what an inference call leaves behind for its caller to read"""
+        self.last_route, self.last_binding = route.stem + ("_lz" if lz is not None else ""), binding
+        self.effective_precision = route.effective_precision
+
+    @staticmethod
+    def _noise(noise, dev):
+        """(u_coarse, n_gauss, u_fill) of a replayed-noise argument, each fp32 on ``dev`` or None"""
+        if noise is None:
+            return None, None, None
+        return [None if t is None else _f32c(t).to(dev) for t in noise]
 
     def composite(self, model, rays, z_samp, *, rgbsigma=None, _sync=False):
         """Alpha compositing (reference nerf_renderer.py:286-365) -> (weights, rgb, depth)."""
@@ -871,128 +935,99 @@ class NeRFRendererDGS(torch.nn.Module):
         :return: ``out.fine.rgb`` [SB,B,3], ``out.fine.depth`` [SB,B], ``out.fine.weights`` iff requested
         """
         assert len(rays.shape) == 3
-        shape = self._validate(model)
         if self._wants_grad(model, rays):
+            shape = self._validate(model)
             if self._use_gen_train(shape, model):
                 return self._forward_train_gen(model, rays, want_weights, shape, noise=noise, z_samples=z_samples)
             if self._needs_gen(shape, model):
                 self._gen_training_unsupported(shape, model)
             return self._forward_train(model, rays, want_weights, noise=noise, z_samples=z_samples)
-        if z_samples is None and self._use_gen(shape, model):
-            return self._forward_gen(model, rays, want_weights, shape, noise)
+        route = self._resolve(model) if z_samples is None else None     # (injected samples: composite() -> render_points() resolves)
         with torch.no_grad():
             r = self._check_rays(rays)
-            SB, NR, _ = r.shape
-            K = int(self.n_samples)
-            dev = r.device
-            big = want_weights or SB * NR > int(self.finite_sync_rays)   # examined before this call returns (see __init__)
+            big = want_weights or r.shape[0] * r.shape[1] > int(self.finite_sync_rays)   # examined before this call returns (see __init__)
             if z_samples is not None:
-                w_, rgb, depth = self.composite(model, r, z_samples, _sync=big)
-                weights = w_ if want_weights else None
+                weights, rgb, depth = self.composite(model, r, z_samples, _sync=big)
             else:
-                packed = self._mlp(model)
-                sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
-                assert SB == sc.SB
-                cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
-                u_c = n_g = u_f = None
-                if noise is not None:
-                    u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
-                prec = _lib.PRECISIONS[self.precision]
-                L, st, seed = _lib.lib(), _stream(dev), self._next_seed()
-                self._poll_status()
-                status = _ptr(self._status_word(dev))
-                ix = self._latent_index(model)   # another lookup mode than bilinear / border: the _ix entry points, through ctypes
-                use_ops = self.stage_events is None and noise is None and self.binding == "torch_ops" and ix is None
-                if not use_ops:    # (the op allocates its own workspace and outputs: never both sets at once)
-                    ws = torch.empty(int(L.diner_render_workspace_floats(SB, NR, K, sc.NV, prec)), dtype=torch.float32, device=dev)
-                    rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
-                    depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
-                    weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
-                if use_ops:
-                    from . import ops as _ops
-                    maps_t, poses_t, focal_t, c_t, latent_t, linz_t = _keep
-                    rgb, depth, w_ = _ops.load().render(maps_t, poses_t, focal_t, c_t, latent_t, linz_t, packed, r, sc.image_w, sc.image_h,
-                                                        sc.feature_padding, sc.num_freqs, sc.freq_factor, cfg.n_candidates, cfg.n_samples,
-                                                        cfg.n_gaussian, cfg.depth_diff_max, bool(self.white_bkgd), prec, seed - (1 << 64) if seed >= (1 << 63) else seed,
-                                                        bool(want_weights), self._status_word(dev))
-                    weights = w_ if want_weights else None
-                elif self.stage_events is None and ix is None:
-                    check(L.diner_render(C.byref(sc), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                                         prec, _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth),
-                                         _ptr(weights), status, st), "diner_render")
-                elif self.stage_events is None:
-                    check(L.diner_render_ix(C.byref(sc), C.byref(ix), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                                            prec, _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth),
-                                            _ptr(weights), status, st), "diner_render_ix")
-                else:
-                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-                    z, c, scr = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5], ws[SB * NR * K * 5:]
-                    ev[0].record()
-                    check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
-                                                     None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
-                    ev[1].record()
-                    check(L.diner_render_points_ix(C.byref(sc), C.byref(ix) if ix is not None else None, _ptr(packed), _ptr(r), _ptr(z),
-                                                   NR, K, prec, _ptr(scr) if scr.numel() else None, _ptr(c), st),
-                          "diner_render_points_ix")
-                    ev[2].record()
-                    check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
-                                            _ptr(depth), _ptr(weights), status, st), "diner_composite")
-                    ev[3].record()
-                    self.stage_events.append(ev)
-                self._after_launch(dev, sync=big)
-                self.effective_precision = self.precision
-                self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
-                self.last_binding = "torch_ops" if use_ops else "ctypes"
+                rgb, depth, weights = self._launch(model, route, rays=r, want_weights=want_weights, noise=noise, sync=big)
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
-    @torch.no_grad()
-    def _forward_gen(self, model, rays, want_weights, shape: MlpShape, noise):
-        """forward() for a non-standard model: diner_render_gen (sampler -> shape-general point kernel -> compositing), or the three
-        stage entry points when stage_events is a list"""
-        self._route(model)
-        r = self._check_rays(rays)
-        SB, NR, _ = r.shape
-        K = int(self.n_samples)
-        dev = r.device
-        big = want_weights or SB * NR > int(self.finite_sync_rays)
-        f16 = self._use_gen_f16(shape, model)
-        packed, gshape = self._gen_packs(model, shape, f16)
-        sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
-        lz = _keep[6] if gshape is not None else None
-        assert SB == sc.SB
-        cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
-        cs = shape.c_struct()
-        u_c = n_g = u_f = None
-        if noise is not None:
-            u_c, n_g, u_f = [None if t is None else _f32c(t).to(dev) for t in noise]
-        L, st, seed = _lib.lib(), _stream(dev), self._next_seed()
-        self._poll_status()
-        status = _ptr(self._status_word(dev))
-        ws = torch.empty(int(L.diner_render_workspace_floats(SB, NR, K, sc.NV, _lib.PRECISIONS["fp32"])), dtype=torch.float32, device=dev)
-        rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
-        depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
-        weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
-        if self.stage_events is None:
-            fn, name, look, tail = self._gen_call("render_gen", f16, model, lz)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), NR, C.byref(cfg), int(bool(self.white_bkgd)),
-                     _ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), _ptr(rgb), _ptr(depth), _ptr(weights), status, st, *tail), name)
+    def _launch(self, model, route: _Route, *, rays=None, cam=None, want_weights=False, noise=None, saved=None, sync=False):
+        """The whole path -- sampler, point stage, compositing -- of one inference call on ``route``, under no_grad: of ``rays`` [SB,NR,8]
+        (forward()), or of the target cameras ``cam`` = (extrinsics, intrinsics, z_near, z_far, H, W), whose rays the sampler generates
+        (render_image: NR = H * W) -> (rgb [SB,NR,3], depth [SB,NR], weights [SB,NR,K] or None).
+        The torch_ops binding takes the call where it serves it: ``route.op_ok``, ``binding``, and none of the build-only extras
+        (replayed ``noise``, ``saved``, forward()'s ``stage_events``).  Else ctypes: the route's entry point, or under ``stage_events``
+        the three stage entry points that it runs internally, bracketed by four events.
+        ``saved`` (a dict; render_image under autograd) receives the generated rays, the samples the compositing used (workspace
+        layout rays | z | ..., here z only: the rays go to their own tensor) and the flat rgb / depth.
+        ``sync``: examine the frame before returning (``_after_launch``)."""
+        image = rays is None
+        if image:
+            E, Ki, zn, zf, H, W = cam
+            dev, SB, NR = E.device, E.shape[0], H * W
         else:
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            z, c = ws[:SB * NR * K], ws[SB * NR * K:SB * NR * K * 5]
-            ev[0].record()
-            check(L.diner_sample_depthguided(C.byref(sc), _ptr(r), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
-                                             None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
-            ev[1].record()
-            fn, name, look, tail = self._gen_call("render_points_gen", f16, model, lz)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), _ptr(r), _ptr(z), NR, K, _ptr(c), st, *tail), name)
-            ev[2].record()
-            check(L.diner_composite(_ptr(r), _ptr(z), _ptr(c), SB * NR, K, int(bool(self.white_bkgd)), _ptr(rgb),
-                                    _ptr(depth), _ptr(weights), status, st), "diner_composite")
-            ev[3].record()
-            self.stage_events.append(ev)
-        self._after_launch(dev, sync=big)
-        self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
-        return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
+            dev, (SB, NR, _) = rays.device, rays.shape
+        packed, sc, keep, lz = self._prepare(model, route, saved is not None)
+        assert SB == sc.SB
+        K = int(self.n_samples)
+        cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
+        white = int(bool(self.white_bkgd))
+        staged = not image and self.stage_events is not None
+        use_ops = route.op_ok and self.binding == "torch_ops" and noise is None and saved is None and not staged
+        seed = self._next_seed()
+        self._poll_status()
+        status = self._status_word(dev)
+        if use_ops:    # (the op allocates its own workspace and outputs: never both sets at once)
+            from . import ops as _ops
+            out = getattr(_ops.load(), "render_image" if image else "render")(
+                *keep[:6], packed, *((E, Ki, zn, zf, H, W) if image else (rays,)), sc.image_w, sc.image_h, sc.feature_padding, sc.num_freqs,
+                sc.freq_factor, cfg.n_candidates, cfg.n_samples, cfg.n_gaussian, cfg.depth_diff_max, bool(self.white_bkgd),
+                _lib.PRECISIONS[route.effective_precision], seed - (1 << 64) if seed >= (1 << 63) else seed,
+                *(() if image else (bool(want_weights),)), status)
+            rgb, depth, weights = out[0], out[1], (out[2] if want_weights else None)
+        else:
+            L, st = _lib.lib(), _stream(dev)
+            # workspace: by precision for the standard kernels (the point stage's scratch); a shape-general route takes the fp32 size
+            wprec = _lib.PRECISIONS["fp32" if route.gen else route.effective_precision]
+            n_ws = (L.diner_render_image_workspace_floats(SB, H, W, K, sc.NV, wprec) if image else
+                    L.diner_render_workspace_floats(SB, NR, K, sc.NV, wprec))
+            ws = torch.empty(int(n_ws), dtype=torch.float32, device=dev)
+            rgb = torch.empty((SB, NR, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((SB, NR), dtype=torch.float32, device=dev)
+            weights = torch.empty((SB, NR, K), dtype=torch.float32, device=dev) if want_weights else None
+            outs = (_ptr(rgb), _ptr(depth), _ptr(weights), _ptr(status), st)
+            if image:
+                tc = _lib.DinerTargetCam()
+                tc.extrinsics, tc.intrinsics, tc.z_near, tc.z_far = E.data_ptr(), Ki.data_ptr(), zn.data_ptr(), zf.data_ptr()
+                tc.H, tc.W = H, W
+                rays_out = None if saved is None else torch.empty((SB, NR, 8), dtype=torch.float32, device=dev)
+                stem, a, b = "render_image", (C.byref(tc), C.byref(cfg), white), (seed, _ptr(ws), _ptr(rays_out), *outs)
+            else:
+                u_c, n_g, u_f = self._noise(noise, dev)
+                stem, a, b = "render", (_ptr(rays), NR, C.byref(cfg), white), (_ptr(u_c), _ptr(n_g), _ptr(u_f), seed, _ptr(ws), *outs)
+            if not staged:
+                fn, name, args = self._entry(route, stem, lz, sc, packed, a, b)
+                check(fn(*args), name)
+            else:
+                n = SB * NR * K
+                z, c, scr = ws[:n], ws[n:5 * n], ws[5 * n:]
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                ev[0].record()
+                check(L.diner_sample_depthguided(C.byref(sc), _ptr(rays), NR, C.byref(cfg), _ptr(u_c), _ptr(n_g), _ptr(u_f),
+                                                 None, seed, _ptr(z), None, None, st), "diner_sample_depthguided")
+                ev[1].record()
+                self._points(route, lz, sc, packed, rays, z, NR, K, scr if scr.numel() else None, c, st)
+                ev[2].record()
+                check(L.diner_composite(_ptr(rays), _ptr(z), _ptr(c), SB * NR, K, white, *outs), "diner_composite")
+                ev[3].record()
+                self.stage_events.append(ev)
+            if saved is not None:
+                n = SB * NR
+                saved.update(rays=rays_out, z=ws[n * 8:n * (8 + K)].view(SB, NR, K).clone(), rgb=rgb, depth=depth)
+        self._ran(route, lz, "torch_ops" if use_ops else "ctypes")
+        self._after_launch(dev, sync=sync)
+        return rgb, depth, weights
 
     def render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False, bounds=None,
                      box_offset=(-0.01, 0.01), return_mask=False):
@@ -1065,104 +1100,47 @@ class NeRFRendererDGS(torch.nn.Module):
             return rgb, depth.view(SB, H, W, 1).permute(0, 3, 1, 2)
         return rgb
 
-    @torch.no_grad()
     def _render_image(self, model, target_extrinsics, target_intrinsics, H, W, z_near, z_far, return_depth=False, saved=None):
-        """render_image's inference launch.  ``saved`` (a dict): take the ctypes binding (the torch op gives no access to its workspace)
-        and hand out the generated rays [SB,H*W,8], the samples the compositing used [SB,H*W,K] (workspace layout rays | z | ..., here
-        z only: the rays go to rays_out) and the flat rgb [SB,H*W,3] / depth [SB,H*W]."""
-        shape = self._route(model, f16_ok=saved is None)   # under autograd (``saved``) the frame is the training path's: exact fp32
-        gen = self._use_gen(shape, model)
-        f16 = saved is None and self._use_gen_f16(shape, model)
-        dev = target_extrinsics.device
-        SB = target_extrinsics.shape[0]
-        E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
-        zn = torch.as_tensor(z_near, dtype=torch.float32, device=dev).expand(SB).contiguous()
-        zf = torch.as_tensor(z_far, dtype=torch.float32, device=dev).expand(SB).contiguous()
-        lz = None
-        if gen and saved is None:
-            packed, gshape = self._gen_packs(model, shape, f16)
-            sc, _keep = self._scene(model, need_latent=True, gen_shape=gshape)
-            lz = _keep[6] if gshape is not None else None
-        elif gen:    # the forward of render_image under autograd: the frame without maps, as before
-            packed = self._mlp_shape_general(model, shape, f16)
-            sc, _keep = self._scene(model, need_latent=True)
-        else:
-            packed = self._mlp(model)
-            sc, _keep = self._scene(model, need_latent=True, packed_mlp=packed)
-        assert SB == sc.SB
-        K = int(self.n_samples)
-        cfg = self._cfg(K, self.n_depth_candidates, self.n_gaussian)
-        cam = _lib.DinerTargetCam()
-        cam.extrinsics, cam.intrinsics, cam.z_near, cam.z_far = E.data_ptr(), Ki.data_ptr(), zn.data_ptr(), zf.data_ptr()
-        cam.H, cam.W = int(H), int(W)
-        prec = _lib.PRECISIONS[self.precision]
-        L = _lib.lib()
-        self._poll_status()
-        seed = self._next_seed()
-        ix = self._index(model)   # another lookup mode than bilinear / border: the _ix (bicubic: _bc) entry points, through ctypes
-        rays_out = None if saved is None else torch.empty((SB, H * W, 8), dtype=torch.float32, device=dev)
-        if gen:
-            cs = shape.c_struct()
-            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, _lib.PRECISIONS["fp32"])),
-                             dtype=torch.float32, device=dev)
-            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
-            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            fn, name, look, tail = self._gen_call("render_image_gen", f16, model, lz)
-            check(fn(C.byref(sc), *look, C.byref(cs), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), seed, _ptr(ws),
-                     _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev), *tail), name)
-            self.last_route, self.last_binding = self._gen_route(f16, lz), "ctypes"
-        elif ix is not None:
-            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, prec)), dtype=torch.float32, device=dev)
-            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
-            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            check(L.diner_render_image_ix(C.byref(sc), C.byref(ix), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec,
-                                          seed, _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)),
-                  "diner_render_image_ix")
-        elif self.binding == "torch_ops" and saved is None:
-            from . import ops as _ops
-            maps_t, poses_t, focal_t, c_t, latent_t, linz_t = _keep
-            rgb, depth = _ops.load().render_image(maps_t, poses_t, focal_t, c_t, latent_t, linz_t, packed, E, Ki, zn, zf, int(H), int(W), sc.image_w,
-                                                  sc.image_h, sc.feature_padding, sc.num_freqs, sc.freq_factor, cfg.n_candidates, cfg.n_samples,
-                                                  cfg.n_gaussian, cfg.depth_diff_max, bool(self.white_bkgd), prec,
-                                                  seed - (1 << 64) if seed >= (1 << 63) else seed, self._status_word(dev))
-        else:
-            ws = torch.empty(int(L.diner_render_image_workspace_floats(SB, int(H), int(W), K, sc.NV, prec)), dtype=torch.float32, device=dev)
-            rgb = torch.empty((SB, H * W, 3), dtype=torch.float32, device=dev)
-            depth = torch.empty((SB, H * W), dtype=torch.float32, device=dev)
-            check(L.diner_render_image(C.byref(sc), _ptr(packed), C.byref(cam), C.byref(cfg), int(bool(self.white_bkgd)), prec, seed,
-                                       _ptr(ws), _ptr(rays_out), _ptr(rgb), _ptr(depth), None, _ptr(self._status_word(dev)), _stream(dev)), "diner_render_image")
-        if not gen:
-            self.last_route = "points_mlp_f16" if self.precision == "f16x3" else "points_mlp"
-            self.last_binding = self.binding if ix is None and saved is None else "ctypes"
-        if saved is not None:
-            n = SB * H * W
-            saved.update(rays=rays_out, z=ws[n * 8:n * (8 + K)].view(SB, H * W, K).clone(), rgb=rgb, depth=depth)
-        self._after_launch(dev, sync=self.finite_check != "off")    # once per frame: a NaN image never leaves this function
-        rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
-        if return_depth:
-            return rgb, depth.view(SB, H, W, 1).permute(0, 3, 1, 2)
-        return rgb
+        """render_image's inference launch.  ``saved`` (a dict): the forward of an autograd frame, which is the training path's -- exact
+        fp32 on a shape-general route, the ctypes binding (the torch op gives no access to its workspace) -- and fills it (``_launch``)."""
+        route = self._resolve(model, f16_ok=saved is None, stacklevel=5)
+        H, W = int(H), int(W)
+        with torch.no_grad():
+            dev = target_extrinsics.device
+            SB = target_extrinsics.shape[0]
+            E, Ki = _f32c(target_extrinsics), _f32c(target_intrinsics)
+            zn = torch.as_tensor(z_near, dtype=torch.float32, device=dev).expand(SB).contiguous()
+            zf = torch.as_tensor(z_far, dtype=torch.float32, device=dev).expand(SB).contiguous()
+            # examined once per frame: a NaN image never leaves this function
+            rgb, depth, _ = self._launch(model, route, cam=(E, Ki, zn, zf, H, W), saved=saved, sync=self.finite_check != "off")
+            rgb = rgb.view(SB, H, W, 3).permute(0, 3, 1, 2)
+            if return_depth:
+                return rgb, depth.view(SB, H, W, 1).permute(0, 3, 1, 2)
+            return rgb
 
-    def _forward_train(self, model, rays, want_weights, noise=None, z_samples=None):
-        """Training path (reference DINER.calc_losses, src/models/diner.py:217-290): sampler under no_grad
-        (src/models/nerf_renderer.py:65), then the differentiable point evaluation + compositing of
-        diner_amd/training.py (HIP building blocks; gradients to the MLP parameters, encoder.latent, the rays, the source
-        cameras and encoder.depths)."""
-        from . import training
+    def _train_prelude(self, model, rays, noise, z_samples, d_latent):
+        """what both training paths start with -> (z, scene, the tensors it points into): the samples (injected, or drawn under no_grad
+        as src/models/nerf_renderer.py:65 does) and the scene without a packed latent, ``encoder.latent``'s own shape written into it"""
         r = self._check_rays(rays)
-        SB, NR, _ = r.shape
-        K = int(self.n_samples)
         with torch.no_grad():
             if z_samples is not None:
                 z = _f32c(z_samples)
             else:
-                z = self._sample(r, model, K, self.n_depth_candidates, self.n_gaussian, 0.05, noise, None)["z"]
-            sc, _keep = self._scene(model, need_latent=False)
-        assert SB == sc.SB
+                z = self._sample(r, model, int(self.n_samples), self.n_depth_candidates, self.n_gaussian, 0.05, noise, None)["z"]
+            sc, keep = self._scene(model, need_latent=False)
+        assert r.shape[0] == sc.SB
         lat = model.encoder.latent
-        assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == 512
+        assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == d_latent
         sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
-        rgb, depth, weights = training.render_with_grad(self, model, rays, z, sc, keep=_keep)
+        return z, sc, keep
+
+    def _forward_train(self, model, rays, want_weights, noise=None, z_samples=None):
+        """Training path (reference DINER.calc_losses, src/models/diner.py:217-290): sampler under no_grad, then the differentiable
+        point evaluation + compositing of diner_amd/training.py (HIP building blocks; gradients to the MLP parameters, encoder.latent,
+        the rays, the source cameras and encoder.depths)."""
+        from . import training
+        z, sc, keep = self._train_prelude(model, rays, noise, z_samples, 512)
+        rgb, depth, weights = training.render_with_grad(self, model, rays, z, sc, keep=keep)
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
     def _forward_train_gen(self, model, rays, want_weights, shape: MlpShape, noise=None, z_samples=None):
@@ -1174,21 +1152,9 @@ class NeRFRendererDGS(torch.nn.Module):
             self.effective_precision = "f16x3"
         else:
             self._settle_fp32(shape, stacklevel=4)
-        r = self._check_rays(rays)
-        SB, NR, _ = r.shape
-        K = int(self.n_samples)
-        with torch.no_grad():
-            if z_samples is not None:
-                z = _f32c(z_samples)
-            else:
-                z = self._sample(r, model, K, self.n_depth_candidates, self.n_gaussian, 0.05, noise, None)["z"]
-            sc, _keep = self._scene(model, need_latent=False)
-        assert SB == sc.SB
-        lat = model.encoder.latent
-        assert lat.shape[:2] == (sc.SB, sc.NV) and lat.shape[2] == shape.d_latent
-        sc.C, sc.h, sc.w = int(lat.shape[2]), int(lat.shape[3]), int(lat.shape[4])
+        z, sc, keep = self._train_prelude(model, rays, noise, z_samples, shape.d_latent)
         kw = dict(f16=True) if f16 else {}   # (the fp32 call keeps the argument list it had)
-        rgb, depth, weights = training_gen.render_with_grad(self, model, rays, z, sc, shape, keep=_keep, **kw)
+        rgb, depth, weights = training_gen.render_with_grad(self, model, rays, z, sc, shape, keep=keep, **kw)
         self.last_route, self.last_binding = ("train_gen_f16" if f16 else "train_gen"), "ctypes"
         return RenderOutput(fine=self._format_outputs(weights, rgb, depth, want_weights=want_weights))
 
